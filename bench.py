@@ -12,6 +12,11 @@ the same step (torch-CPU fp32 restatement of the reference loop) timed on this b
 `--mode eval` measures the other half of the named hot path the same way: engine.evaluate (reference
 engine.py:145-225) over device-resident batches of int(1.5 * 256) = 384 images (the reference's eval batch,
 train.py:167), BatchNorm folded into the filters.
+
+A plain run sets up, warms up, times the `--steps` steps and prints the headline fields (`metric`, `value`, `unit`,
+`ms_per_step` = milliseconds of one timed step, ...).  `--full` adds, after the timed steps, everything else listed above:
+the host enqueue burst, the per-class event pass with the roofline figures and PMC traffic, the CPU baseline and, at N > 1,
+the RCCL op_sel lint.  `--dump-outputs DIR` writes what the timed steps returned (see dump_outputs) as DIR/<name>.npy.
 """
 import argparse
 import contextlib
@@ -241,7 +246,43 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
-def main():
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all arrays together
+DUMP_SAMPLE = 32768           # elements written of a larger tensor: the same seeded sample of positions on every run
+
+
+def dump_outputs(out_dir, stats, states):
+    """--dump-outputs DIR: what the timed call returned to its caller -- its stats dict, as stats.<key>.npy (float64; the
+    per-class precision_<i> / recall_<i> of evaluate as one array each) -- and the state the caller's model (and EMA model)
+    holds after the last timed step, as <prefix>.<name>.npy (float32).  A tensor of more than DUMP_SAMPLE elements is written
+    as the elements at DUMP_SAMPLE positions drawn from a fixed seed, so that two builds are compared at the same positions."""
+    import numpy as np
+    import torch
+    arrays, per_class = {}, {}
+    for k, v in stats.items():
+        head, _, idx = k.rpartition("_")
+        if head in ("precision", "recall") and idx.isdigit():
+            per_class.setdefault(head, {})[int(idx)] = v
+        else:
+            arrays["stats." + k] = np.asarray(v, dtype=np.float64)
+    for head, vals in per_class.items():
+        arrays["stats." + head] = np.asarray([vals[i] for i in sorted(vals)], dtype=np.float64)
+    for prefix, sd in states:
+        for name, t in sd.items():
+            a = t.detach().to(dtype=torch.float32, device="cpu").numpy()
+            if a.size > DUMP_SAMPLE:
+                pos = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+                a = a.reshape(-1)[pos]
+            arrays[f"{prefix}.{name}"] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes in {len(arrays)} arrays, over the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays), total
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -260,7 +301,17 @@ def main():
     ap.add_argument("--transport", default=None, choices=["torch", "rccl"],
                     help="gradient transport at N > 1: torch.distributed's RCCL process group (default) or the library's own "
                          "RCCL communicator (icamd_allreduce_bucket_launch)")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: host enqueue burst, per-kernel-class "
+                         "roofline pass, PMC traffic, CPU baseline, the RCCL op_sel lint at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they returned and the model state after the last one as "
+                         "DIR/<name>.npy (at most 64 MB; rank 0)")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     is_eval = args.mode == "eval"
     if args.batch is None:
         args.batch = 384 if is_eval else 256     # reference train.py:167: the eval loader uses int(1.5 * batch_size)
@@ -321,7 +372,7 @@ def main():
     if world > 1:
         log(f"gradient transport: {model.reducer.transport}, communicator reports {ranks_seen} ranks, "
             f"{len(model.reducer.buckets)} buckets")
-        if rank == 0:     # the packed-fp32 op_sel hazard guard for the RCCL kernels that co-run with the step
+        if rank == 0 and args.full:     # the packed-fp32 op_sel hazard guard for the RCCL kernels that co-run with the step
             guard = foreign_codeobj_guard(lib)
             log(f"RCCL version {guard['rccl_version']} ({guard['rccl_library']}): op_sel lint {guard['verdict']}")
     opt = create_optimizer("adamw", 1e-3, 5e-4, net)
@@ -375,39 +426,47 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     value = world * B * args.steps / dt
-    log(f"timed {args.steps} steps: {1e3 * dt / args.steps:.2f} ms/step, {value:.1f} img/s")
+    ms_step = 1e3 * dt / args.steps
+    log(f"timed {args.steps} steps: {ms_step:.2f} ms/step, {value:.1f} img/s")
+    if args.dump_outputs and rank == 0:
+        states = [("model", net.state_dict())] + ([("ema", model_ema.state_dict())] if model_ema is not None else [])
+        n, nbytes = dump_outputs(args.dump_outputs, stats, states)
+        log(f"wrote {n} arrays ({nbytes / 1e6:.1f} MB) of the timed steps' outputs to {args.dump_outputs}")
 
-    # host_enqueue_ms: a burst of 3 steps from an idle GPU (fewer launches than the queue holds, so no launch call blocks): the
-    # time until the loop reaches its single wait = Python + ctypes + HIP launch cost of a step, with the device never waited on
-    nburst = min(3, args.steps)
-    barrier()
-    run(nburst, 0)
-    enqueue_s = (evaluate if is_eval else train_one_epoch).last_enqueue_s / nburst
-    barrier()
-    log(f"host enqueue {1e3 * enqueue_s:.2f} ms/step (burst of {nburst} from an idle GPU)")
+    def full_measurements():
+        """--full: the passes and figures beyond the headline, run after it on every rank; rank 0 returns the fields they add
+        to the result line."""
+        # host_enqueue_ms: a burst of 3 steps from an idle GPU (fewer launches than the queue holds, so no launch call blocks): the
+        # time until the loop reaches its single wait = Python + ctypes + HIP launch cost of a step, with the device never waited on
+        nburst = min(3, args.steps)
+        barrier()
+        run(nburst, 0)
+        enqueue_s = (evaluate if is_eval else train_one_epoch).last_enqueue_s / nburst
+        barrier()
+        log(f"host enqueue {1e3 * enqueue_s:.2f} ms/step (burst of {nburst} from an idle GPU)")
 
-    # Second pass over the same workload with HIP events recorded around every C-ABI call on the launch stream
-    # (icamd_prof_*): per-kernel-class durations and the algorithmic bytes / flops the C ABI books per call.  Kept out of
-    # the headline timing because the ~1500 event records per step cost ~10 % of the step.
-    prof_steps = min(args.steps, 10)
-    # The timed region above runs the weight gradients on a second stream beside the main chain; co-running kernels
-    # stretch one another, so for per-kernel rates this pass keeps everything on ONE stream (the rocprofv3 summaries of
-    # both modes are in profiles/).
-    net.wgrad_side_stream = False
-    hip.prof_collect()
-    lib.icamd_prof_enable(1)
-    barrier()
-    t1 = time.perf_counter()
-    run(prof_steps, 0)
-    barrier()
-    dt_prof = time.perf_counter() - t1
-    lib.icamd_prof_enable(0)
-    net.wgrad_side_stream = True
-    prof = hip.prof_collect(work=True)
-    psteps = prof_steps
+        # Second pass over the same workload with HIP events recorded around every C-ABI call on the launch stream
+        # (icamd_prof_*): per-kernel-class durations and the algorithmic bytes / flops the C ABI books per call.  Kept out of
+        # the headline timing because the ~1500 event records per step cost ~10 % of the step.
+        prof_steps = min(args.steps, 10)
+        # The timed region above runs the weight gradients on a second stream beside the main chain; co-running kernels
+        # stretch one another, so for per-kernel rates this pass keeps everything on ONE stream (the rocprofv3 summaries of
+        # both modes are in profiles/).
+        net.wgrad_side_stream = False
+        hip.prof_collect()
+        lib.icamd_prof_enable(1)
+        barrier()
+        t1 = time.perf_counter()
+        run(prof_steps, 0)
+        barrier()
+        dt_prof = time.perf_counter() - t1
+        lib.icamd_prof_enable(0)
+        net.wgrad_side_stream = True
+        prof = hip.prof_collect(work=True)
+        psteps = prof_steps
+        if rank != 0:
+            return None
 
-    if rank == 0:
-        ms_step = 1e3 * dt / args.steps
         # ---- every class: time, calls, algorithmic work (booked per call by the C ABI), both roof fractions
         classes = {}
         for k, (ms, calls, nbytes, flops) in prof.items():
@@ -507,6 +566,21 @@ def main():
                    "cpu_model": cpu_model_string(),
                    "sample": f"{args.cpu_steps} timed steps of batch 32 after {args.cpu_warmup} warm-up steps, torch-CPU fp32 "
                              f"restatement of {what}, {args.arch} {HW}x{HW}" + ("" if is_eval else ", AdamW+label smoothing")}
+        return {"foreign_codeobj_lint": guard, "roofline": roofline, "roofline_classes": classes, "roofline_step": step,
+                "host_enqueue_ms": round(1e3 * enqueue_s, 3),
+                "host_enqueue_frac": round(1e3 * enqueue_s / ms_step, 3),
+                "host_enqueue_note": f"Python + ctypes + HIP launch time of one step, burst of {nburst} steps from an idle GPU (no launch "
+                                     f"blocks); over the {args.steps} timed steps the loop reached its wait after "
+                                     f"{round(1e3 * enqueue_timed_s / args.steps, 2)} ms/step, which includes blocking on the full HIP queue",
+                "cpu_baseline": cpu,
+                "kernels": {k: {"ms_per_step": c["ms_per_step"], "calls_per_step": c["calls_per_step"]} for k, c in classes.items()},
+                "kernel_source_hash": kernel_source_hash(),
+                "kernel_timing": {"method": "HIP events on the launch stream around every C-ABI call; separate single-stream pass "
+                                            "(the timed region overlaps weight gradients on a second stream)",
+                                  "steps": psteps, "ms_per_step_with_events": round(1e3 * dt_prof / psteps, 3)}}
+
+    full = full_measurements() if args.full else None
+    if rank == 0:
         label = {"resnet50": "ResNet-50", "vit_base_patch16_224": "ViT-B/16", "convnext_tiny": "ConvNeXt-T"}.get(args.arch, args.arch)
         if args.mixup and not is_eval:
             label += " + mixup/cutmix + EMA"
@@ -523,21 +597,11 @@ def main():
                "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
                "config": {"workload": workload, "global_batch": B * world, "parallelism": f"dp{world}"},
-               "n_ranks_seen": ranks_seen, "foreign_codeobj_lint": guard, "roofline": roofline, "roofline_classes": classes,
-               "roofline_step": step,
-               "host_enqueue_ms": round(1e3 * enqueue_s, 3),
-               "host_enqueue_frac": round(1e3 * enqueue_s / ms_step, 3),
-               "host_enqueue_note": f"Python + ctypes + HIP launch time of one step, burst of {nburst} steps from an idle GPU (no launch "
-                                    f"blocks); over the {args.steps} timed steps the loop reached its wait after "
-                                    f"{round(1e3 * enqueue_timed_s / args.steps, 2)} ms/step, which includes blocking on the full HIP queue",
-               "cpu_baseline": cpu,
-               "kernels": {k: {"ms_per_step": c["ms_per_step"], "calls_per_step": c["calls_per_step"]} for k, c in classes.items()},
-               "kernel_source_hash": kernel_source_hash(),
-               "kernel_timing": {"method": "HIP events on the launch stream around every C-ABI call; separate single-stream pass "
-                                           "(the timed region overlaps weight gradients on a second stream)",
-                                 "steps": psteps, "ms_per_step_with_events": round(1e3 * dt_prof / psteps, 3)},
-               ("eval_stats" if is_eval else "train_stats"): {k: round(v, 5) for k, v in stats.items()
-                                                              if not k.startswith(("precision_", "recall_"))}}
+               "n_ranks_seen": ranks_seen}
+        if full is not None:
+            out.update(full)
+        out["eval_stats" if is_eval else "train_stats"] = {k: round(v, 5) for k, v in stats.items()
+                                                            if not k.startswith(("precision_", "recall_"))}
         print(json.dumps(out))
     if world > 1:
         model.shutdown()            # destroys the library's own communicator when one was made

@@ -201,6 +201,39 @@ def test_bench_self_launches_its_ranks_before_touching_the_gpu(monkeypatch):
     assert "torch" not in vars(bench), "the parent imported torch before launching"
 
 
+def test_bench_options_default_to_the_headline_only():
+    """A plain bench.py run times the headline only: the extra passes come with --full, the outputs with --dump-outputs."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.steps == 3 and a.warmup == 1 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "outs"])
+    assert a.full is True and a.dump_outputs == "outs"
+
+
+def test_bench_dump_outputs_writes_fixed_samples(tmp_path):
+    """bench.dump_outputs: stats as float64 (evaluate's per-class keys as one array each), model state as float32, a tensor
+    larger than DUMP_SAMPLE as the same seeded sample of positions every time; 64 MB in all at most."""
+    import bench
+    from oracle.resnet_ref import ResNetRef
+    sd = ResNetRef("resnet50", 1000).state_dict()
+    stats = {"loss": 6.9, "acc1": 0.5, "precision_0": 0.25, "precision_1": 0.75, "recall_1": 1.0, "recall_0": 0.0}
+    n, total = bench.dump_outputs(str(tmp_path / "a"), stats, [("model", sd)])
+    bench.dump_outputs(str(tmp_path / "b"), stats, [("model", sd)])
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert n == len(files) == 4 + len(sd) and total <= bench.DUMP_LIMIT_BYTES
+    assert np.load(tmp_path / "a" / "stats.precision.npy").tolist() == [0.25, 0.75]
+    assert np.load(tmp_path / "a" / "stats.recall.npy").tolist() == [0.0, 1.0]
+    assert np.load(tmp_path / "a" / "stats.loss.npy").dtype == np.float64
+    big = "layer4.0.conv2.weight"
+    a = np.load(tmp_path / "a" / f"model.{big}.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and sd[big].numel() > bench.DUMP_SAMPLE
+    assert set(a.tolist()) <= set(sd[big].reshape(-1).tolist())
+    small = np.load(tmp_path / "a" / "model.fc.bias.npy")
+    assert small.dtype == np.float32 and np.array_equal(small, sd["fc.bias"].numpy())
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
 def test_meters_match_reference_semantics():
     from imageclassification_amd.utils import MetricLogger, SmoothedValue
     m = SmoothedValue(window_size=4)

@@ -1,4 +1,4 @@
-"""Print value / ms_per_step and the per-class kernel times of one bench.py JSON line (stdin). usage: bench.py ... | bench_classes.py [tag]"""
+"""Print value / ms_per_step and the per-class kernel times of one bench.py JSON line (stdin). usage: bench.py --full ... | bench_classes.py [tag]"""
 import json, sys
 tag = sys.argv[1] if len(sys.argv) > 1 else ""
 d = json.loads(sys.stdin.read())

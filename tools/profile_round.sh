@@ -13,25 +13,25 @@ VIT="--arch vit_base_patch16_224"
 CNX="--arch convnext_tiny --mixup"
 if [ "$PART" = "C" ]; then
   # bench lines only (after part B's PMC summaries have been copied into profiles/: roofline.traffic is then non-null)
-  python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_r50.json 2> $O/bench_r50.err
-  python3 $R/bench.py $VIT --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vit.json 2> $O/bench_vit.err
-  python3 $R/bench.py $CNX --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cnx.json 2> $O/bench_cnx.err
-  python3 $R/bench.py --mode eval --steps 20 --warmup 5 > $O/bench_eval.json 2> $O/bench_eval.err
+  python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_r50.json 2> $O/bench_r50.err
+  python3 $R/bench.py --full $VIT --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vit.json 2> $O/bench_vit.err
+  python3 $R/bench.py --full $CNX --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cnx.json 2> $O/bench_cnx.err
+  python3 $R/bench.py --full --mode eval --steps 20 --warmup 5 > $O/bench_eval.json 2> $O/bench_eval.err
 elif [ "$PART" = "A" ]; then
   echo "== bench lines"; date
-  python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_r50.json 2> $O/bench_r50.err
-  python3 $R/bench.py $VIT --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vit.json 2> $O/bench_vit.err
-  python3 $R/bench.py $CNX --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cnx.json 2> $O/bench_cnx.err
-  python3 $R/bench.py --mode eval --steps 20 --warmup 5 > $O/bench_eval.json 2> $O/bench_eval.err
+  python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_r50.json 2> $O/bench_r50.err
+  python3 $R/bench.py --full $VIT --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_vit.json 2> $O/bench_vit.err
+  python3 $R/bench.py --full $CNX --steps 10 --warmup 3 --no-cpu-baseline > $O/bench_cnx.json 2> $O/bench_cnx.err
+  python3 $R/bench.py --full --mode eval --steps 20 --warmup 5 > $O/bench_eval.json 2> $O/bench_eval.err
   echo "== kernel stats"; date
   RAWA=/tmp/icamd_prof_raw_a; rm -rf $RAWA; mkdir -p $RAWA
-  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_r50 -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_r50.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_r50 -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_r50.log 2>&1
   export ICAMD_WGRAD_STREAM=0
-  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_r50_1s -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_r50_1s.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_r50_1s -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_r50_1s.log 2>&1
   unset ICAMD_WGRAD_STREAM
-  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_vit -- python3 $R/bench.py $VIT --steps 5 --warmup 2 --no-cpu-baseline > $O/stats_vit.log 2>&1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_cnx -- python3 $R/bench.py $CNX --steps 5 --warmup 2 --no-cpu-baseline > $O/stats_cnx.log 2>&1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_eval -- python3 $R/bench.py --mode eval --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_eval.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_vit -- python3 $R/bench.py --full $VIT --steps 5 --warmup 2 --no-cpu-baseline > $O/stats_vit.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_cnx -- python3 $R/bench.py --full $CNX --steps 5 --warmup 2 --no-cpu-baseline > $O/stats_cnx.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $RAWA/stats_eval -- python3 $R/bench.py --full --mode eval --steps 10 --warmup 2 --no-cpu-baseline > $O/stats_eval.log 2>&1
   for d in stats_r50 stats_r50_1s stats_vit stats_cnx stats_eval; do
     mkdir -p $O/$d
     cp $(find $RAWA/$d -name "*kernel_stats.csv" | head -1) $O/$d/kernel_stats.csv
@@ -46,14 +46,14 @@ else
   export ICAMD_WGRAD_STREAM=0
   for a in r50 vit cnx eval; do
     case $a in r50) ARGS="";; vit) ARGS="$VIT";; cnx) ARGS="$CNX";; eval) ARGS="--mode eval";; esac
-    rocprofv3 --pmc FETCH_SIZE -d $RAW/pmc_fetch_$a -- python3 $R/bench.py $ARGS --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_fetch_$a.log 2>&1
-    rocprofv3 --pmc WRITE_SIZE -d $RAW/pmc_write_$a -- python3 $R/bench.py $ARGS --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_write_$a.log 2>&1
+    rocprofv3 --pmc FETCH_SIZE -d $RAW/pmc_fetch_$a -- python3 $R/bench.py --full $ARGS --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_fetch_$a.log 2>&1
+    rocprofv3 --pmc WRITE_SIZE -d $RAW/pmc_write_$a -- python3 $R/bench.py --full $ARGS --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_write_$a.log 2>&1
     date
   done
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma.log 2>&1
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma_vit -- python3 $R/bench.py $VIT --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_vit.log 2>&1
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma_cnx -- python3 $R/bench.py $CNX --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_cnx.log 2>&1
-  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma_eval -- python3 $R/bench.py --mode eval --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_eval.log 2>&1
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma.log 2>&1
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma_vit -- python3 $R/bench.py --full $VIT --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_vit.log 2>&1
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma_cnx -- python3 $R/bench.py --full $CNX --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_cnx.log 2>&1
+  rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES --output-format csv -d $RAW/pmc_mfma_eval -- python3 $R/bench.py --full --mode eval --steps 3 --warmup 1 --no-cpu-baseline > $O/pmc_mfma_eval.log 2>&1
   unset ICAMD_WGRAD_STREAM
   for d in pmc_mfma pmc_mfma_vit pmc_mfma_cnx pmc_mfma_eval; do
     mkdir -p $O/$d

@@ -9,7 +9,7 @@ cp $L /tmp/lib_keep.so
 for rep in 1 2 3; do for v in "$@"; do
   cp tools/attn_ab/lib_$v.so $L
   echo -n "$v  "; python3 tools/bench_attn.py 256 20 2>&1 | grep -v amdgpu.ids | cut -c1-100
-  echo -n "$v  vit "; python3 bench.py --arch vit_base_patch16_224 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
+  echo -n "$v  vit "; python3 bench.py --full --arch vit_base_patch16_224 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); c = d['roofline_classes']
 print(d['ms_per_step'], 'attn_bwd', c['attn_bwd']['ms_per_step'], 'attn_fwd', c['attn_fwd']['ms_per_step'])"

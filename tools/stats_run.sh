@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $R/bench.py --steps $STEPS --warmup 2 --no-cpu-baseline "$@" > $O/run.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O -- python3 $R/bench.py --full --steps $STEPS --warmup 2 --no-cpu-baseline "$@" > $O/run.log 2>&1
 cd $R
 F=$(find $O -name "*kernel_stats.csv" | head -1)
 python3 - "$F" "$STEPS" <<'PY'
