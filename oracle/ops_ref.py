@@ -23,9 +23,72 @@ def nchw_to_nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
 
+# ---- accumulation precision -------------------------------------------------------------------------
+# Every function below accumulates in fp32 by default (acc=torch.float32: the pinned behaviour).  With acc=torch.float64 the
+# same formula, with the same bf16 rounding points, is accumulated in fp64 -- the reference of the full-size layer tests,
+# which run it on the GPU on tensors of any device.  Convolutions then run as one fp64 matmul per filter tap (fp64
+# convolution has no vendor kernel there).
+def _wide(acc):
+    """True for the fp64 path; the default fp32 path otherwise.  Any other dtype would be a reference narrower than fp32."""
+    assert acc in (torch.float32, torch.float64), acc
+    return acc == torch.float64
+
+
+def _taps(xp, KH, KW, stride, OH, OW):
+    """(r, s, view of the padded NHWC input read by tap (r, s)) for every filter tap."""
+    for r in range(KH):
+        for s in range(KW):
+            yield r, s, xp[:, r:r + stride * (OH - 1) + 1:stride, s:s + stride * (OW - 1) + 1:stride, :]
+
+
+def _out_hw(H, W, KH, KW, stride, pad):
+    return (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+
+
+def _conv_fwd_taps(x, w, stride, pad):
+    N, H, W, Cin = x.shape
+    Cout, KH, KW, _ = w.shape
+    OH, OW = _out_hw(H, W, KH, KW, stride, pad)
+    xp = F.pad(x, (0, 0, pad, pad, pad, pad))
+    y = torch.zeros(N * OH * OW, Cout, dtype=x.dtype, device=x.device)
+    for r, s, xs in _taps(xp, KH, KW, stride, OH, OW):
+        y.addmm_(xs.reshape(-1, Cin), w[:, r, s, :].t())
+    return y.reshape(N, OH, OW, Cout)
+
+
+def _conv_dgrad_taps(dy, w, in_hw, stride, pad):
+    N, OH, OW, Cout = dy.shape
+    _, KH, KW, Cin = w.shape
+    H, W = in_hw
+    dxp = torch.zeros(N, H + 2 * pad + stride, W + 2 * pad + stride, Cin, dtype=dy.dtype, device=dy.device)
+    dy2 = dy.reshape(-1, Cout)
+    for r, s, view in _taps(dxp, KH, KW, stride, OH, OW):
+        view += (dy2 @ w[:, r, s, :]).reshape(N, OH, OW, Cin)
+    return dxp[:, pad:pad + H, pad:pad + W, :]
+
+
+def _conv_wgrad_taps(x, dy, ksize, stride, pad):
+    N, OH, OW, Cout = dy.shape
+    Cin = x.shape[-1]
+    KH, KW = ksize
+    xp = F.pad(x, (0, 0, pad, pad, pad, pad))
+    dy2t = dy.reshape(-1, Cout).t()
+    dw = torch.empty(Cout, KH, KW, Cin, dtype=x.dtype, device=x.device)
+    for r, s, xs in _taps(xp, KH, KW, stride, OH, OW):
+        dw[:, r, s, :] = dy2t @ xs.reshape(-1, Cin)
+    return dw
+
+
 # ---- convolution: icamd_conv2d_fwd / _dgrad / _wgrad -----------------------------------------------
-def conv2d_fwd(x_nhwc, w_krsc, stride, pad, bias=None, addend=None):
+def conv2d_fwd(x_nhwc, w_krsc, stride, pad, bias=None, addend=None, acc=torch.float32):
     """x [N,H,W,Cin], w [Cout,KH,KW,Cin] (bf16-representable fp32). Returns (y rounded to bf16 grid, fp32)."""
+    if _wide(acc):
+        y = _conv_fwd_taps(x_nhwc.to(acc), w_krsc.to(acc), stride, pad)
+        if bias is not None:
+            y = y + bias.to(acc)
+        if addend is not None:
+            y = y + addend.to(acc)
+        return bf16_round(y)
     x = nhwc_to_nchw(x_nhwc.float())
     w = w_krsc.float().permute(0, 3, 1, 2).contiguous()
     y = F.conv2d(x, w, None, stride=stride, padding=pad)
@@ -43,7 +106,12 @@ def conv2d_stats(y_nhwc):
     return y.sum(0), (y * y).sum(0)
 
 
-def conv2d_dgrad(dy_nhwc, w_krsc, in_hw, stride, pad, addend=None):
+def conv2d_dgrad(dy_nhwc, w_krsc, in_hw, stride, pad, addend=None, acc=torch.float32):
+    if _wide(acc):
+        dx = _conv_dgrad_taps(dy_nhwc.to(acc), w_krsc.to(acc), in_hw, stride, pad)
+        if addend is not None:
+            dx = dx + addend.to(acc)
+        return bf16_round(dx)
     dy = nhwc_to_nchw(dy_nhwc.float())
     w = w_krsc.float().permute(0, 3, 1, 2).contiguous()
     N = dy.shape[0]
@@ -54,8 +122,10 @@ def conv2d_dgrad(dy_nhwc, w_krsc, in_hw, stride, pad, addend=None):
     return bf16_round(dx)
 
 
-def conv2d_wgrad(x_nhwc, dy_nhwc, ksize, stride, pad):
-    """Returns dw [Cout,KH,KW,Cin] fp32 (not rounded: the HIP path keeps weight gradients in fp32)."""
+def conv2d_wgrad(x_nhwc, dy_nhwc, ksize, stride, pad, acc=torch.float32):
+    """Returns dw [Cout,KH,KW,Cin] fp32 (not rounded: the HIP path keeps weight gradients in fp32); in `acc` if that is wider."""
+    if _wide(acc):
+        return _conv_wgrad_taps(x_nhwc.to(acc), dy_nhwc.to(acc), ksize, stride, pad)
     x = nhwc_to_nchw(x_nhwc.float())
     dy = nhwc_to_nchw(dy_nhwc.float())
     Cout, Cin = dy.shape[1], x.shape[1]
@@ -82,7 +152,12 @@ def bn_train_coeffs(y_nhwc, gamma, beta, running_mean, running_var, momentum, ep
     return meanf, invstd, scale, shift, rm, rv
 
 
-def bn_apply(y_nhwc, scale, shift, residual=None, relu=True):
+def bn_apply(y_nhwc, scale, shift, residual=None, relu=True, acc=torch.float32):
+    if _wide(acc):
+        out = y_nhwc.to(acc) * scale.to(acc) + shift.to(acc)
+        if residual is not None:
+            out = out + residual.to(acc)
+        return bf16_round(out.clamp_min(0) if relu else out)
     out = torch.addcmul(shift.float(), y_nhwc.float(), scale.float())  # fma(y, scale, shift)
     if residual is not None:
         out = out + residual.float()
@@ -91,9 +166,21 @@ def bn_apply(y_nhwc, scale, shift, residual=None, relu=True):
     return bf16_round(out)
 
 
-def bn_bwd(dout, act, y, mean, invstd, scale, relu=True):
+def bn_bwd(dout, act, y, mean, invstd, scale, relu=True, acc=torch.float32):
     """dout, act (post-activation output, or None -> recompute the mask), y: NHWC. Returns dy, dgamma, dbeta, g."""
     C = y.shape[-1]
+    if _wide(acc):
+        g = dout.to(acc)
+        if relu:
+            if act is None:
+                raise ValueError("oracle needs the activation for the mask")
+            g = g * (act > 0)
+        xhat = ((y.to(acc) - mean.to(acc)) * invstd.to(acc)).reshape(-1, C)
+        g2 = g.reshape(-1, C)
+        n = g2.shape[0]
+        sg, sgx = g2.sum(0), (g2 * xhat).sum(0)
+        dy = scale.to(acc) * (g2 - sg / n - xhat * (sgx / n))
+        return bf16_round(dy.reshape(y.shape)), sgx, sg, bf16_round(g)
     g = dout.float()
     if relu:
         if act is not None:
@@ -120,15 +207,17 @@ def maxpool3x3s2_fwd(x_nhwc):
     return nchw_to_nhwc(out), idx
 
 
-def maxpool3x3s2_bwd(dout_nhwc, x_nhwc):
-    x = nhwc_to_nchw(x_nhwc.float()).requires_grad_(True)
+def maxpool3x3s2_bwd(dout_nhwc, x_nhwc, acc=torch.float32):
+    _wide(acc)
+    x = nhwc_to_nchw(x_nhwc.detach().to(acc)).requires_grad_(True)
     out = F.max_pool2d(x, 3, 2, 1)
-    out.backward(nhwc_to_nchw(dout_nhwc.float()))
+    out.backward(nhwc_to_nchw(dout_nhwc.to(acc)))
     return bf16_round(nchw_to_nhwc(x.grad))
 
 
-def avgpool_fwd(x_nhwc):
-    return bf16_round(x_nhwc.float().mean(dim=(1, 2)))
+def avgpool_fwd(x_nhwc, acc=torch.float32):
+    _wide(acc)
+    return bf16_round(x_nhwc.to(acc).mean(dim=(1, 2)))
 
 
 def avgpool_bwd(dout_nc, hw):
@@ -293,39 +382,44 @@ def bf16_close(a, b, ulps=2.0, atol_rms=2e-3, max_frac=0.0):
 
 
 # ---- token ops: LayerNorm / GELU / attention (ViT, ConvNeXt) ---------------------------------------------------
-def layernorm_fwd(x, gamma, beta, eps):
+def layernorm_fwd(x, gamma, beta, eps, acc=torch.float32):
     """x [rows, C] bf16-representable. Returns y (bf16 grid), mean, rstd."""
-    xf = x.float()
+    _wide(acc)
+    xf = x.to(acc)
     mean = xf.mean(-1)
     var = ((xf - mean[:, None]) ** 2).mean(-1)
     rstd = torch.rsqrt(var + eps)
-    y = (xf - mean[:, None]) * rstd[:, None] * gamma.float() + beta.float()
+    y = (xf - mean[:, None]) * rstd[:, None] * gamma.to(acc) + beta.to(acc)
     return bf16_round(y), mean, rstd
 
 
-def layernorm_bwd(dy, x, gamma, eps):
+def layernorm_bwd(dy, x, gamma, eps, acc=torch.float32):
     """Gradients through torch's own layer_norm (fp32): dx (bf16 grid), dgamma, dbeta."""
-    xf = x.float().requires_grad_(True)
-    g = gamma.float().clone().requires_grad_(True)
+    _wide(acc)
+    xf = x.detach().to(acc).requires_grad_(True)
+    g = gamma.detach().to(acc).clone().requires_grad_(True)
     b = torch.zeros_like(g).requires_grad_(True)
     y = F.layer_norm(xf, (x.shape[-1],), g, b, eps)
-    y.backward(dy.float())
+    y.backward(dy.to(acc))
     return bf16_round(xf.grad), g.grad, b.grad
 
 
-def gelu_fwd(z):
-    return bf16_round(F.gelu(z.float()))
+def gelu_fwd(z, acc=torch.float32):
+    _wide(acc)
+    return bf16_round(F.gelu(z.to(acc)))
 
 
-def gelu_bwd(da, z):
-    zf = z.float().requires_grad_(True)
-    F.gelu(zf).backward(da.float())
+def gelu_bwd(da, z, acc=torch.float32):
+    _wide(acc)
+    zf = z.detach().to(acc).requires_grad_(True)
+    F.gelu(zf).backward(da.to(acc))
     return bf16_round(zf.grad)
 
 
-def attention_fwd(qkv, B, T, H, D, scale):
+def attention_fwd(qkv, B, T, H, D, scale, acc=torch.float32):
     """qkv [B*T, 3*H*D] (timm layout: reshape(B, T, 3, H, D)). Returns out [B*T, H*D] (bf16 grid), lse [B,H,T]."""
-    q, k, v = qkv.float().reshape(B, T, 3, H, D).permute(2, 0, 3, 1, 4)
+    _wide(acc)
+    q, k, v = qkv.to(acc).reshape(B, T, 3, H, D).permute(2, 0, 3, 1, 4)
     s = (q @ k.transpose(-1, -2)) * scale
     lse = torch.logsumexp(s, dim=-1)
     p = torch.softmax(s, dim=-1)
@@ -333,24 +427,47 @@ def attention_fwd(qkv, B, T, H, D, scale):
     return bf16_round(o.permute(0, 2, 1, 3).reshape(B * T, H * D)), lse
 
 
-def attention_bwd(qkv, dout, B, T, H, D, scale):
-    x = qkv.float().requires_grad_(True)
+def attention_bwd(qkv, dout, B, T, H, D, scale, acc=torch.float32):
+    _wide(acc)
+    x = qkv.detach().to(acc).requires_grad_(True)
     q, k, v = x.reshape(B, T, 3, H, D).permute(2, 0, 3, 1, 4)
     o = torch.softmax((q @ k.transpose(-1, -2)) * scale, dim=-1) @ v
-    o.permute(0, 2, 1, 3).reshape(B * T, H * D).backward(dout.float())
+    o.permute(0, 2, 1, 3).reshape(B * T, H * D).backward(dout.to(acc))
     return bf16_round(x.grad)
 
 
 # ---- ConvNeXt pieces ------------------------------------------------------------------------------------------------
-def dwconv7_fwd(x_nhwc, w_c77, bias):
+def dwconv7_fwd(x_nhwc, w_c77, bias, acc=torch.float32):
     """x [N,H,W,C], w [C,7,7] (torch depthwise layout), bias [C]. Returns y NHWC on the bf16 grid."""
     C = x_nhwc.shape[-1]
+    if _wide(acc):     # one multiply-add pass per tap
+        xp = F.pad(x_nhwc.to(acc), (0, 0, 3, 3, 3, 3))
+        N, H, W, _ = x_nhwc.shape
+        w = w_c77.to(acc)
+        y = bias.to(acc).expand(N, H, W, C).clone()
+        for r, s, xs in _taps(xp, 7, 7, 1, H, W):
+            y += xs * w[:, r, s]
+        return bf16_round(y)
     y = F.conv2d(nhwc_to_nchw(x_nhwc.float()), w_c77.float().reshape(C, 1, 7, 7), bias.float(), padding=3, groups=C)
     return bf16_round(nchw_to_nhwc(y))
 
 
-def dwconv7_bwd(x_nhwc, w_c77, dy_nhwc, addend=None):
+def dwconv7_bwd(x_nhwc, w_c77, dy_nhwc, addend=None, acc=torch.float32):
     C = x_nhwc.shape[-1]
+    if _wide(acc):     # one pass per tap: dx scatters dy through the tap, dw[:, r, s] reduces x * dy
+        N, H, W, _ = x_nhwc.shape
+        xp = F.pad(x_nhwc.to(acc), (0, 0, 3, 3, 3, 3))
+        dyw = dy_nhwc.to(acc)
+        w = w_c77.to(acc)
+        dxp = torch.zeros_like(xp)
+        dw = torch.empty(C, 7, 7, dtype=acc, device=x_nhwc.device)
+        for (r, s, xs), (_, _, dxs) in zip(_taps(xp, 7, 7, 1, H, W), _taps(dxp, 7, 7, 1, H, W)):
+            dxs += dyw * w[:, r, s]
+            dw[:, r, s] = (xs * dyw).reshape(-1, C).sum(0)
+        dx = dxp[:, 3:3 + H, 3:3 + W, :]
+        if addend is not None:
+            dx = dx + addend.to(acc)
+        return bf16_round(dx), dw
     x = nhwc_to_nchw(x_nhwc.float()).requires_grad_(True)
     w = w_c77.float().reshape(C, 1, 7, 7).clone().requires_grad_(True)
     F.conv2d(x, w, None, padding=3, groups=C).backward(nhwc_to_nchw(dy_nhwc.float()))
