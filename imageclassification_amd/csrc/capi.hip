@@ -168,7 +168,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 extern "C" {
 
-int icamd_abi_version(void) { return 5; }
+int icamd_abi_version(void) { return 6; }
 
 int icamd_prof_enable(int on) { g_prof_on = on != 0; return ICAMD_OK; }
 int icamd_prof_classes(void) { return PC_COUNT; }

@@ -6,7 +6,7 @@ Resize([s, s]) -> ToTensor -> Normalize(ImageNet mean/std) (datasets.py:139-144)
 subset of timm.create_transform the reference configures (datasets.py:124-136: RandomResizedCrop with scale=(1,1),
 ratio=(1,1) -- the whole image when it is square, timm's fallback centre crop to min(W, H) otherwise -- resized
 bicubically to the input size, hflip 0.5, vflip 0.5, colour jitter, pixel-mode random erasing); auto-augment policies
-(`--aa`) are not implemented and raise.
+(`--aa`) raise here: RandAugment runs on the GPU input pipeline only (`--gpu_aug true`, gpu_pipeline.py).
 """
 import json
 import os
@@ -98,7 +98,7 @@ class EvalTransform:
 class TrainTransform:
     def __init__(self, input_size, color_jitter=0.3, reprob=0.25, vflip=0.5, hflip=0.5, auto_augment=""):
         if auto_augment:
-            raise NotImplementedError("--aa auto-augment policies need timm and are outside the MI355X hot path")
+            raise NotImplementedError("--aa runs on the GPU input pipeline only (train.py --gpu_aug true; RandAugment 'rand-...')")
         self.size, self.cj, self.reprob, self.vflip, self.hflip = input_size, color_jitter, reprob, vflip, hflip
 
     def _jitter(self, a):

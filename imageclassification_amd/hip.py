@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libicamd.so")
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 ERRORS = {1: "ICAMD_ERR_BAD_ARG", 2: "ICAMD_ERR_UNSUPPORTED", 3: "ICAMD_ERR_WORKSPACE", 4: "ICAMD_ERR_LAUNCH"}
 
 
@@ -31,6 +31,17 @@ class ImageDesc(Structure):
                 ("crop_h", c_int), ("crop_w", c_int), ("hflip", c_int), ("vflip", c_int), ("jitter_order", c_int * 3),
                 ("jitter_factor", c_float * 3), ("erase_top", c_int), ("erase_left", c_int), ("erase_h", c_int),
                 ("erase_w", c_int), ("erase_seed", ctypes.c_uint32), ("reserved", c_int)]
+
+
+class AugOp(Structure):
+    """include/icamd.h icamd_aug_op (64 bytes): one RandAugment op of one image (kind AUG_KINDS[name], 0 = identity)."""
+    _fields_ = [("kind", c_int), ("arg", c_int), ("factor", c_float), ("fill", ctypes.c_uint8 * 3),
+                ("reserved", ctypes.c_uint8), ("affine", c_double * 6)]
+
+
+AUG_OP_BYTES = 64
+AUG_KINDS = {"identity": 0, "affine": 1, "autocontrast": 2, "equalize": 3, "invert": 4, "posterize": 5, "solarize": 6,
+             "solarize_add": 7, "color": 8, "contrast": 9, "brightness": 10, "sharpness": 11}
 
 
 class ConvDesc(Structure):
@@ -127,6 +138,9 @@ _SIGNATURES = {
     "icamd_image_pipeline": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float), POINTER(c_float), _P,
                                      _P, c_size_t, _P]),
     "icamd_image_pipeline_u8": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "icamd_image_pipeline_aug_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_image_pipeline_aug": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_float),
+                                         POINTER(c_float), _P, _P, c_size_t, _P]),
     "icamd_softmax_xent": (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, c_float, c_float, _P, _P, _P, _P]),
     "icamd_step_metrics": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
     "icamd_grad_norm_workspace_bytes": (c_size_t, []),

@@ -374,6 +374,41 @@ int icamd_image_pipeline(const uint8_t* src, const icamd_image_desc* descs, int 
  * jitter, before ToTensor): what Pillow would hold at that point */
 int icamd_image_pipeline_u8(const void* workspace, int B, int max_crop_h, int out_h, int out_w, int kmax, const uint8_t** img);
 
+/* ---- RandAugment on the GPU (ABI 6; timm rand_augment_transform with the reference's --aa, e.g. rand-m9-mstd0.5-inc1).
+ *      The host draws timm's decisions and encodes each applied op as one descriptor; the kernels do Pillow's arithmetic
+ *      (Geometry.c bicubic affine with fill, ImageOps LUTs, ImageEnhance blends, the 3x3 SMOOTH filter of Sharpness) bit
+ *      for bit, tests/test_randaugment_gpu.py.  sizeof(icamd_aug_op) == 64. */
+enum {
+  ICAMD_AUG_IDENTITY = 0,
+  ICAMD_AUG_AFFINE = 1,         /* Image.transform(size, AFFINE, affine, BICUBIC, fillcolor=fill): Rotate / Shear / Translate */
+  ICAMD_AUG_AUTOCONTRAST = 2,   /* ImageOps.autocontrast                                                                   */
+  ICAMD_AUG_EQUALIZE = 3,       /* ImageOps.equalize                                                                       */
+  ICAMD_AUG_INVERT = 4,         /* ImageOps.invert                                                                         */
+  ICAMD_AUG_POSTERIZE = 5,      /* ImageOps.posterize(img, arg bits); arg >= 8 is the identity                             */
+  ICAMD_AUG_SOLARIZE = 6,       /* ImageOps.solarize(img, threshold=arg)                                                   */
+  ICAMD_AUG_SOLARIZE_ADD = 7,   /* img.point(lut): v < 128 ? min(255, v + arg) : v                                         */
+  ICAMD_AUG_COLOR = 8,          /* ImageEnhance.Color(img).enhance(factor)                                                 */
+  ICAMD_AUG_CONTRAST = 9,       /* ImageEnhance.Contrast(img).enhance(factor)                                              */
+  ICAMD_AUG_BRIGHTNESS = 10,    /* ImageEnhance.Brightness(img).enhance(factor)                                            */
+  ICAMD_AUG_SHARPNESS = 11      /* ImageEnhance.Sharpness(img).enhance(factor)                                             */
+};
+typedef struct icamd_aug_op {
+  int32_t kind;                        /* ICAMD_AUG_*; an unknown kind is applied as the identity                     */
+  int32_t arg;                         /* posterize bits / solarize threshold / solarize-add addend                   */
+  float factor;                        /* ImageEnhance factor (Image.blend alpha)                                     */
+  uint8_t fill[3];                     /* RGB colour of output pixels that map outside the image (AFFINE)             */
+  uint8_t reserved;
+  double affine[6];                    /* Pillow's AFFINE data: output pixel centre (x+.5, y+.5) -> input coordinates  */
+} icamd_aug_op;                        /* 64 bytes */
+/* workspace of icamd_image_pipeline_aug: icamd_image_pipeline's, then a second image and the per-image LUTs */
+size_t icamd_image_pipeline_aug_workspace_bytes(int B, int max_crop_h, int out_h, int out_w, int kmax);
+/* icamd_image_pipeline, with ops (device, [B][ops_per_image], ICAMD_AUG_IDENTITY for an unused slot) applied in slot order
+ * after resize / flips / colour jitter and before ToTensor + Normalize + erasing.  0 <= ops_per_image <= 16.  The final
+ * uint8 image sits where icamd_image_pipeline_u8 points, with the same arguments. */
+int icamd_image_pipeline_aug(const uint8_t* src, const icamd_image_desc* descs, const icamd_aug_op* ops, int ops_per_image,
+                             int B, int max_crop_h, int out_h, int out_w, int filter, int kmax, const float* mean3,
+                             const float* std3, float* out_nchw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- loss + metrics (criterion engine.py:49,52,178,181; accuracy / TP-FP-FN engine.py:82-97,184-196) ---- */
 /* logits bf16 [B][ld]; targets int64; target distribution lam*onehot_s(y1) + (1-lam)*onehot_s(y2).
  * loss_rows float[B]; pred int32[B] (optional argmax); dlogits bf16 [B][ld] (optional) = (softmax - t)*gscale */

@@ -1,6 +1,8 @@
 """GPU box tool: throughput of the input pipeline on a generated JPEG folder -- the host path of datasets.TrainTransform
 (PIL bicubic resize + numpy jitter / normalise / erase, what a DataLoader worker does per sample) next to the GPU pipeline
-(host: JPEG decode only; device: icamd_image_pipeline).  usage: python tools/bench_input_pipeline.py [n_images] [batch]"""
+(host: JPEG decode only; device: icamd_image_pipeline).  With a RandAugment policy (e.g. rand-m9-mstd0.5-inc1) the GPU
+pipeline also runs icamd_image_pipeline_aug on decisions drawn for the batch, and the kernel time of both entry points is
+printed.  usage: python tools/bench_input_pipeline.py [n_images] [batch] [policy]"""
 import io
 import os
 import sys
@@ -18,6 +20,7 @@ from imageclassification_amd.gpu_pipeline import GpuImagePipeline
 def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+    policy = sys.argv[3] if len(sys.argv) > 3 else ""
     rng = np.random.RandomState(0)
     blobs = []
     for i in range(n):      # photo-like sizes, smooth content + noise so that JPEG decoding costs what photos cost
@@ -62,6 +65,29 @@ def main():
     print(f"  host decode + TrainTransform   : {n / t_host:8.1f} img/s per core   (the reference's per-worker path)")
     print(f"  GPU pipeline, host staging incl.: {reps * B / t_gpu:8.1f} img/s (one host thread packs + uploads; decode excluded)")
     print(f"  GPU pipeline kernels alone     : {Bk / t_kern:8.1f} img/s ({1e3 * t_kern:.2f} ms per batch of {Bk})")
+    if policy:
+        import random
+        from imageclassification_amd.gpu_pipeline import draw_train_params
+        pa = GpuImagePipeline(224, True, auto_augment=policy)
+        random.seed(0)
+        np.random.seed(0)
+        params = [draw_train_params(224, 0.3, 0.25, aa=pa.policy) for _ in range(B)]
+        n_ops = max(len(p["aug"]) for p in params)
+        pa(decoded[:B], params)
+        torch.cuda.synchronize()
+        src, ddev = pa._last[3], pa._last[4]
+        Bk, max_crop, kmax = pa._last[:3]
+        ops = ddev.data_ptr() + Bk * 88
+        a.record()
+        for _ in range(10):
+            hip.check(pa.lib.icamd_image_pipeline_aug(src.data_ptr(), ddev.data_ptr(), ops, n_ops, Bk, max_crop, 224, 224, 1, kmax,
+                                                      pa.mean, pa.std, out.data_ptr(), pa._ws.data_ptr(), pa._ws.numel(),
+                                                      hip.stream_ptr()))
+        b.record()
+        torch.cuda.synchronize()
+        t_aug = a.elapsed_time(b) / 10 / 1e3
+        print(f"  GPU pipeline + {policy} ({n_ops} op slots): {Bk / t_aug:8.1f} img/s ({1e3 * t_aug:.2f} ms per batch of {Bk}, "
+              f"+{1e3 * (t_aug - t_kern):.2f} ms)")
 
 
 main()

@@ -71,8 +71,8 @@ def get_args_parser():
     # additions for the MI355X build
     a("--synthetic", default=0, type=int, help="use N seeded random images instead of --data_path")
     a("--gpu_aug", type=str2bool, default=False,
-      help="run the transforms of datasets.py (resize, flips, colour jitter, normalise, random erasing) as HIP kernels on the "
-           "decoded uint8 images instead of per sample on the host (imageclassification_amd/gpu_pipeline.py)")
+      help="run the transforms of datasets.py (resize, flips, colour jitter or --aa RandAugment, normalise, random erasing) as "
+           "HIP kernels on the decoded uint8 images instead of per sample on the host (imageclassification_amd/gpu_pipeline.py)")
     a("--num_classes", default=1000, type=int, help="classes of the synthetic dataset")
     return p
 
@@ -88,6 +88,11 @@ def create_model(name, num_classes, input_size=224, drop_path=0.0):
 
 
 def main(args):
+    if getattr(args, "aa", "") and not args.synthetic:   # an unsupported --aa fails here, before any GPU work
+        from imageclassification_amd.gpu_pipeline import parse_rand_augment
+        parse_rand_augment(args.aa)
+        if not getattr(args, "gpu_aug", False):
+            raise NotImplementedError("--aa runs on the GPU input pipeline only: add --gpu_aug true")
     utils.init_distributed_mode(args)
     print(args)
     device = torch.device(args.device)
@@ -115,7 +120,7 @@ def main(args):
         data_loader_train = GpuAugmentLoader(
             torch.utils.data.DataLoader(dataset_train, sampler=sampler_train, batch_size=args.batch_size,
                                         num_workers=args.num_workers, drop_last=True, collate_fn=raw_collate),
-            GpuImagePipeline(args.input_size, True, args.color_jitter, args.reprob, device=str(device)))
+            GpuImagePipeline(args.input_size, True, args.color_jitter, args.reprob, device=str(device), auto_augment=args.aa))
         data_loader_val = GpuAugmentLoader(
             torch.utils.data.DataLoader(dataset_val, sampler=sampler_val, batch_size=int(1.5 * args.batch_size),
                                         num_workers=args.num_workers, collate_fn=raw_collate),
