@@ -275,11 +275,16 @@ __global__ __launch_bounds__(256) void grad_guard_kernel(float* __restrict__ g, 
     ((f32x4*)g)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
-// dst += w*(src-dst)  (EMA of float buffers) ; with w == 1 a plain copy
+// dst += w*(src-dst)  (EMA of float buffers) ; with w == 1 a plain copy: bit-exact, whatever dst held (dst + (src - dst)
+// rounds twice, and keeps a NaN or Inf of dst)
 __global__ __launch_bounds__(256) void lerp_kernel(float* __restrict__ dst, const float* __restrict__ src, long long n,
                                                    float w, const int* __restrict__ finite_flag) {
   if (finite_flag != nullptr && *finite_flag == 0) return;
   const long long stride = (long long)gridDim.x * blockDim.x;
+  if (w == 1.f) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = src[i];
+    return;
+  }
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     dst[i] = dst[i] + w * (src[i] - dst[i]);
 }

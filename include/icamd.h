@@ -460,6 +460,8 @@ enum { ICAMD_OPT_ADAMW = 0, ICAMD_OPT_ADAM = 1, ICAMD_OPT_SGD_MOMENTUM = 2, ICAM
 int icamd_optim_ema(int kind, float* p, float* g, float* m, float* v, float* ema, void* shadow, long long n, float lr,
                     float wd, float beta1, float beta2, float eps, int step, float gscale, float ema_decay,
                     const float* clip, const int32_t* finite_flag, int32_t* skipped_steps, int zero_grad, void* stream);
+/* dst += w * (src - dst) over n floats (EMA of the buffers; skipped when *finite_flag == 0, finite_flag may be NULL);
+ * w == 1 is a bit-exact copy of src, whatever dst held. */
 int icamd_lerp(float* dst, const float* src, long long n, float w, const int32_t* finite_flag, void* stream);
 int icamd_f32_to_bf16(const float* src, void* dst, long long n, void* stream);
 int icamd_colsum(const void* x, int rows, int ld, int cols, float* out, int accumulate, void* stream);

@@ -7,6 +7,8 @@ it relies on is what torch runs for timm's layers under /root/reference/engine.p
 torch.optim.AdamW / timm ModelEmaV3 / timm Mixup (engine.py:44,68,74,77); torch-CPU is therefore the pin.
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this package.
 """
+import math
+
 import torch
 import torch.nn.functional as F
 
@@ -234,7 +236,7 @@ def pack_input(x_nchw, mode=0, lam=1.0, box=None):
         yl, yh, xl, xh = box
         x[:, :, yl:yh, xl:xh] = x_nchw.float().flip(0)[:, :, yl:yh, xl:xh]
     B, C, H, W = x.shape
-    out = torch.zeros(B, H, W, 8)
+    out = torch.zeros(B, H, W, 8, device=x.device)
     out[..., :C] = x.permute(0, 2, 3, 1)
     return bf16_round(out)
 
@@ -334,6 +336,42 @@ def optimizer_ema_steps(name, p0, grads, lrs, wds, ema0=None, ema_decay=0.9995, 
     st = opt.state[p]
     m = st.get("momentum_buffer", st.get("exp_avg"))
     return p.detach(), m, st.get("exp_avg_sq"), ema
+
+
+OPT_KINDS = {"adamw": 0, "adam": 1, "momentum": 2, "nesterov": 3, "lion": 4}
+
+
+def optimizer_step_f64(name, p, g, m, v, lr, wd, t, betas=(0.9, 0.999), eps=1e-8, gscale=1.0):
+    """ONE step of torch.optim.AdamW / Adam / SGD (momentum 0.9, dampening 0, Nesterov or not) / LionRef restated on flat
+    tensors in fp64 (any device): t is the 1-based number of the step (the Adam bias corrections), m the first moment or
+    momentum buffer (zeros in front of step 1), v the second moment (Adam kinds only, else ignored and returned as it
+    came).  Returns new (p, m, v); nothing is modified in place.  Pinned against adamw_ema_steps / optimizer_ema_steps
+    (torch.optim itself) in tests/test_oracle_cpu.py."""
+    p, g, m = p.double(), g.double() * gscale, m.double()
+    b1, b2 = betas
+    if name in ("adamw", "adam"):
+        v = v.double()
+        if name == "adamw":
+            p = p * (1.0 - lr * wd)
+        else:
+            g = g + wd * p
+        m = m + (g - m) * (1.0 - b1)
+        v = v * b2 + (1.0 - b2) * g * g
+        denom = v.sqrt() / math.sqrt(1.0 - b2 ** t) + eps
+        return p - (lr / (1.0 - b1 ** t)) * (m / denom), m, v
+    if name in ("momentum", "nesterov"):
+        g = g + wd * p
+        m = b1 * m + g
+        return p - lr * (g + b1 * m if name == "nesterov" else m), m, v
+    if name == "lion":
+        p = p * (1.0 - lr * wd) - lr * torch.sign(m * b1 + g * (1.0 - b1))
+        return p, m + (g - m) * (1.0 - b2), v
+    raise ValueError(name)
+
+
+def ema_step_f64(ema, p, ema_decay):
+    """ModelEmaV3.update: ema.lerp_(p, 1 - decay), in fp64."""
+    return ema.double() + (p.double() - ema.double()) * (1.0 - ema_decay)
 
 
 def grad_norm(g, max_norm=0.0):

@@ -1,4 +1,4 @@
-"""Comparisons of the full-size layer tests (tests/test_fullsize_layers_gpu.py), kept apart so that
+"""Comparisons of the full-size layer and step tests (tests/test_fullsize_layers_gpu.py, tests/test_fullsize_step_gpu.py), kept apart so that
 tests/test_fullsize_checkers_cpu.py can show on synthetic data that each of them rejects a subtly wrong output.
 
 Every checker returns a list of failure messages (empty: accepted); `require` turns that into an assertion.
@@ -117,8 +117,127 @@ def check_stats(partials, y, weight=None, rtol=1e-5):
 def check_close(got, ref, rtol, atol=0.0, what="values"):
     """Small vectors (BatchNorm coefficients, LayerNorm row statistics, bias gradients)."""
     g, r = got.double().flatten(), ref.double().to(got.device).flatten()
-    bad = ~((g - r).abs() <= rtol * r.abs() + atol)
+    bad = ~((g - r).abs() <= rtol * r.abs() + _atol(atol, got.device))     # atol: a number, or one value per element
     if bool(bad.any()):
         i = int(torch.nonzero(bad)[0])
         return [f"{what}: {int(bad.sum())} of {r.numel()} off, [{i}] {float(g[i]):.9g} vs {float(r[i]):.9g}"]
     return []
+
+
+# ---- comparisons of the full-size step tests (tests/test_fullsize_step_gpu.py): flat arenas, job tables, loss and metrics ----
+def _atol(atol, device):
+    return atol.double().to(device).flatten() if torch.is_tensor(atol) else atol
+
+
+def check_arena(got, ref, rtol, atol, what="arena", chunk=1 << 24):
+    """EVERY element of a flat arena within rtol * |ref| + atol of the reference, no outliers allowed (a NaN on either side
+    counts as off).  Compared chunk by chunk, so that an 86 M-element arena needs no third fp64 copy."""
+    g, r = got.flatten(), ref.flatten()
+    if g.numel() != r.numel():
+        return [f"{what}: {g.numel()} elements, reference has {r.numel()}"]
+    nbad, first, last = 0, None, None
+    for lo in range(0, r.numel(), chunk):
+        gc, rc = g[lo:lo + chunk].double(), r[lo:lo + chunk].double().to(g.device)
+        bad = ~((gc - rc).abs() <= rtol * rc.abs() + atol)
+        k = int(bad.sum())
+        if k:
+            idx = torch.nonzero(bad).flatten()
+            first = lo + int(idx[0]) if first is None else first
+            last = lo + int(idx[-1])
+            nbad += k
+    if nbad:
+        return [f"{what}: {nbad} of {r.numel()} off (rtol {rtol:g} atol {atol:g}), first [{first}] {float(g[first]):.9g} vs "
+                f"{float(r[first]):.9g}, last [{last}]"]
+    return []
+
+
+def _bits(t):
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()]).flatten()
+
+
+def check_bits(got, ref, what="values"):
+    """Bit equality of two tensors of one dtype (-0 != +0, NaN payloads count)."""
+    if got.dtype != ref.dtype or got.numel() != ref.numel():
+        return [f"{what}: {got.dtype}[{got.numel()}] vs {ref.dtype}[{ref.numel()}]"]
+    bad = _bits(got) != _bits(ref.to(got.device))
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        return [f"{what}: {int(bad.sum())} of {got.numel()} differ bitwise, first [{i}] {float(got.flatten()[i]):.9g} vs "
+                f"{float(ref.flatten()[i]):.9g}"]
+    return []
+
+
+def check_transposed(shadow, shadow_t, descs, sentinel):
+    """The models' transpose tables: for every desc row (src_off, dst_off, Cout, T, Cin, ...) the [Cin][T][Cout] slot of
+    shadow_t is bit-equal to the transpose of the [Cout][T][Cin] slot of shadow; the slots do not overlap; every element of
+    shadow_t outside all slots still holds `sentinel` (an int16 bit pattern shadow_t was filled with)."""
+    s, t = _bits(shadow), _bits(shadow_t)
+    out = []
+    covered = torch.zeros(t.numel(), dtype=torch.bool, device=t.device)
+    total = 0
+    for i, (src, dst, co, taps, ci) in enumerate([tuple(int(v) for v in d[:5]) for d in descs]):
+        n = co * taps * ci
+        if src < 0 or dst < 0 or src + n > s.numel() or dst + n > t.numel():
+            out.append(f"desc {i}: slot outside the arenas")
+            continue
+        want = s[src:src + n].view(co, taps, ci).permute(2, 1, 0)
+        have = t[dst:dst + n].view(ci, taps, co)
+        bad = have != want
+        if bool(bad.any()):
+            a, b, c = (int(v) for v in torch.nonzero(bad)[0])
+            out.append(f"desc {i} ({co}x{taps}x{ci}): {int(bad.sum())} elements off, first (ci {a}, tap {b}, co {c})")
+        covered[dst:dst + n] = True
+        total += n
+    if int(covered.sum()) != total:
+        out.append("transposed slots overlap")
+    stray = (t != sentinel) & ~covered
+    if bool(stray.any()):
+        out.append(f"{int(stray.sum())} elements outside every slot written, first [{int(torch.nonzero(stray)[0])}]")
+    return out
+
+
+def check_fold(got, ref64, what="folded filter", ulps=1.0, block_rel=BLOCK_REL_L2):
+    """Folded bf16 filters [rows, K] against bf16(fp64 product): every element within `ulps` bf16 steps (the fp32 scale of
+    the kernel can move a product across a rounding boundary, never further) and rel L2 of every 64 x 64 block."""
+    r = ref64.to(torch.bfloat16).float()
+    g = got.float().reshape(r.shape)
+    out = []
+    if not bool(torch.isfinite(g).all()):
+        out.append(f"{what}: non-finite values")
+    u = R.max_bf16_ulp(g, r)
+    if not u <= ulps:
+        out.append(f"{what}: {u:.3g} bf16 ulp > {ulps:g}")
+    return out + [f"{what}: {m}" for m in _blocks(g, r, None, block_rel)]
+
+
+def lowest_argmax(logits):
+    """Index of the row maximum, the LOWEST one where it is tied -- written out, so that torch.argmax is not taken on trust."""
+    x = logits.float()
+    C = x.shape[1]
+    idx = torch.arange(C, device=x.device).expand_as(x)
+    return torch.where(x == x.max(1, keepdim=True).values, idx, C).min(1).values
+
+
+def check_pred(pred, logits):
+    want = lowest_argmax(logits)
+    bad = pred.long().to(want.device) != want
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0])
+        return [f"prediction of {int(bad.sum())} rows off, row {i}: {int(pred[i])} vs {int(want[i])}"]
+    return []
+
+
+def check_counts(counts, pred, target, C, times=1):
+    """TP / FP / FN per class (int32 [3][C]) against torch.bincount of the predictions and targets, `times` steps of them."""
+    p, t = pred.long().cpu(), target.long().cpu()
+    hit = p == t
+    want = torch.stack([torch.bincount(t[hit], minlength=C), torch.bincount(p[~hit], minlength=C),
+                        torch.bincount(t[~hit], minlength=C)]) * times
+    got = counts.long().cpu().reshape(3, C)
+    out = []
+    for k, name in enumerate(("TP", "FP", "FN")):
+        bad = got[k] != want[k]
+        if bool(bad.any()):
+            c = int(torch.nonzero(bad)[0])
+            out.append(f"{name}: {int(bad.sum())} classes off, class {c}: {int(got[k, c])} vs {int(want[k, c])}")
+    return out

@@ -650,3 +650,35 @@ def test_foreign_codeobj_guard_reports_the_mapped_rccl():
     assert g["verdict"].startswith(("clean:", "unverified:", "HAZARD:"))
     if lib.icamd_rccl_available():
         assert g["rccl_version"] > 0 and g["rccl_library"] and "librccl" in g["rccl_library"]
+
+
+@pytest.mark.parametrize("name", ["adamw", "adam", "momentum", "nesterov", "lion"])
+def test_single_step_fp64_optimizer_formulas_are_torch_optims(name):
+    """R.optimizer_step_f64 / R.ema_step_f64 (the references of tests/test_fullsize_step_gpu.py) chained for 4 steps give what
+    torch.optim's own AdamW / Adam / SGD and LionRef give (R.adamw_ema_steps / R.optimizer_ema_steps, fp32), with the lr = 0
+    first step, per-step weight decay, gradient scale and EMA: the new formulas are not their own witness."""
+    n = 4096
+    g = torch.Generator().manual_seed(62)
+    p0 = torch.randn(n, generator=g)
+    grads = [torch.randn(n, generator=g) * 0.1 for _ in range(4)]
+    lrs, wds = [0.0, 2.5e-4, 5e-4, 1e-3], [5e-4, 4.9e-4, 4.8e-4, 4.7e-4]
+    if name == "adamw":
+        rp, rm, rv, rema = R.adamw_ema_steps(p0, grads, lrs, wds, ema0=p0, ema_decay=0.9995, gscale=0.5)
+    else:
+        rp, rm, rv, rema = R.optimizer_ema_steps(name, p0, grads, lrs, wds, ema0=p0, ema_decay=0.9995, gscale=0.5)
+    p, m, v, ema = p0.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64), p0.double()
+    for t, (gr, lr, wd) in enumerate(zip(grads, lrs, wds), 1):
+        p, m, v = R.optimizer_step_f64(name, p, gr, m, v, lr, wd, t, gscale=0.5)
+        ema = R.ema_step_f64(ema, p, 0.9995)
+    assert p.dtype == torch.float64
+    # the bounds test_adamw_ema_gradnorm / test_other_fused_optimizers hold the kernels to (fp32 torch.optim vs fp64 here)
+    if name == "lion":
+        # fp32 sign() of a value within rounding of zero may differ from fp64's: a handful of +-2*lr outliers, as in
+        # test_other_fused_optimizers
+        assert int(((p - rp.double()).abs() > 1e-6).sum()) <= 2
+    else:
+        assert torch.allclose(p, rp.double(), rtol=2e-5, atol=1e-6)
+        assert torch.allclose(ema, rema.double(), rtol=1e-5, atol=1e-6)
+    assert torch.allclose(m, rm.double(), rtol=1e-5, atol=1e-7)
+    if name in ("adamw", "adam"):
+        assert torch.allclose(v, rv.double(), rtol=1e-5, atol=1e-9)
