@@ -157,11 +157,23 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
                                                             double* __restrict__ partial) {
   __shared__ double red[4];
   const long long stride = (long long)gridDim.x * blockDim.x;
-  double s = 0.0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const f32x4 v = ((const f32x4*)g)[i];
-    s += (double)(v[0] * v[0] + v[1] * v[1]) + (double)(v[2] * v[2] + v[3] * v[3]);
+  // four loads in flight and four independent fp64 chains per thread (one load feeding one dependent fp64 add ran at 0.6 of the
+  // streaming rate); the chains are folded in a fixed order, so the sum is the same from run to run
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    f32x4 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) v[u] = ((const f32x4*)g)[i + u * stride];
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      acc[u] += (double)(v[u][0] * v[u][0] + v[u][1] * v[u][1]) + (double)(v[u][2] * v[u][2] + v[u][3] * v[u][3]);
   }
+  for (; i < n4; i += stride) {
+    const f32x4 v = ((const f32x4*)g)[i];
+    acc[0] += (double)(v[0] * v[0] + v[1] * v[1]) + (double)(v[2] * v[2] + v[3] * v[3]);
+  }
+  double s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
   if (blockIdx.x == 0 && threadIdx.x == 0)
     for (long long i = n4 * 4; i < n; ++i) s += (double)g[i] * (double)g[i];
   s = wave_sum_d(s);
@@ -173,9 +185,13 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
 // out[0] = norm * inv_scale ; out[1] = clip coefficient (torch clip_grad_norm_: min(1, max_norm/(norm+1e-6)))
 __global__ void gradnorm_finalize_kernel(const double* __restrict__ partial, int nblk, float inv_scale, float max_norm,
                                          float* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  // one wave: lane l adds partial[l], partial[l + 64], ... (independent loads), then the fixed xor butterfly -- the order never
+  // changes, so the norm is bit-reproducible (one thread walking all partials was a chain of nblk dependent loads: 34 us)
+  if (blockIdx.x != 0 || threadIdx.x >= 64) return;
   double s = 0.0;
-  for (int i = 0; i < nblk; ++i) s += partial[i];
+  for (int i = (int)threadIdx.x; i < nblk; i += 64) s += partial[i];
+  s = wave_sum_d(s);
+  if (threadIdx.x != 0) return;
   const float norm = (float)sqrt(s) * inv_scale;
   out[0] = norm;
   float coef = 1.f;
@@ -356,14 +372,29 @@ __global__ __launch_bounds__(256) void filter_transpose_tiled_kernel(const bf16_
   }
 }
 
-// column sums of a bf16 matrix [rows][ld] -> fp32 [cols] (FC bias gradient); one thread per column
+// column sums of a bf16 matrix [rows][ld] -> fp32 [cols] (FC bias gradient).  A workgroup takes 32 columns: its 8 row lanes load
+// a tile of 64 rows at once (one thread per column walking the rows had 4 workgroups and one load in flight per thread), then one
+// thread per column adds the staged values in row order -- the sum a single thread walking the rows would have made, bit for bit.
 __global__ __launch_bounds__(256) void colsum_kernel(const bf16_t* __restrict__ x, int rows, int ld, int cols,
                                                      float* __restrict__ out, int accumulate) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
+  __shared__ float tile[64][32];
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+  const int c = blockIdx.x * 32 + cl;
   float s = 0.f;
-  for (int r = 0; r < rows; ++r) s += bf16_to_f32(x[(long long)r * ld + c]);
-  out[c] = accumulate ? out[c] + s : s;
+  for (int r0 = 0; r0 < rows; r0 += 64) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int r = r0 + rl + 8 * j;
+      tile[rl + 8 * j][cl] = (c < cols && r < rows) ? bf16_to_f32(x[(long long)r * ld + c]) : 0.f;
+    }
+    __syncthreads();
+    if (rl == 0) {
+      const int nr = rows - r0 < 64 ? rows - r0 : 64;
+      for (int k = 0; k < nr; ++k) s += tile[k][cl];
+    }
+    __syncthreads();
+  }
+  if (rl == 0 && c < cols) out[c] = accumulate ? out[c] + s : s;
 }
 
 inline unsigned int grid_for(long long work_items, int threads) {
@@ -527,7 +558,7 @@ int icamd_filter_transpose_tiled_launch(const bf16_t* src_base, bf16_t* dst_base
 }
 
 int icamd_colsum_launch(const bf16_t* x, int rows, int ld, int cols, float* out, int accumulate, hipStream_t s) {
-  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, s, x, rows, ld, cols, out,
+  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((cols + 31) / 32)), dim3(256), 0, s, x, rows, ld, cols, out,
                      accumulate);
   return icamd_launch_status();
 }

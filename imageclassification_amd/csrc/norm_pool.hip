@@ -239,18 +239,26 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict_
 // is gathered on the fly -- the sum over the (<= 4) 3x3/s2/p1 windows that cover it and whose recorded argmax it is, rounded
 // to bf16 exactly as icamd_maxpool3x3s2_bwd would have stored it -- so the 4x larger full-resolution gradient is never
 // written or read.
+//
+// The gather itself: a full-resolution pixel asks for up to four (gradient, argmax) window vectors, and its neighbours ask for
+// the same ones again (every window is wanted by nine pixels).  Sent to global memory that is 4.5 load requests per 16 B of
+// result, and the passes were bound by L1 requests, not by bytes.  So a workgroup walks its range of pixels in strips of
+// `krows` image rows and first copies the (krows / 2 + 1) POOLED rows such a strip touches -- contiguous in memory -- into LDS
+// with coalesced 16 B / 8 B loads; the per-pixel gather then reads LDS.  One global request per 16 B staged, each pooled row
+// fetched 1.5 times (krows = 4) instead of 9.  krows = 0 (the pooled rows do not fit in LDS): gather from global memory as before.
 struct PoolGather {
-  const unsigned char* idx;   // nullptr: no pooling in front, dout is read directly
+  const unsigned char* idx;   // argmax bytes of the pooled map (never null in the kernels that take this)
   int IH, IW, OH, OW;
   FastDiv dIW, dIH;
+  int krows;                  // image rows per LDS strip (even), 0 = no staging
+  int cap;                    // vectors the LDS strip holds: (krows / 2 + 1) * OW * C/8
 };
 
-__device__ __forceinline__ u32x4 pool_gather8(const bf16_t* __restrict__ dout, const PoolGather& pg, unsigned int row,
+// Sum over the (<= 4) windows that cover pixel (h, w) of image n and whose argmax it is, in (oh, ow) order, rounded to bf16
+// once.  d8 / i8: the pooled gradient / argmax vectors, indexed by ((n*OH + oh) * OW + ow) * cpr + cg - base.
+template <class DPtr, class IPtr>
+__device__ __forceinline__ u32x4 pool_gather8(DPtr d8, IPtr i8, unsigned int base, const PoolGather& pg, unsigned int n, int h, int w,
                                               unsigned int cpr, unsigned int cg) {
-  const unsigned int t1 = fdiv(row, pg.dIW);
-  const int w = (int)(row - t1 * pg.IW);
-  const unsigned int n = fdiv(t1, pg.dIH);
-  const int h = (int)(t1 - n * pg.IH);
   float acc[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) acc[e] = 0.f;
@@ -261,9 +269,10 @@ __device__ __forceinline__ u32x4 pool_gather8(const bf16_t* __restrict__ dout, c
     for (int ow = ow_lo; ow <= ow_hi; ++ow) {
       if (ow >= pg.OW) continue;
       const unsigned int code4 = (unsigned)(r * 3 + (w - (ow * 2 - 1))) * 0x01010101u;
-      const unsigned int o = ((n * pg.OH + oh) * pg.OW + ow) * cpr + cg;
-      const u32x2 iv = ((const u32x2*)pg.idx)[o];
-      const u32x4 d = ((const u32x4*)dout)[o];
+      const unsigned int o = ((n * pg.OH + oh) * pg.OW + ow) * cpr + cg - base;
+      const u32x2 iv = i8[o];
+      const u32x4 d = d8[o];
+      // a byte of iv ^ code4 is zero where that channel's argmax is this pixel
       const unsigned int m0 = iv[0] ^ code4, m1 = iv[1] ^ code4;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -279,6 +288,68 @@ __device__ __forceinline__ u32x4 pool_gather8(const bf16_t* __restrict__ dout, c
   return out;
 }
 
+// The same sum with the window counts known at compile time: NH / NW = 1 for an even row / column (one window row / column covers
+// it), 2 for an odd one.  No loop and no divergence, so the (<= 4) window loads are issued together and waited for once; the loop
+// above waited for each LDS read in turn, at five waves per SIMD.  A window outside the pooled map (the last odd row / column
+// of an even-sized image) is read at a valid address with an argmax code no byte can equal: it adds 0.f, which changes nothing.
+template <int NH, int NW, class DPtr, class IPtr>
+__device__ __forceinline__ u32x4 pool_gather8_fixed(DPtr d8, IPtr i8, unsigned int base, const PoolGather& pg, unsigned int n, int h,
+                                                    int w, unsigned int cpr, unsigned int cg) {
+  u32x4 d[NH * NW];
+  u32x2 iv[NH * NW];
+  unsigned int code4[NH * NW];
+#pragma unroll
+  for (int a = 0; a < NH; ++a) {
+#pragma unroll
+    for (int b = 0; b < NW; ++b) {
+      const int oh = (h >> 1) + a, ow = (w >> 1) + b;
+      const bool ok = oh < pg.OH && ow < pg.OW;
+      code4[a * NW + b] = ok ? (unsigned)((h - (oh * 2 - 1)) * 3 + (w - (ow * 2 - 1))) * 0x01010101u : 0x7f7f7f7fu;
+      const unsigned int o = ((n * pg.OH + (ok ? oh : h >> 1)) * pg.OW + (ok ? ow : w >> 1)) * cpr + cg - base;
+      iv[a * NW + b] = i8[o];
+      d[a * NW + b] = d8[o];
+    }
+  }
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll
+  for (int k = 0; k < NH * NW; ++k) {
+    const unsigned int m0 = iv[k][0] ^ code4[k], m1 = iv[k][1] ^ code4[k];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const unsigned int mb = ((e < 4 ? m0 : m1) >> ((e & 3) * 8)) & 0xffu;
+      const float dv = (e & 1) ? bf16_hi(d[k][e >> 1]) : bf16_lo(d[k][e >> 1]);
+      acc[e] += mb == 0u ? dv : 0.f;
+    }
+  }
+  u32x4 out;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) out[e] = pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
+  return out;
+}
+
+// The two per-vector steps of the BatchNorm backward, shared by the plain and the pooled kernels so that both round alike.
+__device__ __forceinline__ void bn_bwd_accumulate8(const float (&g)[8], const float (&yy)[8], const float (&mu)[8],
+                                                   const float (&is)[8], float (&sg)[8], float (&sgx)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sg[e] += g[e];
+    sgx[e] += g[e] * ((yy[e] - mu[e]) * is[e]);
+  }
+}
+__device__ __forceinline__ u32x4 bn_bwd_dy8(const float (&g)[8], const float (&yy)[8], const float (&mu)[8],
+                                            const float (&is)[8], const float (&sc)[8], const float (&k1)[8],
+                                            const float (&k2)[8]) {
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) o[e] = sc[e] * (g[e] - k1[e] - ((yy[e] - mu[e]) * is[e]) * k2[e]);
+  u32x4 ov;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o[2 * e], o[2 * e + 1]);
+  return ov;
+}
+
 // ------------------------------------------------------------------------------------------------
 // BN backward, pass 1: per-channel partial sums of g and g*xhat, g = dout * [act > 0]
 //   act == nullptr && relu : mask recomputed from y*scale+shift > 0 (no residual in front of the ReLU)
@@ -289,7 +360,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const bf16_t* __rest
                                                             const float* __restrict__ invstd, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, float* __restrict__ part,
                                                             const unsigned char* __restrict__ maskbits, long long rows, int C,
-                                                            int rows_per_block, int relu, const PoolGather pg) {
+                                                            int rows_per_block, int relu) {
   __shared__ float red[256 * 16];
   const int cpr = C >> 3;                 // 8-channel groups per row
   const int tid = threadIdx.x;
@@ -310,8 +381,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const bf16_t* __rest
       for (int e = 0; e < 8; ++e) { mu[e] = mean[c + e]; is[e] = invstd[c + e]; sc[e] = scale[c + e]; sh[e] = shift[c + e]; }
       for (long long r = r0 + rl; r < r1; r += rlanes) {
         const long long off = r * cpr + cg0 + cgi;
-        const u32x4 d = pg.idx != nullptr ? pool_gather8(dout, pg, (unsigned)r, (unsigned)cpr, (unsigned)(cg0 + cgi))
-                                          : bn_ld(dout, off);
+        const u32x4 d = bn_ld(dout, off);
         const u32x4 yv = bn_ld(y, off);
         float g[8], yy[8];
 #pragma unroll
@@ -338,11 +408,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const bf16_t* __rest
               if (!(fmaf(yy[e], sc[e], sh[e]) > 0.f)) g[e] = 0.f;
           }
         }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          sg[e] += g[e];
-          sgx[e] += g[e] * ((yy[e] - mu[e]) * is[e]);
-        }
+        bn_bwd_accumulate8(g, yy, mu, is, sg, sgx);
       }
     }
     // cross-row-lane reduction through LDS: red[tid][16]
@@ -368,8 +434,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
                                                            const float* __restrict__ shift, const float* __restrict__ c1,
                                                            const float* __restrict__ c2, bf16_t* __restrict__ dy,
                                                            bf16_t* __restrict__ gout, const unsigned char* __restrict__ maskbits,
-                                                           long long nvec, int cpr, int relu, int reverse,
-                                                           const PoolGather pg, const FastDiv dcpr) {
+                                                           long long nvec, int cpr, int relu, int reverse) {
   // `reverse`: walk the tensors from the END.  The reduce pass that ran just before streamed dout and y front to back, so
   // their tails are what the 256 MB Infinity Cache (and L2) still hold: reading back to front meets those lines first.
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -384,13 +449,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
   }
   for (; k0 < nvec; k0 += stride) {
     const long long i = reverse ? nvec - 1 - k0 : k0;
-    u32x4 d;
-    if (pg.idx != nullptr) {
-      const unsigned int row = fdiv((unsigned)i, dcpr);
-      d = pool_gather8(dout, pg, row, (unsigned)cpr, (unsigned)i - row * (unsigned)cpr);
-    } else {
-      d = bn_ld(dout, i);
-    }
+    const u32x4 d = bn_ld(dout, i);
     const u32x4 yv = bn_ld(y, i);
     float g[8], yy[8];
 #pragma unroll
@@ -417,13 +476,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
           if (!(fmaf(yy[e], sc[e], sh[e]) > 0.f)) g[e] = 0.f;
       }
     }
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = sc[e] * (g[e] - k1[e] - ((yy[e] - mu[e]) * is[e]) * k2[e]);
-    u32x4 ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(o[2 * e], o[2 * e + 1]);
-    bn_st(dy, i, ov);
+    bn_st(dy, i, bn_bwd_dy8(g, yy, mu, is, sc, k1, k2));
     if (gout != nullptr) {
       u32x4 gv;
 #pragma unroll
@@ -431,6 +484,171 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
       bn_st(gout, i, gv);
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The three kernels that gather a max-pool gradient (PoolGather above) share one body:
+//   PASS 0  BatchNorm-backward reduce over the gathered gradient (ReLU mask recomputed from y*scale+shift > 0)
+//   PASS 1  BatchNorm-backward apply over it
+//   PASS 2  the pooling backward alone: dx = gathered gradient
+// Thread -> (channel group, row lane) and the rows a thread takes, r0 + rl + k * rlanes in rising k, are those of
+// bn_bwd_reduce_kernel, and so is the fold over row lanes: PASS 0 adds the same numbers in the same order as that kernel does
+// on the materialised gradient, so its partial sums are bit-equal.  The strips only say WHEN a row is taken (after the pooled
+// rows it needs are in LDS), never by whom.  Needs C/8 <= 256.  Dynamic LDS: max(16 KB, pg.cap * 24 B).
+// ------------------------------------------------------------------------------------------------
+template <int PASS>
+__device__ __forceinline__ void pool_bwd_body(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ y,
+                                              const float* __restrict__ mean, const float* __restrict__ invstd,
+                                              const float* __restrict__ scale, const float* __restrict__ shift,
+                                              const float* __restrict__ c1, const float* __restrict__ c2,
+                                              float* __restrict__ part, bf16_t* __restrict__ out, unsigned int rows, int C,
+                                              unsigned int rows_per_block, const PoolGather& pg) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pool_smem[];
+  u32x4* sd = (u32x4*)pool_smem;                                  // staged gradient vectors [cap]
+  u32x2* si = (u32x2*)(pool_smem + (size_t)pg.cap * 16);          // staged argmax vectors   [cap]
+  const unsigned int cpr = (unsigned)C >> 3;
+  const unsigned int tid = threadIdx.x;
+  const unsigned int rlanes = 256u / cpr;
+  // Which lane plays which (channel group, row lane) is free -- the fold below goes by row lane, not by thread -- so the row
+  // lanes are dealt to the waves in pairs: of 2G neighbouring row lanes (G = 64 / cpr per wave) one wave takes the even ones, the
+  // next the odd ones.  With an even image width all pixels of a wave then have the same column parity, so the wave walks one
+  // window column for even columns and two for odd ones (2.25 windows per pixel on average) instead of always two with half
+  // of its lanes switched off (3 per pixel): the gather is VALU work, a quarter of it less.
+  const unsigned int cgi = tid % cpr;
+  unsigned int rl = tid / cpr;
+  if (64u % cpr == 0u && cpr <= 32u) {
+    const unsigned int G = 64u / cpr, wv = tid >> 6, j = (tid & 63u) / cpr;
+    rl = 2u * G * (wv >> 1) + 2u * j + (wv & 1u);
+  }
+  const unsigned int r0 = blockIdx.x * rows_per_block;
+  const unsigned int r1 = (rows - r0 < rows_per_block) ? rows : r0 + rows_per_block;
+  const unsigned int vpr = (unsigned)pg.OW * cpr;                 // vectors per pooled row
+  float mu[8], is[8], sc[8], sh[8], k1[8], k2[8], sg[8], sgx[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { sg[e] = 0.f; sgx[e] = 0.f; }
+  if constexpr (PASS != 2) {
+    const unsigned int c = cgi * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[c + e]; is[e] = invstd[c + e]; sc[e] = scale[c + e]; sh[e] = shift[c + e]; }
+    if constexpr (PASS == 1) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { k1[e] = c1[c + e]; k2[e] = c2[c + e]; }
+    }
+  }
+  unsigned int r = rl < rlanes ? r0 + rl : r1;                    // idle lanes (256 % cpr != 0) take no rows
+  for (unsigned int s0 = r0; s0 < r1;) {
+    unsigned int s1 = r1, base = 0;
+    if (pg.krows > 0) {
+      // the strip: up to krows image rows of ONE image from the row that holds pixel s0, cut at the end of the block's range
+      const unsigned int grow = fdiv(s0, pg.dIW);
+      const unsigned int n0 = fdiv(grow, pg.dIH);
+      const unsigned int h0 = grow - n0 * (unsigned)pg.IH;
+      unsigned int hend = h0 + (unsigned)pg.krows;
+      if (hend > (unsigned)pg.IH) hend = (unsigned)pg.IH;
+      const unsigned int send = (n0 * (unsigned)pg.IH + hend) * (unsigned)pg.IW;
+      if (send < s1) s1 = send;
+      // pooled rows h0/2 .. min(hend/2, OH-1) of image n0: at most krows/2 + 1 of them, contiguous in memory
+      unsigned int ohi = hend >> 1;
+      if (ohi > (unsigned)pg.OH - 1u) ohi = (unsigned)pg.OH - 1u;
+      base = (n0 * (unsigned)pg.OH + (h0 >> 1)) * vpr;
+      const unsigned int nv = (ohi - (h0 >> 1) + 1u) * vpr;       // <= pg.cap
+      __syncthreads();                                            // the previous strip's readers are done
+      for (unsigned int v = tid; v < nv; v += 256u) {
+        sd[v] = ((const u32x4*)dout)[base + v];
+        si[v] = ((const u32x2*)pg.idx)[base + v];
+      }
+      __syncthreads();
+    }
+    // (n, h, w) of this thread's next pixel: two divisions per strip, then steps of rlanes pixels along the rows
+    unsigned int n = 0;
+    int h = 0, w = 0;
+    if (r < s1) {
+      const unsigned int t1 = fdiv(r, pg.dIW);
+      w = (int)(r - t1 * (unsigned)pg.IW);
+      n = fdiv(t1, pg.dIH);
+      h = (int)(t1 - n * (unsigned)pg.IH);
+    }
+    for (; r < s1; r += rlanes) {
+      u32x4 d;
+      if (pg.krows > 0) {
+        // the row / column parities are the same for a whole wave almost always (see the lane roles above): a scalar branch
+        const int key = ((h & 1) << 1) | (w & 1);
+        const int key0 = __builtin_amdgcn_readfirstlane(key);
+        if (__all(key == key0)) {
+          if (key0 == 0) d = pool_gather8_fixed<1, 1>(sd, si, base, pg, n, h, w, cpr, cgi);
+          else if (key0 == 1) d = pool_gather8_fixed<1, 2>(sd, si, base, pg, n, h, w, cpr, cgi);
+          else if (key0 == 2) d = pool_gather8_fixed<2, 1>(sd, si, base, pg, n, h, w, cpr, cgi);
+          else d = pool_gather8_fixed<2, 2>(sd, si, base, pg, n, h, w, cpr, cgi);
+        } else {
+          d = pool_gather8(sd, si, base, pg, n, h, w, cpr, cgi);
+        }
+      } else {
+        d = pool_gather8((const u32x4*)dout, (const u32x2*)pg.idx, 0u, pg, n, h, w, cpr, cgi);
+      }
+      w += (int)rlanes;
+      while (w >= pg.IW) {
+        w -= pg.IW;
+        if (++h == pg.IH) { h = 0; ++n; }
+      }
+      const long long off = (long long)r * cpr + cgi;
+      if constexpr (PASS == 2) {
+        ((u32x4*)out)[off] = d;
+      } else {
+        const u32x4 yv = bn_ld(y, off);
+        float g[8], yy[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          g[2 * e] = bf16_lo(d[e]); g[2 * e + 1] = bf16_hi(d[e]);
+          yy[2 * e] = bf16_lo(yv[e]); yy[2 * e + 1] = bf16_hi(yv[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+          if (!(fmaf(yy[e], sc[e], sh[e]) > 0.f)) g[e] = 0.f;
+        if constexpr (PASS == 0) bn_bwd_accumulate8(g, yy, mu, is, sg, sgx);
+        else bn_st(out, off, bn_bwd_dy8(g, yy, mu, is, sc, k1, k2));
+      }
+    }
+    s0 = s1;
+  }
+  if constexpr (PASS == 0) {
+    // cross-row-lane reduction through LDS, as in bn_bwd_reduce_kernel: red[tid][16]
+    float* red = (float*)pool_smem;
+    __syncthreads();                                              // the last strip's readers are done
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[(rl * cpr + cgi) * 16 + e] = sg[e]; red[(rl * cpr + cgi) * 16 + 8 + e] = sgx[e]; }
+    __syncthreads();
+    for (unsigned int o = tid; o < cpr * 16; o += 256) {
+      const unsigned int cgo = o >> 4, e = o & 15;
+      float s = 0.f;
+      for (unsigned int l = 0; l < rlanes; ++l) s += red[(l * cpr + cgo) * 16 + e];
+      const unsigned int which = e >> 3;
+      part[((long long)blockIdx.x * 2 + which) * C + cgo * 8 + (e & 7)] = s;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_pool_reduce_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ y,
+                                                                 const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                 const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                 float* __restrict__ part, unsigned int rows, int C,
+                                                                 unsigned int rows_per_block, const PoolGather pg) {
+  pool_bwd_body<0>(dout, y, mean, invstd, scale, shift, nullptr, nullptr, part, nullptr, rows, C, rows_per_block, pg);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_pool_apply_kernel(const bf16_t* __restrict__ dout, const bf16_t* __restrict__ y,
+                                                                const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                const float* __restrict__ scale, const float* __restrict__ shift,
+                                                                const float* __restrict__ c1, const float* __restrict__ c2,
+                                                                bf16_t* __restrict__ dy, unsigned int rows, int C,
+                                                                unsigned int rows_per_block, const PoolGather pg) {
+  pool_bwd_body<1>(dout, y, mean, invstd, scale, shift, c1, c2, nullptr, dy, rows, C, rows_per_block, pg);
+}
+
+// dx[n,h,w,c] = sum over the (<=4) windows that cover (h,w) and whose recorded argmax is (h,w)
+__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const bf16_t* __restrict__ dout, bf16_t* __restrict__ dx,
+                                                               unsigned int rows, int C, unsigned int rows_per_block,
+                                                               const PoolGather pg) {
+  pool_bwd_body<2>(dout, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dx, rows, C, rows_per_block, pg);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -659,55 +877,6 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_fwd_kernel(const bf16_t* __r
   }
 }
 
-// dx[n,h,w,c] = sum over the (<=4) windows that cover (h,w) and whose recorded argmax is (h,w).  dv: reciprocals of
-// C/8, IW, IH.
-__global__ __launch_bounds__(256) void maxpool3x3s2_bwd_kernel(const bf16_t* __restrict__ dout,
-                                                               const unsigned char* __restrict__ idx,
-                                                               bf16_t* __restrict__ dx, int N, int IH, int IW, int C,
-                                                               int OH, int OW, const PoolDivs dv) {
-  const unsigned int cpr = (unsigned)C >> 3;
-  const unsigned int total = (unsigned)N * IH * IW * cpr;
-  const unsigned int stride = gridDim.x * blockDim.x;
-  unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned int cg = i - fdiv(i, dv.cpr) * cpr;
-  for (; i < total; i += stride) {
-    const unsigned int t = fdiv(i, dv.cpr);
-    const unsigned int t1 = fdiv(t, dv.ow);
-    const int w = (int)(t - t1 * IW);
-    const unsigned int n = fdiv(t1, dv.oh);
-    const int h = (int)(t1 - n * IH);
-    float acc[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    const int oh_lo = h >> 1, oh_hi = (h + 1) >> 1;   // windows rows covering h: ceil((h-1)/2) .. floor((h+1)/2)
-    const int ow_lo = w >> 1, ow_hi = (w + 1) >> 1;
-    for (int oh = oh_lo; oh <= oh_hi; ++oh) {
-      if (oh >= OH) continue;
-      const int r = h - (oh * 2 - 1);
-      for (int ow = ow_lo; ow <= ow_hi; ++ow) {
-        if (ow >= OW) continue;
-        const int s = w - (ow * 2 - 1);
-        const unsigned int code4 = (unsigned)(r * 3 + s) * 0x01010101u;
-        const unsigned int o = ((n * OH + oh) * OW + ow) * cpr + cg;
-        const u32x2 iv = ((const u32x2*)idx)[o];
-        const u32x4 d = ((const u32x4*)dout)[o];
-        // a byte of iv ^ code4 is zero where that channel's argmax is this pixel
-        const unsigned int m0 = iv[0] ^ code4, m1 = iv[1] ^ code4;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const unsigned int mb = ((e < 4 ? m0 : m1) >> ((e & 3) * 8)) & 0xffu;
-          const float dvv = (e & 1) ? bf16_hi(d[e >> 1]) : bf16_lo(d[e >> 1]);
-          acc[e] += mb == 0u ? dvv : 0.f;
-        }
-      }
-    }
-    u32x4 ov;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ov[e] = pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
-    ((u32x4*)dx)[i] = ov;
-  }
-}
-
 // global average pool: x[N][HW][C] -> out[N][C] (fp32 mean rounded once to bf16)
 __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ out,
                                                           int N, int HW, int C) {
@@ -788,37 +957,60 @@ __global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict
 // ResNet stem layout: fp32 NCHW -> bf16 [B][H][Wp][4] (RGB + one zero channel), Wp = W + 8 with 3 zero columns on the left and
 // 5 on the right, so that the 7x7/2 window row of output column q is the 64 contiguous, 16 B-aligned bytes starting at padded
 // column 2q (8 pixels x 4 channels; the 8th pixel meets a zero filter tap) and no load ever crosses the image border.
-// One thread writes two adjacent padded pixels (16 B).  Same fused mixup / cutmix as pack_input_kernel.
+// One thread writes two adjacent padded pixels (16 B), image columns 2p-3 and 2p-2: one 8 B load per colour plane (4 B aligned:
+// the pair starts on an odd column) where both are inside the image, and 32-bit index arithmetic with precomputed reciprocals
+// (it was six 4 B loads and two 64-bit divisions per 16 B stored).  Same fused mixup / cutmix as pack_input_kernel, the mixup
+// rounded exactly as torch rounds it.
+struct PackDivs { FastDiv wp2, h; };
+typedef float f32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+
 __global__ __launch_bounds__(256) void pack_input_rgb4_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int B,
                                                               int Cin, int H, int W, int mode, float lam, int yl, int yh,
-                                                              int xl, int xh) {
-  const int Wp2 = (W + (W & 1) + 8) / 2;        // an odd width gets one more zero column: the row pitch stays even
-  const long long total = (long long)B * H * Wp2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
+                                                              int xl, int xh, const PackDivs dv) {
+  const unsigned int Wp2 = (unsigned)(W + (W & 1) + 8) / 2;   // an odd width gets one more zero column: the row pitch stays even
+  const unsigned int total = (unsigned)B * H * Wp2;
+  const unsigned int stride = gridDim.x * blockDim.x;
   const long long hw = (long long)H * W;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const long long row = i / Wp2;
+  for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+    const unsigned int row = fdiv(i, dv.wp2);
     const int pp = (int)(i - row * Wp2);
-    const int b = (int)(row / H), h = (int)(row - (long long)b * H);
-    const int fb = B - 1 - b;
+    const unsigned int b = fdiv(row, dv.h);
+    const int h = (int)(row - b * (unsigned)H);
+    const unsigned int fb = (unsigned)B - 1 - b;
+    const int w0 = 2 * pp - 3;
+    const bool in0 = w0 >= 0 && w0 < W, in1 = w0 + 1 >= 0 && w0 + 1 < W;
+    const bool inbox = mode == 2 && h >= yl && h < yh;
+    const bool other = mode == 1 || inbox;
+    const float* pa = x + (long long)b * Cin * hw + (long long)h * W + w0;
+    const float* pb = x + (long long)fb * Cin * hw + (long long)h * W + w0;
     float f[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) f[c] = 0.f;
 #pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int w = 2 * pp + e - 3;
-      if (w >= 0 && w < W) {
-        const long long pix = (long long)h * W + w;
-        for (int c = 0; c < Cin; ++c) {
-          float v = x[((long long)b * Cin + c) * hw + pix];
-          if (mode == 1) {
-            const float o = x[((long long)fb * Cin + c) * hw + pix];
-            v = v * lam + o * (1.f - lam);
-          } else if (mode == 2) {
-            if (h >= yl && h < yh && w >= xl && w < xh) v = x[((long long)fb * Cin + c) * hw + pix];
-          }
-          f[4 * e + c] = v;
+    for (int c = 0; c < 3; ++c) {
+      if (c < Cin) {
+        float v0 = 0.f, v1 = 0.f, o0 = 0.f, o1 = 0.f;
+        if (in0 && in1) {
+          const f32x2_a4 v = *(const f32x2_a4*)(pa + c * hw);
+          v0 = v[0]; v1 = v[1];
+          if (other) { const f32x2_a4 o = *(const f32x2_a4*)(pb + c * hw); o0 = o[0]; o1 = o[1]; }
+        } else {
+          if (in0) { v0 = pa[c * hw]; if (other) o0 = pb[c * hw]; }
+          if (in1) { v1 = pa[c * hw + 1]; if (other) o1 = pb[c * hw + 1]; }
         }
+        if (mode == 1) {
+          // two products and a sum, each rounded, as torch computes x * lam + x.flip(0) * (1 - lam): left to the compiler, some
+          // of these became fused multiply-adds and some did not, and a result near zero then differed from torch's by
+          // hundreds of bf16 ulps
+#pragma clang fp contract(off)
+          v0 = v0 * lam + o0 * (1.f - lam);
+          v1 = v1 * lam + o1 * (1.f - lam);
+        } else if (inbox) {
+          if (w0 >= xl && w0 < xh) v0 = o0;
+          if (w0 + 1 >= xl && w0 + 1 < xh) v1 = o1;
+        }
+        f[c] = in0 ? v0 : 0.f;
+        f[4 + c] = in1 ? v1 : 0.f;
       }
     }
     u32x4 o;
@@ -922,6 +1114,21 @@ int icamd_bn_apply_launch(const bf16_t* y, const float* scale, const float* shif
   return icamd_launch_status();
 }
 
+// Strip geometry of the pooled-gradient gather: 4 image rows (3 pooled rows in LDS) if that fits in the 64 KB a plain launch may
+// ask for, else 2 (2 pooled rows), else none.  *lds_bytes also covers the 16 KB the reduce pass folds its row lanes through.
+static PoolGather pool_gather_for(const unsigned char* idx, int IH, int IW, int C, size_t* lds_bytes) {
+  PoolGather pg;
+  memset(&pg, 0, sizeof(pg));
+  pg.idx = idx; pg.IH = IH; pg.IW = IW; pg.OH = (IH - 1) / 2 + 1; pg.OW = (IW - 1) / 2 + 1;
+  pg.dIW = make_fastdiv((unsigned)IW); pg.dIH = make_fastdiv((unsigned)IH);
+  const long long vpr = (long long)pg.OW * (C / 8);
+  for (int k = 4; k >= 2 && pg.krows == 0; k -= 2)
+    if ((k / 2 + 1) * vpr * 24 <= 65536) { pg.krows = k; pg.cap = (int)((k / 2 + 1) * vpr); }
+  const size_t need = (size_t)pg.cap * 24;
+  *lds_bytes = need > 16384 ? need : 16384;
+  return pg;
+}
+
 int icamd_bn_bwd_rows_per_block(long long rows, int C) {
   // aim for ~N blocks (default 2048), at least 32 rows each
   static const long long nb = []() { const char* e = getenv("ICAMD_BNBWD_BLOCKS"); return e ? atoll(e) : 1024ll; }();
@@ -937,18 +1144,22 @@ int icamd_bn_bwd_launch(const bf16_t* dout, const bf16_t* act, const bf16_t* y, 
                         double* chunks, float* c1c2, hipStream_t s, const unsigned char* pool_idx, int pool_ih, int pool_iw) {
   if (C % 8 != 0) return ICAMD_ERR_BAD_ARG;
   PoolGather pg;
-  memset(&pg, 0, sizeof(pg));
+  size_t pool_lds = 0;
   if (pool_idx != nullptr) {   // dout is the pooled map's gradient: rows = N * pool_ih * pool_iw full-resolution pixels
-    if (rows * (C / 8) >= (1ll << 31) || pool_ih < 1 || pool_iw < 1 || rows % ((long long)pool_ih * pool_iw) != 0)
+    if (rows * (C / 8) >= (1ll << 31) || pool_ih < 1 || pool_iw < 1 || rows % ((long long)pool_ih * pool_iw) != 0 ||
+        act != nullptr || maskbits != nullptr || gout != nullptr || !relu)
       return ICAMD_ERR_BAD_ARG;
-    pg.idx = pool_idx; pg.IH = pool_ih; pg.IW = pool_iw; pg.OH = (pool_ih - 1) / 2 + 1; pg.OW = (pool_iw - 1) / 2 + 1;
-    pg.dIW = make_fastdiv((unsigned)pool_iw); pg.dIH = make_fastdiv((unsigned)pool_ih);
+    if (C > 2048) return ICAMD_ERR_UNSUPPORTED;
+    pg = pool_gather_for(pool_idx, pool_ih, pool_iw, C, &pool_lds);
   }
-  const FastDiv dcpr = make_fastdiv((unsigned)(C / 8));
   const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
   const int nblk = (int)((rows + rpb - 1) / rpb);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)nblk), dim3(256), 0, s, dout, act, y, mean, invstd, scale, shift,
-                     part, maskbits, rows, C, rpb, relu, pg);
+  if (pool_idx != nullptr)
+    hipLaunchKernelGGL(bn_bwd_pool_reduce_kernel, dim3((unsigned)nblk), dim3(256), pool_lds, s, dout, y, mean, invstd, scale,
+                       shift, part, (unsigned)rows, C, (unsigned)rpb, pg);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)nblk), dim3(256), 0, s, dout, act, y, mean, invstd, scale, shift,
+                       part, maskbits, rows, C, rpb, relu);
   int rc = icamd_launch_status();
   if (rc) return rc;
   float* c1 = c1c2;
@@ -963,8 +1174,12 @@ int icamd_bn_bwd_launch(const bf16_t* dout, const bf16_t* act, const bf16_t* y, 
     if (rc) return rc;
   }
   const long long nvec = rows * (C / 8);
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(elementwise_grid(nvec, C / 8)), dim3(256), 0, s, dout, act, y, mean, invstd,
-                     scale, shift, c1, c2, dy, gout, maskbits, nvec, C / 8, relu, bn_reverse(), pg, dcpr);
+  if (pool_idx != nullptr)
+    hipLaunchKernelGGL(bn_bwd_pool_apply_kernel, dim3((unsigned)nblk), dim3(256), pool_lds, s, dout, y, mean, invstd, scale,
+                       shift, c1, c2, dy, (unsigned)rows, C, (unsigned)rpb, pg);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(elementwise_grid(nvec, C / 8)), dim3(256), 0, s, dout, act, y, mean, invstd,
+                       scale, shift, c1, c2, dy, gout, maskbits, nvec, C / 8, relu, bn_reverse());
   return icamd_launch_status();
 }
 
@@ -1002,12 +1217,10 @@ int icamd_bn_bwd_dual_launch(const bf16_t* dout, const unsigned char* maskbits, 
 int icamd_bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* mean, const float* invstd, float* part, long long rows,
                                int C, int* nblk_out, hipStream_t s) {
   if (C % 8 != 0) return ICAMD_ERR_BAD_ARG;
-  PoolGather pg;
-  memset(&pg, 0, sizeof(pg));
   const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
   const int nblk = (int)((rows + rpb - 1) / rpb);
   hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3((unsigned)nblk), dim3(256), 0, s, g, (const bf16_t*)nullptr, y, mean, invstd, mean, mean,
-                     part, (const unsigned char*)nullptr, rows, C, rpb, 0, pg);
+                     part, (const unsigned char*)nullptr, rows, C, rpb, 0);
   *nblk_out = nblk;
   return icamd_launch_status();
 }
@@ -1047,7 +1260,7 @@ int icamd_bn_bwd_apply_launch(const float* part, int nrows, const bf16_t* g, con
   }
   const long long nvec = rows * (C / 8);
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(elementwise_grid(nvec, C / 8)), dim3(256), 0, s, g, (const bf16_t*)nullptr, y,
-                     mean, invstd, scale, scale, c1, c2, dy, (bf16_t*)nullptr, (const unsigned char*)nullptr, nvec, C / 8, 0, 0, PoolGather{}, make_fastdiv((unsigned)(C / 8)));
+                     mean, invstd, scale, scale, c1, c2, dy, (bf16_t*)nullptr, (const unsigned char*)nullptr, nvec, C / 8, 0, 0);
   return icamd_launch_status();
 }
 
@@ -1077,10 +1290,15 @@ int icamd_bn_relu_maxpool_fwd_launch(const bf16_t* y, const float* scale, const 
 
 int icamd_maxpool_bwd_launch(const bf16_t* dout, const unsigned char* idx, bf16_t* dx, int N, int IH, int IW, int C, int OH,
                              int OW, hipStream_t s) {
-  if (C % 8 != 0 || (long long)N * IH * IW * (C / 8) >= (1ll << 31)) return ICAMD_ERR_BAD_ARG;
-  const long long total = (long long)N * IH * IW * (C / 8);
-  hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3(elementwise_grid(total, C / 8) * 4), dim3(256), 0, s, dout, idx, dx, N, IH,
-                     IW, C, OH, OW, pool_divs(C, IW, IH));
+  if (C % 8 != 0 || (long long)N * IH * IW * (C / 8) >= (1ll << 31) || OH != (IH - 1) / 2 + 1 || OW != (IW - 1) / 2 + 1)
+    return ICAMD_ERR_BAD_ARG;
+  if (C > 2048) return ICAMD_ERR_UNSUPPORTED;
+  size_t lds = 0;
+  const PoolGather pg = pool_gather_for(idx, IH, IW, C, &lds);
+  const long long rows = (long long)N * IH * IW;
+  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
+  hipLaunchKernelGGL(maxpool3x3s2_bwd_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), lds, s, dout, dx,
+                     (unsigned)rows, C, (unsigned)rpb, pg);
   return icamd_launch_status();
 }
 
@@ -1110,10 +1328,14 @@ int icamd_pack_input_launch(const float* x, bf16_t* out, int B, int Cin, int H, 
 
 int icamd_pack_input_rgb4_launch(const float* x, bf16_t* out, int B, int Cin, int H, int W, int mode, float lam, int yl,
                                  int yh, int xl, int xh, hipStream_t s) {
-  if (Cin < 1 || Cin > 3) return ICAMD_ERR_BAD_ARG;
-  const long long total = (long long)B * H * ((W + (W & 1) + 8) / 2);
+  if (Cin < 1 || Cin > 3 || B < 1 || H < 1 || W < 1) return ICAMD_ERR_BAD_ARG;
+  const long long Wp2 = (W + (W & 1) + 8) / 2;
+  const long long total = (long long)B * H * Wp2;
+  if (total >= (1ll << 31)) return ICAMD_ERR_BAD_ARG;
+  PackDivs dv;
+  dv.wp2 = make_fastdiv((unsigned)Wp2); dv.h = make_fastdiv((unsigned)H);
   hipLaunchKernelGGL(pack_input_rgb4_kernel, dim3(grid_for(total, 256, 1) * 2), dim3(256), 0, s, x, out, B, Cin, H, W, mode,
-                     lam, yl, yh, xl, xh);
+                     lam, yl, yh, xl, xh, dv);
   return icamd_launch_status();
 }
 

@@ -28,10 +28,13 @@ _FUSED_BNBWD = os.environ.get("ICAMD_FUSED_BNBWD", "0") == "1"
 _WGRAD_STREAM = os.environ.get("ICAMD_WGRAD_STREAM", "1") != "0"
 _DUAL_BNBWD = os.environ.get("ICAMD_DUAL_BNBWD", "1") != "0"
 _SUB2_SHORTCUT = os.environ.get("ICAMD_SUB2_SHORTCUT", "1") != "0"
-# stem max-pool backward folded into the BatchNorm backward (icamd_bn_bwd_maxpool3x3s2, bit-identical): measured on MI355X it
-# trades 0.20 ms of pooling backward for +0.27 ms of BatchNorm backward (the gather of <= 4 windows per pixel, done in both
-# passes, is bound by L1 / texture-address requests, not by the HBM bytes it saves), so it is opt-in
-_FUSED_POOL_BWD = os.environ.get("ICAMD_FUSED_POOL_BWD", "0") == "1"
+# stem max-pool backward folded into the BatchNorm backward (icamd_bn_bwd_maxpool3x3s2, bit-identical): the 411 MB pooled
+# gradient at full resolution is never written or read.  On by default since the gather reads the pooled rows from LDS
+# (norm_pool.hip, PoolGather): measured on one MI355X in one call (profiles/r06_stem_tail_ab.txt), 183 + 210 = 393 us for the two
+# folded passes against 195 + 164 + 197 = 555 us for pool backward + the two BatchNorm passes of the parent library, and
+# 17.78 against 18.06 ms per step.  (Round 2, gather from global memory: -0.20 ms of pooling, +0.27 ms of BatchNorm backward.)
+# ICAMD_FUSED_POOL_BWD=0 forces the two-call route.
+_FUSED_POOL_BWD = os.environ.get("ICAMD_FUSED_POOL_BWD", "1") != "0"
 BN_MOMENTUM = 0.1
 
 ARCHS = {
