@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -I../../include"
-UNITS="conv_igemm conv3x3_halo conv1x1_resident conv_fused_bwd conv_fused_fwd conv_stem conv_wgrad norm_pool loss_optim token_ops attention dwconv gemm_nt image_ops collective capi"
+UNITS="conv_igemm conv3x3_halo conv1x1_resident conv_fused_bwd conv_fused_fwd conv_stem conv_wgrad norm_pool loss_optim token_ops attention attention_long dwconv gemm_nt image_ops collective capi"
 asm_of() { echo "build/$1-hip-amdgcn-amd-amdhsa-gfx950.s"; }
 OBJS=""
 ASMS=""
@@ -14,7 +14,7 @@ REUSED=""
 for f in $UNITS; do
   # An object is reused only together with the device assembly it was built with: the ISA lint below reads that file, and an
   # object whose .s is missing (a build directory of an older tree, a deleted file) would otherwise be linked unlinted.
-  if [ ! -f build/$f.o ] || [ ! -f "$(asm_of $f)" ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ icamd_internal.h -nt build/$f.o ] || [ ../../include/icamd.h -nt build/$f.o ]; then
+  if [ ! -f build/$f.o ] || [ ! -f "$(asm_of $f)" ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ icamd_internal.h -nt build/$f.o ] || [ attention_common.h -nt build/$f.o ] || [ ../../include/icamd.h -nt build/$f.o ]; then
     mkdir -p build
     rm -f build/$f.o "$(asm_of $f)"   # a failed compile must not leave a stale object (or its assembly) for the link step
     # -save-temps=obj leaves build/$f-hip-amdgcn-amd-amdhsa-gfx950.s next to the object: the device assembly tools/isa_lint.py reads

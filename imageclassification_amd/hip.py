@@ -121,6 +121,8 @@ _SIGNATURES = {
     "icamd_batch_sum": (c_int, [_P, c_longlong, c_int, c_longlong, _P, c_int, _P]),
     "icamd_strided_rows_copy": (c_int, [_P, c_longlong, _P, c_longlong, c_longlong, c_longlong, _P]),
     "icamd_fill_zero": (c_int, [_P, c_size_t, _P]),
+    # attention: any T >= 1, D = 64.  T <= 208 runs on the LDS-resident kernels (csrc/attention.hip), T > 208 on the tiled ones
+    # (csrc/attention_long.hip); ICAMD_ATTN_LONG=2 forces the tiled route for every T, 0 disables it (see include/icamd.h)
     "icamd_attention_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "icamd_attention_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "icamd_maxpool3x3s2_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -27,8 +27,14 @@ CONFIGS = {
     # name: (patch, dim, depth, heads, mlp_ratio)
     "vit_base_patch16_224": (16, 768, 12, 12, 4),
     "vit_small_patch16_224": (16, 384, 12, 6, 4),
+    "vit_base_patch16_384": (16, 768, 12, 12, 4),    # the _224 architectures at their fine-tuning resolution (T = 577)
+    "vit_small_patch16_384": (16, 384, 12, 6, 4),
     "vit_tiny_test": (16, 128, 2, 2, 4),   # small configuration for parity tests
 }
+
+
+# input size a name is built at when none is given (timm: the model's default_cfg; 224 for every other name)
+NATIVE_SIZE = {"vit_base_patch16_384": 384, "vit_small_patch16_384": 384}
 
 
 def _align(n, a):
@@ -62,7 +68,7 @@ class _Lin:
 
 
 class VisionTransformer(PicklableModel):
-    def __init__(self, arch="vit_base_patch16_224", num_classes=1000, device="cuda", img_size=224, seed=None):
+    def __init__(self, arch="vit_base_patch16_224", num_classes=1000, device="cuda", img_size=None, seed=None):
         hip.require_gpu()
         self.lib = hip.load()
         self.arch, self.num_classes = arch, num_classes
@@ -72,6 +78,10 @@ class VisionTransformer(PicklableModel):
         if self.dim // self.heads != 64:
             raise ValueError("the attention kernel is built for a head dimension of 64")
         self.hidden = self.dim * mlp_ratio
+        if img_size is None:
+            img_size = NATIVE_SIZE.get(arch, 224)
+        if img_size < self.patch or img_size % self.patch != 0:
+            raise ValueError(f"img_size {img_size} is not a positive multiple of the patch size {self.patch}")
         self.img_size = img_size
         self.grid = img_size // self.patch
         self.T = self.grid * self.grid + 1

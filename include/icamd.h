@@ -303,10 +303,15 @@ int icamd_strided_rows_copy(const void* src, long long src_stride, void* dst, lo
                             void* stream);
 int icamd_fill_zero(void* ptr, size_t bytes, void* stream);
 
-/* ---- multi-head self-attention for short sequences (timm Attention under the same reference calls, ViT-B/16:
- *      T = 197 tokens, 12 heads of 64).  qkv: bf16 [B*T][3*H*D] (q | k | v, each [head][D]); out: bf16 [B*T][H*D];
- *      lse / delta: float [B][H][T] (log-sum-exp of the scaled scores; rowsum(dout*out), scratch for the backward).
- *      D must be 64, T <= 208.  One workgroup per (image, head); no atomics, fixed summation order. --------------- */
+/* ---- multi-head self-attention (timm Attention under the same reference calls; ViT-B/16: T = 197 tokens at 224^2,
+ *      577 / 785 / 1025 at 384^2 / 448^2 / 512^2, 12 heads of 64).  qkv: bf16 [B*T][3*H*D] (q | k | v, each [head][D]);
+ *      out: bf16 [B*T][H*D]; lse / delta: float [B][H][T] (log-sum-exp of the scaled scores; rowsum(dout*out), written by
+ *      the backward for its own second kernel).  D must be 64; any T >= 1.  Two routes, no atomics and a fixed summation
+ *      order on both (bitwise reproducible): T <= 208 keeps a whole (image, head) pair resident in LDS, one persistent
+ *      workgroup per CU (attention.hip); T > 208 streams K / V (backward: also Q / dO) through LDS in 64-row tiles with
+ *      an online softmax, one workgroup per (image, head, block of 128 rows) (attention_long.hip).  ICAMD_ATTN_LONG (read
+ *      once per process): 1 / unset = that rule, 2 = every T on the tiled route, 0 = no tiled route (T > 208 returns
+ *      ICAMD_ERR_UNSUPPORTED and writes nothing). ------------------------------------------------------------------ */
 int icamd_attention_fwd(const void* qkv, void* out, float* lse, int B, int T, int H, int D, float scale, void* stream);
 int icamd_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                         int B, int T, int H, int D, float scale, void* stream);

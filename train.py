@@ -24,7 +24,7 @@ from imageclassification_amd.ema import ModelEmaV3
 from imageclassification_amd.engine import evaluate, train_one_epoch
 from imageclassification_amd.mixup import CrossEntropyLoss, LabelSmoothingCrossEntropy, Mixup, SoftTargetCrossEntropy
 from imageclassification_amd.nets import ARCHS, ResNet
-from imageclassification_amd.vit import CONFIGS as VIT_CONFIGS, VisionTransformer
+from imageclassification_amd.vit import CONFIGS as VIT_CONFIGS, NATIVE_SIZE as VIT_NATIVE_SIZE, VisionTransformer
 from imageclassification_amd.convnext import CONFIGS as CNX_CONFIGS, ConvNeXt
 from imageclassification_amd.optim_factory import create_optimizer
 from imageclassification_amd.utils import NativeScalerWithGradNormCount as NativeScaler
@@ -77,11 +77,17 @@ def get_args_parser():
     return p
 
 
-def create_model(name, num_classes, input_size=224, drop_path=0.0):
+def create_model(name, num_classes, input_size=None, drop_path=0.0):
     if name in ARCHS:
         return ResNet(name, num_classes)
     if name in VIT_CONFIGS:
-        return VisionTransformer(name, num_classes, img_size=input_size)
+        # a name that carries its size (vit_*_384) is built at that size only -- timm asserts the same at the first forward; the
+        # command line's --input_size (default 224, which also sizes the data pipeline) has to say it too
+        native = VIT_NATIVE_SIZE.get(name)
+        if native is not None and input_size not in (None, native):
+            raise ValueError(f"model '{name}' is built for {native}x{native} inputs, not --input_size {input_size}: pass "
+                             f"--input_size {native}, or use {name.rsplit('_', 1)[0]}_224 --input_size {input_size}")
+        return VisionTransformer(name, num_classes, img_size=input_size)   # None: the name's own size (224 unless it says 384)
     if name in CNX_CONFIGS:
         return ConvNeXt(name, num_classes, drop_path_rate=drop_path)   # reference train.py:189-192
     raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS)})")
