@@ -527,6 +527,78 @@ static int wgrad_impl(const icamd_conv_desc* d, const void* x, const void* dy, f
   return icamd_slab_reduce_launch(p.bias_slab, dbias, (long long)p.Cout, p.S, accumulate, (hipStream_t)stream);
 }
 
+// ---- grouped 3x3 convolution (conv_grouped.hip).  Algorithmic work: x + y + filter bytes, 2 M C 9 Cg flops.
+static bool gconv_ok(const icamd_conv_desc* d, int groups) {
+  if (!conv_desc_ok(d) || groups <= 0) return false;
+  if (d->KH != 3 || d->KW != 3 || d->pad != 1 || d->Cin != d->Cout) return false;
+  return icamd_gconv3x3_ok(d->N, d->IH, d->IW, d->OH, d->OW, d->Cin, groups, d->stride);
+}
+static GConvParams gconv_params(const icamd_conv_desc* d, int groups) {
+  GConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.N = d->N; p.IH = d->IH; p.IW = d->IW; p.OH = d->OH; p.OW = d->OW; p.C = d->Cin; p.groups = groups; p.stride = d->stride;
+  return p;
+}
+static void gconv_work(ProfScope& prof, const icamd_conv_desc* d, int groups, double filter_bytes_per_element) {
+  if (d == nullptr || groups <= 0) return;
+  const double wel = 9.0 * d->Cout * (d->Cin / groups);
+  prof.work(2.0 * d->N * d->IH * d->IW * d->Cin + 2.0 * d->N * d->OH * d->OW * d->Cout + filter_bytes_per_element * wel,
+            2.0 * d->N * d->OH * d->OW * wel);
+}
+
+int icamd_gconv3x3_supported(const icamd_conv_desc* d, int groups) { return gconv_ok(d, groups) ? 1 : 0; }
+
+int icamd_gconv3x3_fwd(const icamd_conv_desc* d, int groups, const void* x, const void* w, void* y, float* stats, void* stream) {
+  ProfScope _prof(PC_IGEMM_FWD, stream);
+  gconv_work(_prof, d, groups, 2.0);
+  if (d == nullptr || x == nullptr || w == nullptr || y == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!gconv_ok(d, groups)) return ICAMD_ERR_UNSUPPORTED;
+  GConvParams p = gconv_params(d, groups);
+  p.in = (const bf16_t*)x; p.w = (const bf16_t*)w; p.out = (bf16_t*)y; p.stats = stats;
+  return icamd_gconv3x3_fwd_launch(p, (hipStream_t)stream);
+}
+
+int icamd_gconv3x3_fwd_act(const icamd_conv_desc* d, int groups, const void* x, const void* w, void* y, const float* bias, int relu,
+                           void* stream) {
+  ProfScope _prof(PC_IGEMM_FWD, stream);
+  gconv_work(_prof, d, groups, 2.0);
+  if (d == nullptr || x == nullptr || w == nullptr || y == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!gconv_ok(d, groups)) return ICAMD_ERR_UNSUPPORTED;
+  GConvParams p = gconv_params(d, groups);
+  p.in = (const bf16_t*)x; p.w = (const bf16_t*)w; p.out = (bf16_t*)y; p.bias = bias; p.relu = relu ? 1 : 0;
+  return icamd_gconv3x3_fwd_launch(p, (hipStream_t)stream);
+}
+
+int icamd_gconv3x3_dgrad(const icamd_conv_desc* d, int groups, const void* dy, const void* w, void* dx, void* stream) {
+  ProfScope _prof(PC_IGEMM_DGRAD, stream);
+  gconv_work(_prof, d, groups, 2.0);
+  if (d == nullptr || dy == nullptr || w == nullptr || dx == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!gconv_ok(d, groups)) return ICAMD_ERR_UNSUPPORTED;
+  GConvParams p = gconv_params(d, groups);
+  p.in = (const bf16_t*)dy; p.w = (const bf16_t*)w; p.out = (bf16_t*)dx;
+  return icamd_gconv3x3_dgrad_launch(p, (hipStream_t)stream);
+}
+
+size_t icamd_gconv3x3_wgrad_workspace_bytes(const icamd_conv_desc* d, int groups) {
+  if (!gconv_ok(d, groups)) return 0;
+  return icamd_gconv3x3_wgrad_bytes(d->N, d->IH, d->IW, d->OH, d->OW, d->Cin, groups, d->stride);
+}
+
+int icamd_gconv3x3_wgrad(const icamd_conv_desc* d, int groups, const void* x, const void* dy, float* dw, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+  ProfScope _prof(PC_WGRAD, stream);
+  gconv_work(_prof, d, groups, 4.0);
+  if (d == nullptr || x == nullptr || dy == nullptr || dw == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!gconv_ok(d, groups)) return ICAMD_ERR_UNSUPPORTED;
+  const size_t need = icamd_gconv3x3_wgrad_workspace_bytes(d, groups);
+  if (workspace == nullptr || need == 0 || workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
+  GConvParams p = gconv_params(d, groups);
+  p.in = (const bf16_t*)x; p.dy = (const bf16_t*)dy; p.slab = (float*)workspace;
+  const int rc = icamd_gconv3x3_wgrad_launch(p, (hipStream_t)stream);
+  if (rc) return rc;
+  return icamd_slab_reduce_launch(p.slab, dw, (long long)d->Cin * 9 * (d->Cin / groups), p.S, accumulate, (hipStream_t)stream);
+}
+
 int icamd_filter_transpose(const void* src_base, void* dst_base, const int64_t* descs, const int32_t* jobs, int njobs,
                            void* stream) {
   ProfScope _prof(PC_OPTIM, stream);

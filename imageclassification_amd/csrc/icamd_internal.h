@@ -55,6 +55,27 @@ struct Halo3x3Params {
 bool icamd_halo3x3_wanted(int N, int H, int W, int C, int Cout);
 int icamd_halo3x3_launch(Halo3x3Params& p, hipStream_t stream);
 
+// Grouped 3x3 / pad 1 / stride 1 or 2 convolution, Cin == Cout == C, C / groups in {4, 8, 16, 32} (conv_grouped.hip)
+struct GConvParams {
+  const bf16_t* in;      // forward / weight gradient: x [N][IH][IW][C]; data gradient: dy [N][OH][OW][C]
+  const bf16_t* w;       // [C][3][3][Cg], the forward layout for every launch
+  bf16_t* out;           // forward: y; data gradient: dx
+  const bf16_t* dy;      // weight gradient only
+  float* slab;           // weight gradient: [S][C][3][3][Cg] partial sums
+  const float* bias;     // optional [C] (forward)
+  float* stats;          // optional [ceil(M/128)][2][C] (forward)
+  int relu;
+  int N, IH, IW, OH, OW, C, groups, stride;
+  int Cg, M, npix_in, nalloc;          // filled by the launcher
+  int S, tiles_per_split, ntiles;      // filled by the launcher (weight gradient)
+  FastDiv divOHW, divOW;
+};
+bool icamd_gconv3x3_ok(int N, int IH, int IW, int OH, int OW, int C, int groups, int stride);
+int icamd_gconv3x3_fwd_launch(GConvParams& p, hipStream_t stream);
+int icamd_gconv3x3_dgrad_launch(GConvParams& p, hipStream_t stream);
+size_t icamd_gconv3x3_wgrad_bytes(int N, int IH, int IW, int OH, int OW, int C, int groups, int stride);
+int icamd_gconv3x3_wgrad_launch(GConvParams& p, hipStream_t stream);   // fills p.S; the caller folds the slabs
+
 // Dense NT GEMM for big pointwise problems: out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) (+ addend[m][n])
 struct GemmNtParams {
   const bf16_t* A;       // [M][K]

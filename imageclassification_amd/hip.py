@@ -83,6 +83,13 @@ _SIGNATURES = {
     "icamd_conv2d_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvDesc)]),
     "icamd_conv2d_wgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P, c_size_t, _P]),
     "icamd_conv2d_wgrad_bias": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    # grouped 3x3 convolution (csrc/conv_grouped.hip): the dense descriptor plus the group count; filter [C][3][3][C/groups]
+    "icamd_gconv3x3_supported": (c_int, [POINTER(ConvDesc), c_int]),
+    "icamd_gconv3x3_fwd": (c_int, [POINTER(ConvDesc), c_int, _P, _P, _P, _P, _P]),
+    "icamd_gconv3x3_fwd_act": (c_int, [POINTER(ConvDesc), c_int, _P, _P, _P, _P, c_int, _P]),
+    "icamd_gconv3x3_dgrad": (c_int, [POINTER(ConvDesc), c_int, _P, _P, _P, _P]),
+    "icamd_gconv3x3_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvDesc), c_int]),
+    "icamd_gconv3x3_wgrad": (c_int, [POINTER(ConvDesc), c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "icamd_filter_transpose": (c_int, [_P, _P, _P, _P, c_int, _P]),
     "icamd_filter_transpose_tiled": (c_int, [_P, _P, _P, _P, c_int, _P]),
     "icamd_bn_workspace_bytes": (c_size_t, [c_int]),

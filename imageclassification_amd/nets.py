@@ -1,4 +1,5 @@
-"""ResNet-18/34/50 on the gfx950 kernels: static layer lists with hand-written forward and backward.
+"""The ResNet family (ResNet-18/34/50/101/152, wide ResNet-50/101-2, ResNeXt-50/101 32x4d) on the gfx950 kernels: static layer
+lists with hand-written forward and backward.
 
 The reference builds its network with timm.create_model (/root/reference/train.py:194) and runs it through
 autograd (engine.py:48,51,64,72); there is no model code in the reference tree.  Here a model is a flat list
@@ -37,11 +38,68 @@ _SUB2_SHORTCUT = os.environ.get("ICAMD_SUB2_SHORTCUT", "1") != "0"
 _FUSED_POOL_BWD = os.environ.get("ICAMD_FUSED_POOL_BWD", "1") != "0"
 BN_MOMENTUM = 0.1
 
+# name -> (block, blocks per stage, cardinality, base width), as timm / torchvision: a bottleneck's inner width is
+# floor(planes * base_width / 64) * cardinality and its 3x3 convolution has `cardinality` groups
 ARCHS = {
-    "resnet18": ("basic", [2, 2, 2, 2]),
-    "resnet34": ("basic", [3, 4, 6, 3]),
-    "resnet50": ("bottleneck", [3, 4, 6, 3]),
+    "resnet18": ("basic", [2, 2, 2, 2], 1, 64),
+    "resnet34": ("basic", [3, 4, 6, 3], 1, 64),
+    "resnet50": ("bottleneck", [3, 4, 6, 3], 1, 64),
+    "resnet101": ("bottleneck", [3, 4, 23, 3], 1, 64),
+    "resnet152": ("bottleneck", [3, 8, 36, 3], 1, 64),
+    "wide_resnet50_2": ("bottleneck", [3, 4, 6, 3], 1, 128),
+    "wide_resnet101_2": ("bottleneck", [3, 4, 23, 3], 1, 128),
+    "resnext50_32x4d": ("bottleneck", [3, 4, 6, 3], 32, 4),
+    "resnext101_32x4d": ("bottleneck", [3, 4, 23, 3], 32, 4),
 }
+
+
+def block_specs(arch):
+    """The residual blocks of `arch` as plain data (no GPU, no arenas): one dict per block with
+    convs: [(name, cin, cout, k, stride, pad, groups)], bns: [(name, channels)], down: None or ((conv tuple), (bn tuple))."""
+    block, layers, cardinality, base_width = ARCHS[arch]
+    expansion = 4 if block == "bottleneck" else 1
+    specs = []
+    inplanes = 64
+    for li, (planes, nblocks) in enumerate(zip([64, 128, 256, 512], layers)):
+        for bi in range(nblocks):
+            stride = 2 if (bi == 0 and li > 0) else 1
+            name = f"layer{li + 1}.{bi}"
+            outplanes = planes * expansion
+            if block == "bottleneck":
+                width = int(math.floor(planes * base_width / 64)) * cardinality
+                convs = [(f"{name}.conv1", inplanes, width, 1, 1, 0, 1),
+                         (f"{name}.conv2", width, width, 3, stride, 1, cardinality),
+                         (f"{name}.conv3", width, outplanes, 1, 1, 0, 1)]
+                bns = [(f"{name}.bn1", width), (f"{name}.bn2", width), (f"{name}.bn3", outplanes)]
+            else:
+                convs = [(f"{name}.conv1", inplanes, planes, 3, stride, 1, 1),
+                         (f"{name}.conv2", planes, planes, 3, 1, 1, 1)]
+                bns = [(f"{name}.bn1", planes), (f"{name}.bn2", planes)]
+            down = None
+            if stride != 1 or inplanes != outplanes:
+                down = ((f"{name}.downsample.0", inplanes, outplanes, 1, stride, 0, 1), (f"{name}.downsample.1", outplanes))
+            specs.append({"name": name, "stride": stride, "convs": convs, "bns": bns, "down": down})
+            inplanes = outplanes
+    return specs
+
+
+def param_shapes(arch, num_classes=1000):
+    """[(parameter name, torch shape)] of `arch` in module order, from ARCHS alone (what state_dict() / the arenas hold)."""
+    def bn(name, c):
+        return [(name + ".weight", (c,)), (name + ".bias", (c,))]
+
+    def conv(name, cin, cout, k, stride, pad, groups):
+        return [(name + ".weight", (cout, cin // groups, k, k))]
+
+    out = conv("conv1", 3, 64, 7, 2, 3, 1) + bn("bn1", 64)
+    feat = 64
+    for blk in block_specs(arch):
+        for c, b in zip(blk["convs"], blk["bns"]):
+            out += conv(*c) + bn(*b)
+        if blk["down"] is not None:
+            out += conv(*blk["down"][0]) + bn(*blk["down"][1])
+        feat = blk["convs"][-1][2]
+    return out + [("fc.weight", (num_classes, feat)), ("fc.bias", (num_classes,))]
 
 
 def _align(n, a):
@@ -58,10 +116,12 @@ class _Param:
 
 
 class _Conv:
-    """Convolution record. weight param in arena layout [Cout_p][KH][KW][Cin_p]."""
+    """Convolution record. weight param in arena layout [Cout_p][KH][KW][Cin_p / groups] (groups > 1: ResNeXt's 3x3, which runs on
+    the icamd_gconv3x3_* entries with this same filter for forward, data gradient and weight gradient)."""
 
-    def __init__(self, name, cin, cout, k, stride, pad, cin_p=None, cout_p=None, bias=False, k_p=None):
+    def __init__(self, name, cin, cout, k, stride, pad, cin_p=None, cout_p=None, bias=False, k_p=None, groups=1):
         self.name = name
+        self.groups = groups
         self.cin, self.cout, self.k, self.stride, self.pad = cin, cout, k, stride, pad
         self.cin_p = cin_p or cin
         self.cout_p = cout_p or cout
@@ -102,11 +162,11 @@ class ResNet(PicklableModel):
         self._fold_dirty = True
         # eval forwards use BatchNorm-folded filters (ICAMD_EVAL_FOLD=0 keeps the separate BatchNorm pass)
         self.fold_eval = os.environ.get("ICAMD_EVAL_FOLD", "1") != "0"
-        block, layers = ARCHS[arch]
+        block = ARCHS[arch][0]
         self.block = block
         self.expansion = 4 if block == "bottleneck" else 1
         self.ncls_p = _align(num_classes, 64)
-        self._build_graph(layers)
+        self._build_graph()
         self._allocate()
         self.num_batches_tracked = 0
         self._ws = {}
@@ -116,7 +176,7 @@ class ResNet(PicklableModel):
         self.init_weights(zero_init_last=zero_init_last, seed=seed)
 
     # ------------------------------------------------------------------ structure
-    def _build_graph(self, layers):
+    def _build_graph(self):
         self.convs, self.bns = [], []
         # stem filters live as [64][8][8][4] (row 7, column 7, channel 3 zero): the layout icamd_stem7x7s2_fwd / _wgrad
         # reduce over, on the [N][H][W+8][4] image icamd_pack_input_rgb4 writes
@@ -124,32 +184,22 @@ class ResNet(PicklableModel):
         self.stem_bn = self._bn("bn1", 64)
         self.blocks = []
         inplanes = 64
-        for li, (planes, nblocks) in enumerate(zip([64, 128, 256, 512], layers)):
-            for bi in range(nblocks):
-                stride = 2 if (bi == 0 and li > 0) else 1
-                name = f"layer{li + 1}.{bi}"
-                outplanes = planes * self.expansion
-                blk = {"name": name, "stride": stride}
-                if self.block == "bottleneck":
-                    blk["convs"] = [self._conv(f"{name}.conv1", inplanes, planes, 1, 1, 0),
-                                    self._conv(f"{name}.conv2", planes, planes, 3, stride, 1),
-                                    self._conv(f"{name}.conv3", planes, outplanes, 1, 1, 0)]
-                    blk["bns"] = [self._bn(f"{name}.bn1", planes), self._bn(f"{name}.bn2", planes),
-                                  self._bn(f"{name}.bn3", outplanes)]
-                else:
-                    blk["convs"] = [self._conv(f"{name}.conv1", inplanes, planes, 3, stride, 1),
-                                    self._conv(f"{name}.conv2", planes, planes, 3, 1, 1)]
-                    blk["bns"] = [self._bn(f"{name}.bn1", planes), self._bn(f"{name}.bn2", planes)]
-                if stride != 1 or inplanes != outplanes:
-                    blk["down_conv"] = self._conv(f"{name}.downsample.0", inplanes, outplanes, 1, stride, 0)
-                    blk["down_bn"] = self._bn(f"{name}.downsample.1", outplanes)
-                self.blocks.append(blk)
-                inplanes = outplanes
+        for spec in block_specs(self.arch):
+            blk = {"name": spec["name"], "stride": spec["stride"]}
+            # (record order: the block's convolutions, its BatchNorms, then the shortcut pair -- as before the specs existed)
+            blk["convs"] = [self._conv(n, cin, cout, k, st, pad, groups=g) for n, cin, cout, k, st, pad, g in spec["convs"]]
+            blk["bns"] = [self._bn(n, c) for n, c in spec["bns"]]
+            if spec["down"] is not None:
+                (n, cin, cout, k, st, pad, g), (bn_name, bn_c) = spec["down"]
+                blk["down_conv"] = self._conv(n, cin, cout, k, st, pad, groups=g)
+                blk["down_bn"] = self._bn(bn_name, bn_c)
+            self.blocks.append(blk)
+            inplanes = spec["convs"][-1][2]
         self.feat_dim = inplanes
         self.fc = self._conv("fc", inplanes, self.num_classes, 1, 1, 0, cout_p=self.ncls_p, bias=True)
 
-    def _conv(self, name, cin, cout, k, stride, pad, cin_p=None, cout_p=None, bias=False, k_p=None):
-        c = _Conv(name, cin, cout, k, stride, pad, cin_p, cout_p, bias, k_p)
+    def _conv(self, name, cin, cout, k, stride, pad, cin_p=None, cout_p=None, bias=False, k_p=None, groups=1):
+        c = _Conv(name, cin, cout, k, stride, pad, cin_p, cout_p, bias, k_p, groups)
         self.convs.append(c)
         return c
 
@@ -186,7 +236,7 @@ class ResNet(PicklableModel):
         for m in order:
             if isinstance(m, _Conv):
                 wname = m.name + ".weight"
-                m.w = add(wname, (m.cout, m.cin, m.k, m.k), "conv", (m.cout_p, m.k_p, m.k_p, m.cin_p))
+                m.w = add(wname, (m.cout, m.cin // m.groups, m.k, m.k), "conv", (m.cout_p, m.k_p, m.k_p, m.cin_p // m.groups))
                 if m.has_bias:
                     m.b = add(m.name + ".bias", (m.cout,), "vec", (m.cout_p,))
             else:
@@ -202,11 +252,12 @@ class ResNet(PicklableModel):
         self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev)
         self.buffer_arena = torch.zeros(max(boff, 64), dtype=torch.float32, device=dev)
         self.stat_arena = torch.zeros(max(soff, 64), dtype=torch.float32, device=dev)
-        # transposed filters for the data-gradient kernels (every conv except the stem)
+        # transposed filters for the data-gradient kernels (every conv except the stem and the grouped ones, whose data gradient
+        # reads the forward layout)
         toff = 0
         descs, jobs, tjobs = [], [], []
         for m in self.convs:
-            if m is self.stem_conv:
+            if m is self.stem_conv or m.groups > 1:
                 continue
             m.wt_offset = toff
             T = m.k * m.k
@@ -403,6 +454,12 @@ class ResNet(PicklableModel):
                                                    self.eval_shift.data_ptr() + 4 * bn.shift_offset, None, int(relu), N, IH, IW,
                                                    conv.cout_p, s), conv.name)
             return d
+        if conv.groups > 1:
+            assert residual is None
+            hip.check(self.lib.icamd_gconv3x3_fwd_act(ctypes.byref(d), conv.groups, x, self.shadow_eval.data_ptr() + 2 * conv.w.offset,
+                                                      out.data_ptr(), self.eval_shift.data_ptr() + 4 * bn.shift_offset, int(relu), s),
+                      conv.name)
+            return d
         hip.check(self.lib.icamd_conv2d_fwd_act(ctypes.byref(d), x, self.shadow_eval.data_ptr() + 2 * conv.w.offset,
                                                 out.data_ptr(), self.eval_shift.data_ptr() + 4 * bn.shift_offset, residual,
                                                 int(relu), s), conv.name)
@@ -484,7 +541,12 @@ class ResNet(PicklableModel):
                 acts.append(act(N, d.OH, d.OW, conv.cout_p))
                 max_act = max(max_act, ys[-1].numel())
                 max_stats = max(max_stats, lib.icamd_conv2d_stats_rows(ctypes.byref(d)) * 2 * conv.cout_p)
-                max_wg = max(max_wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
+                if conv.groups > 1:
+                    if not lib.icamd_gconv3x3_supported(ctypes.byref(d), conv.groups):
+                        raise hip.IcamdError(f"{conv.name}: no grouped 3x3 kernel for {d.key()} with {conv.groups} groups")
+                    max_wg = max(max_wg, lib.icamd_gconv3x3_wgrad_workspace_bytes(ctypes.byref(d), conv.groups))
+                else:
+                    max_wg = max(max_wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
                 max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d.OH * d.OW, conv.cout_p))
                 ih, iw = d.OH, d.OW
             b["y"], b["a"] = ys, acts
@@ -561,6 +623,9 @@ class ResNet(PicklableModel):
                 return
             if stem:
                 hip.check(lib.icamd_stem7x7s2_fwd(x, self._w(conv), y.data_ptr(), None, stats_ptr, 0, N, IH, IW, conv.cout_p, s),
+                          conv.name)
+            elif conv.groups > 1:
+                hip.check(lib.icamd_gconv3x3_fwd(ctypes.byref(d), conv.groups, x, self._w(conv), y.data_ptr(), stats_ptr, s),
                           conv.name)
             else:
                 hip.check(lib.icamd_conv2d_fwd(ctypes.byref(d), x, self._w(conv), y.data_ptr(), None, None, stats_ptr, s),
@@ -736,6 +801,9 @@ class ResNet(PicklableModel):
             if conv is self.stem_conv:
                 hip.check(lib.icamd_stem7x7s2_wgrad(x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, n, ih, iw, conv.cout_p, ws_side),
                           conv.name + " wgrad")
+            elif conv.groups > 1:
+                hip.check(lib.icamd_gconv3x3_wgrad(ctypes.byref(d), conv.groups, x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb,
+                                                   ws_side), conv.name + " wgrad")
             else:
                 hip.check(lib.icamd_conv2d_wgrad(ctypes.byref(d), x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, ws_side),
                           conv.name + " wgrad")
@@ -758,6 +826,11 @@ class ResNet(PicklableModel):
 
         def dgrad(conv, dy_ptr, dx_ptr, addend, n, ih, iw, addend_bits=None):
             d = conv.desc(n, ih, iw)
+            if conv.groups > 1:
+                assert addend is None
+                hip.check(lib.icamd_gconv3x3_dgrad(ctypes.byref(d), conv.groups, dy_ptr, self._w(conv), dx_ptr, s),
+                          conv.name + " dgrad")
+                return
             hip.check(lib.icamd_conv2d_dgrad(ctypes.byref(d), dy_ptr, self._wt(conv), dx_ptr, addend, addend_bits, s),
                       conv.name + " dgrad")
 
@@ -992,6 +1065,10 @@ class ResNet(PicklableModel):
                 hip.check(lib.icamd_stem7x7s2_wgrad(x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, n, ih, iw, conv.cout_p, s),
                           conv.name + " wgrad")
                 return
+            if conv.groups > 1:
+                hip.check(lib.icamd_gconv3x3_wgrad(ctypes.byref(d), conv.groups, x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, s),
+                          conv.name + " wgrad")
+                return
             hip.check(lib.icamd_conv2d_wgrad(ctypes.byref(d), x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, s),
                       conv.name + " wgrad")
 
@@ -1062,6 +1139,13 @@ class ResNet(PicklableModel):
             for i in range(nconv - 1, 0, -1):
                 x_i = b["a"][i - 1]
                 wgrad(convs[i], x_i.data_ptr(), Y, N, *hw_in[i])
+                if convs[i].groups > 1:
+                    # the grouped data gradient has no fused BatchNorm reduction: plain data gradient, two-pass BatchNorm backward
+                    dg = convs[i].desc(N, *hw_in[i])
+                    hip.check(lib.icamd_gconv3x3_dgrad(ctypes.byref(dg), convs[i].groups, Y, self._w(convs[i]), DA, s),
+                              convs[i].name + " dgrad")
+                    bn_bwd(bns[i - 1], DA, None, b["y"][i - 1], Y, None, True)
+                    continue
                 nrows = dgrad_bnbwd(convs[i], Y, DA, None, N, *hw_in[i], bns[i - 1], b["y"][i - 1], None, True)
                 bn_bwd_from_partials(bns[i - 1], nrows, DA, b["y"][i - 1], Y)
             wgrad(convs[0], xin.data_ptr(), Y, N, h, w)

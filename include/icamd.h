@@ -112,6 +112,27 @@ int icamd_conv2d_wgrad(const icamd_conv_desc* d, const void* x, const void* dy, 
 int icamd_conv2d_wgrad_bias(const icamd_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias,
                             int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- grouped 3x3 convolution (ResNeXt's conv2: timm Bottleneck.conv2 with cardinality > 1) ----------------
+ * Problem class: KH = KW = 3, pad 1, stride 1 or 2, Cin == Cout == C, C % 32 == 0, C % groups == 0 and
+ * Cg = C / groups in {4, 8, 16, 32}; any N, IH, IW whose staged tile fits the LDS (image widths up to a few hundred
+ * pixels).  Everything else: _supported returns 0, the launches ICAMD_ERR_UNSUPPORTED (nothing is written).  The
+ * descriptor is the dense one; the group count travels beside it.  The filter is bf16 [C][3][3][Cg] for EVERY entry: the
+ * data gradient re-indexes the forward layout itself, a grouped convolution has no transposed copy. */
+int icamd_gconv3x3_supported(const icamd_conv_desc* d, int groups);
+/* stats: as the dense forward -- float [icamd_conv2d_stats_rows][2][C], partial sum / sum of squares of the ROUNDED y, one
+ * row per 128 output pixels; may be NULL */
+int icamd_gconv3x3_fwd(const icamd_conv_desc* d, int groups, const void* x, const void* w, void* y, float* stats, void* stream);
+/* evaluate(): y = [relu](conv + bias), one rounding; w is the BatchNorm-folded filter (fold with Cout = C, K = 9 * Cg) */
+int icamd_gconv3x3_fwd_act(const icamd_conv_desc* d, int groups, const void* x, const void* w, void* y, const float* bias, int relu,
+                           void* stream);
+/* dx = conv_transpose(dy, w): every dx element written once, stride 1 and stride 2 in ONE launch each */
+int icamd_gconv3x3_dgrad(const icamd_conv_desc* d, int groups, const void* dy, const void* w, void* dx, void* stream);
+size_t icamd_gconv3x3_wgrad_workspace_bytes(const icamd_conv_desc* d, int groups);
+/* dw fp32 [C][3][3][Cg] = (accumulate ? dw : 0) + sum over pixels; fp32 partial slabs [S][C][3][3][Cg] in the workspace,
+ * folded in a fixed order: bitwise reproducible */
+int icamd_gconv3x3_wgrad(const icamd_conv_desc* d, int groups, const void* x, const void* dy, float* dw, int accumulate,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* table-driven batched filter transpose [Cout][T][Cin] -> [Cin][T][Cout] (bf16).
  * descs: int64[nlayers][8] = {src_off, dst_off, Cout, T, Cin, 0,0,0} (element offsets);
  * jobs: int32[njobs][2] = {layer, first destination element}, each job covers 4096 destination elements. */
