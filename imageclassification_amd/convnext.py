@@ -19,6 +19,7 @@ import torch
 
 from . import hip
 from .checkpoint import PicklableModel
+from .streams import side_lane
 from .vit import _P, _align
 
 LN_EPS = 1e-6
@@ -507,9 +508,8 @@ class ConvNeXt(PicklableModel):
         csp, csb = ws["cs_ws"].data_ptr(), ws["cs_bytes"]
         G = [g.data_ptr() for g in self._scratch(ws)]
 
-        lane = self._side_lane()
-        lane.enabled = lane.side is not None and getattr(self, "wgrad_side_stream", True)
-        lane.begin()
+        lane = side_lane(self, "ICAMD_WGRAD_STREAM", True)
+        lane.begin(getattr(self, "wgrad_side_stream", True))
 
         def W(ptr):
             """`ptr` is about to be overwritten on the main stream: wait for side-lane launches still reading it."""
@@ -612,8 +612,3 @@ class ConvNeXt(PicklableModel):
         if hook:
             hook(0, None)
 
-    def _side_lane(self):
-        if getattr(self, "_lane", None) is None:
-            from .streams import SideLane
-            self._lane = SideLane(self.device, os.environ.get("ICAMD_WGRAD_STREAM", "1") != "0")
-        return self._lane

@@ -15,14 +15,17 @@ Data layout in HBM: activations NHWC bf16; filters [Cout][KH][KW][Cin] (stem Cin
 zero-padded to a multiple of 64); everything 256 B aligned inside the arenas.
 """
 import ctypes
+import itertools
 import math
 import os
 from collections import OrderedDict
+from types import SimpleNamespace
 
 import torch
 
 from . import hip
 from .checkpoint import PicklableModel
+from .streams import side_lane
 
 BN_EPS = 1e-5
 _FUSED_BNBWD = os.environ.get("ICAMD_FUSED_BNBWD", "0") == "1"
@@ -170,9 +173,10 @@ class ResNet(PicklableModel):
         self._allocate()
         self.num_batches_tracked = 0
         self._ws = {}
-        self._streams_ready = False
         self.wgrad_side_stream = True   # bench.py turns this off for its per-kernel timing pass
-        self.grad_ready_hook = None   # called with (param_offset_lo, param_offset_hi) as gradients complete
+        # called as gradients complete with (param_offset_lo, param_offset_hi or None, events): `events` are side-stream events a
+        # consumer on another stream must wait for besides the main stream
+        self.grad_ready_hook = None
         self.init_weights(zero_init_last=zero_init_last, seed=seed)
 
     # ------------------------------------------------------------------ structure
@@ -208,16 +212,19 @@ class ResNet(PicklableModel):
         self.bns.append(b)
         return b
 
+    def conv_bn_pairs(self):
+        """[(conv, bn)] in module order: the stem, then each block's convolutions, then its shortcut pair."""
+        pairs = [(self.stem_conv, self.stem_bn)]
+        for blk in self.blocks:
+            pairs += zip(blk["convs"], blk["bns"])
+            if "down_conv" in blk:
+                pairs.append((blk["down_conv"], blk["down_bn"]))
+        return pairs
+
     def _allocate(self):
         dev = self.device
         # parameter order = timm/torchvision module order (conv, bn, ..., downsample, fc)
-        order = [self.stem_conv, self.stem_bn]
-        for blk in self.blocks:
-            for c, b in zip(blk["convs"], blk["bns"]):
-                order += [c, b]
-            if "down_conv" in blk:
-                order += [blk["down_conv"], blk["down_bn"]]
-        order.append(self.fc)
+        order = [m for pair in self.conv_bn_pairs() for m in pair] + [self.fc]
         self.params = OrderedDict()
         off = 0
 
@@ -434,12 +441,7 @@ class ResNet(PicklableModel):
                 b.shift_offset = off
                 off += b.c
         s = hip.stream_ptr()
-        pairs = [(self.stem_conv, self.stem_bn)]
-        for blk in self.blocks:
-            pairs += list(zip(blk["convs"], blk["bns"]))
-            if "down_conv" in blk:
-                pairs.append((blk["down_conv"], blk["down_bn"]))
-        for conv, bn in pairs:
+        for conv, bn in self.conv_bn_pairs():
             rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
             hip.check(self.lib.icamd_bn_fold_filters(self._pf(conv.w), self._pf(bn.weight), self._pf(bn.bias), rm,
                                                      rm + 4 * bn.c, BN_EPS, conv.cout_p, conv.w.numel // conv.cout_p,
@@ -449,20 +451,8 @@ class ResNet(PicklableModel):
 
     def _conv_act_eval(self, conv, bn, x, N, IH, IW, out, residual, relu, s):
         d = conv.desc(N, IH, IW)
-        if conv is self.stem_conv:
-            hip.check(self.lib.icamd_stem7x7s2_fwd(x, self.shadow_eval.data_ptr() + 2 * conv.w.offset, out.data_ptr(),
-                                                   self.eval_shift.data_ptr() + 4 * bn.shift_offset, None, int(relu), N, IH, IW,
-                                                   conv.cout_p, s), conv.name)
-            return d
-        if conv.groups > 1:
-            assert residual is None
-            hip.check(self.lib.icamd_gconv3x3_fwd_act(ctypes.byref(d), conv.groups, x, self.shadow_eval.data_ptr() + 2 * conv.w.offset,
-                                                      out.data_ptr(), self.eval_shift.data_ptr() + 4 * bn.shift_offset, int(relu), s),
-                      conv.name)
-            return d
-        hip.check(self.lib.icamd_conv2d_fwd_act(ctypes.byref(d), x, self.shadow_eval.data_ptr() + 2 * conv.w.offset,
-                                                out.data_ptr(), self.eval_shift.data_ptr() + 4 * bn.shift_offset, residual,
-                                                int(relu), s), conv.name)
+        self._conv_fwd(conv, d, x, self.shadow_eval.data_ptr() + 2 * conv.w.offset, out.data_ptr(), s,
+                       shift=self.eval_shift.data_ptr() + 4 * bn.shift_offset, residual=residual, relu=int(relu))
         return d
 
     def _forward_eval_folded(self, ws):
@@ -527,37 +517,35 @@ class ResNet(PicklableModel):
         ws["p0_idx"] = torch.empty(N, PH, PW, 64, dtype=torch.uint8, device=dev)
         max_act = max(ws["y0"].numel(), ws["x8"].numel())
         max_stats = lib.icamd_conv2d_stats_rows(ctypes.byref(d0)) * 2 * 64
-        max_wg = lib.icamd_stem7x7s2_wgrad_workspace_bytes(N, H, Ws, 64)
+        max_wg = self._wgrad_workspace_bytes(self.stem_conv, d0)
         max_bnb = lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, 64)
         h, w = PH, PW
         blocks_ws = []
         for blk in self.blocks:
             b = {}
             ih, iw = h, w
-            ys, acts = [], []
-            for ci, conv in enumerate(blk["convs"]):
+            ys, acts, launches = [], [], []
+            for conv in blk["convs"]:
                 d = conv.desc(N, ih, iw)
                 ys.append(act(N, d.OH, d.OW, conv.cout_p))
                 acts.append(act(N, d.OH, d.OW, conv.cout_p))
                 max_act = max(max_act, ys[-1].numel())
-                max_stats = max(max_stats, lib.icamd_conv2d_stats_rows(ctypes.byref(d)) * 2 * conv.cout_p)
-                if conv.groups > 1:
-                    if not lib.icamd_gconv3x3_supported(ctypes.byref(d), conv.groups):
-                        raise hip.IcamdError(f"{conv.name}: no grouped 3x3 kernel for {d.key()} with {conv.groups} groups")
-                    max_wg = max(max_wg, lib.icamd_gconv3x3_wgrad_workspace_bytes(ctypes.byref(d), conv.groups))
-                else:
-                    max_wg = max(max_wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(d)))
-                max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d.OH * d.OW, conv.cout_p))
+                launches.append((conv, d))
                 ih, iw = d.OH, d.OW
             b["y"], b["a"] = ys, acts
+            b["hw"] = [(d.IH, d.IW) for _, d in launches]     # input size of each convolution
             b["mask"] = torch.empty(acts[-1].numel() // 8, dtype=torch.uint8, device=dev)   # ReLU mask of the block output
             if "down_conv" in blk:
                 dd = blk["down_conv"].desc(N, h, w)
                 b["yd"] = act(N, dd.OH, dd.OW, blk["down_conv"].cout_p)
                 b["ad"] = act(N, dd.OH, dd.OW, blk["down_conv"].cout_p)
-                max_stats = max(max_stats, lib.icamd_conv2d_stats_rows(ctypes.byref(dd)) * 2 * blk["down_conv"].cout_p)
-                max_wg = max(max_wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(dd)))
-                max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * dd.OH * dd.OW, blk["down_conv"].cout_p))
+                launches.append((blk["down_conv"], dd))
+            for conv, d in launches:      # every convolution of the block, shortcut included
+                if conv.groups > 1 and not lib.icamd_gconv3x3_supported(ctypes.byref(d), conv.groups):
+                    raise hip.IcamdError(f"{conv.name}: no grouped 3x3 kernel for {d.key()} with {conv.groups} groups")
+                max_stats = max(max_stats, lib.icamd_conv2d_stats_rows(ctypes.byref(d)) * 2 * conv.cout_p)
+                max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d))
+                max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d.OH * d.OW, conv.cout_p))
             blocks_ws.append(b)
             h, w = ih, iw
         ws["blocks"] = blocks_ws
@@ -565,7 +553,7 @@ class ResNet(PicklableModel):
         ws["pooled"] = torch.empty(N, self.feat_dim, dtype=torch.bfloat16, device=dev)
         ws["logits"] = torch.zeros(N, self.ncls_p, dtype=torch.bfloat16, device=dev)
         dfc = self.fc.desc(N, 1, 1)
-        max_wg = max(max_wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(dfc)))
+        max_wg = max(max_wg, self._wgrad_workspace_bytes(self.fc, dfc))
         ws["stats"] = torch.empty(max_stats, dtype=torch.float32, device=dev)
         ws["bn_ws"] = torch.zeros(lib.icamd_bn_workspace_bytes(2048), dtype=torch.uint8, device=dev)
         ws["wgrad_ws"] = torch.empty(max_wg, dtype=torch.uint8, device=dev)
@@ -607,41 +595,76 @@ class ResNet(PicklableModel):
     def _gf(self, p):  # fp32 grad pointer
         return self.grad_arena.data_ptr() + 4 * p.offset
 
+    def _stats(self, bn):
+        """(mean, invstd, scale, shift) pointers of a BatchNorm's saved batch statistics."""
+        st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
+        c = bn.c
+        return st, st + 4 * c, st + 8 * c, st + 12 * c
+
+    # The stem / grouped / dense dispatch on a convolution, once per kind of launch.  `d` is conv.desc(...) of the input shape.
+    def _conv_fwd(self, conv, d, x, w, y, s, stats=None, shift=None, residual=None, relu=0):
+        """y = conv(x) with filters `w`.  Training form (shift None): the raw output, BatchNorm statistic rows to `stats`.  Folded
+        eval form: + shift (+ residual) (+ ReLU) in the epilogue."""
+        lib = self.lib
+        if conv is self.stem_conv:
+            rc = lib.icamd_stem7x7s2_fwd(x, w, y, shift, stats, relu, d.N, d.IH, d.IW, conv.cout_p, s)
+        elif conv.groups > 1 and shift is None:
+            rc = lib.icamd_gconv3x3_fwd(ctypes.byref(d), conv.groups, x, w, y, stats, s)
+        elif conv.groups > 1:
+            assert residual is None
+            rc = lib.icamd_gconv3x3_fwd_act(ctypes.byref(d), conv.groups, x, w, y, shift, relu, s)
+        elif shift is None:
+            rc = lib.icamd_conv2d_fwd(ctypes.byref(d), x, w, y, None, None, stats, s)
+        else:
+            rc = lib.icamd_conv2d_fwd_act(ctypes.byref(d), x, w, y, shift, residual, relu, s)
+        hip.check(rc, conv.name)
+
+    def _wgrad_workspace_bytes(self, conv, d):
+        lib = self.lib
+        if conv is self.stem_conv:
+            return lib.icamd_stem7x7s2_wgrad_workspace_bytes(d.N, d.IH, d.IW, conv.cout_p)
+        if conv.groups > 1:
+            return lib.icamd_gconv3x3_wgrad_workspace_bytes(ctypes.byref(d), conv.groups)
+        return lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
+
+    def _wgrad(self, conv, d, x, dy, acc, wsp, wsb, s):
+        lib = self.lib
+        if conv is self.stem_conv:
+            rc = lib.icamd_stem7x7s2_wgrad(x, dy, self._gf(conv.w), acc, wsp, wsb, d.N, d.IH, d.IW, conv.cout_p, s)
+        elif conv.groups > 1:
+            rc = lib.icamd_gconv3x3_wgrad(ctypes.byref(d), conv.groups, x, dy, self._gf(conv.w), acc, wsp, wsb, s)
+        else:
+            rc = lib.icamd_conv2d_wgrad(ctypes.byref(d), x, dy, self._gf(conv.w), acc, wsp, wsb, s)
+        hip.check(rc, conv.name + " wgrad")
+
+    def _dgrad(self, conv, d, dy, dx, addend, addend_bits, s):
+        """dx = data gradient of conv (+ addend, where the 1-bit mask `addend_bits` is set when given)."""
+        if conv.groups > 1:
+            assert addend is None
+            rc = self.lib.icamd_gconv3x3_dgrad(ctypes.byref(d), conv.groups, dy, self._w(conv), dx, s)
+        else:
+            rc = self.lib.icamd_conv2d_dgrad(ctypes.byref(d), dy, self._wt(conv), dx, addend, addend_bits, s)
+        hip.check(rc, conv.name + " dgrad")
+
     def _conv_bn_fwd(self, ws, conv, bn, x, N, IH, IW, y, out, residual, relu, s, maskbits=None, res_bn=None, conv_launch=None):
         """y = conv(x); out = act(bn(y) (+ residual)). Training: batch statistics from the conv epilogue.
         conv_launch(stats_ptr): replaces the convolution launch (round 5: the fused "previous block's apply + this conv1" kernel)."""
         lib = self.lib
         d = conv.desc(N, IH, IW)
-        st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
         c = bn.c
-        mean, invstd, scale, shift = st, st + 4 * c, st + 8 * c, st + 12 * c
-        stem = conv is self.stem_conv
-
-        def conv_fwd(stats_ptr):
-            if conv_launch is not None:
-                conv_launch(stats_ptr)
-                return
-            if stem:
-                hip.check(lib.icamd_stem7x7s2_fwd(x, self._w(conv), y.data_ptr(), None, stats_ptr, 0, N, IH, IW, conv.cout_p, s),
-                          conv.name)
-            elif conv.groups > 1:
-                hip.check(lib.icamd_gconv3x3_fwd(ctypes.byref(d), conv.groups, x, self._w(conv), y.data_ptr(), stats_ptr, s),
-                          conv.name)
-            else:
-                hip.check(lib.icamd_conv2d_fwd(ctypes.byref(d), x, self._w(conv), y.data_ptr(), None, None, stats_ptr, s),
-                          conv.name)
-
+        stats = ws["stats"].data_ptr() if self.training else None
+        if conv_launch is not None:
+            conv_launch(stats)
+        else:
+            self._conv_fwd(conv, d, x, self._w(conv), y.data_ptr(), s, stats=stats)
+        rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
         if self.training:
-            stats = ws["stats"].data_ptr()
-            conv_fwd(stats)
+            mean, invstd, scale, shift = self._stats(bn)
             rows = lib.icamd_conv2d_stats_rows(ctypes.byref(d))
-            rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
             hip.check(lib.icamd_bn_train_finalize(stats, rows, c, float(N * d.OH * d.OW), self._pf(bn.weight),
                                                   self._pf(bn.bias), rm, rm + 4 * c, BN_MOMENTUM, BN_EPS, mean, invstd,
                                                   scale, shift, ws["bn_ws"].data_ptr(), s), bn.name)
         else:
-            conv_fwd(None)
-            rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
             scale = ws["scale_shift_eval"].data_ptr()
             shift = scale + 4 * 2048
             hip.check(lib.icamd_bn_eval_coeffs(c, self._pf(bn.weight), self._pf(bn.bias), rm, rm + 4 * c, BN_EPS, scale,
@@ -759,417 +782,311 @@ class ResNet(PicklableModel):
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False):
         """Backward from ws['dlogits'] (bf16 [N, ncls_p]); fills the flat fp32 gradient arena.
-        Gradients become final in reverse layer order; `grad_ready_hook(lo, hi)` is called as ranges complete.
+        Gradients become final in reverse layer order; `grad_ready_hook(lo, hi, events)` is called as ranges complete (hi None:
+        to the end of the range of the previous call; events: what a consumer on another stream waits for besides the main one).
 
-        Weight gradients run on a second HIP stream (ICAMD_WGRAD_STREAM=0 keeps one stream): a layer's wgrad only needs
-        that layer's output gradient and its saved input, nothing downstream needs its result before the optimizer, and it
-        is MFMA/latency-bound while the BatchNorm-backward passes the main stream runs next are HBM-bound -- side by side
+        Weight gradients run on a second HIP stream (streams.SideLane; ICAMD_WGRAD_STREAM=0 keeps one stream): a layer's wgrad
+        only needs that layer's output gradient and its saved input, nothing downstream needs its result before the optimizer,
+        and it is MFMA/latency-bound while the BatchNorm-backward passes the main stream runs next are HBM-bound -- side by side
         they fill both.  The output-gradient buffers rotate through a small pool so the main stream can run ahead; an
         event per buffer keeps it from overwriting one a pending wgrad still reads."""
         if _FUSED_BNBWD:
             return self._backward_packed_fused(ws, accumulate)
-        lib = self.lib
-        main = torch.cuda.current_stream()
-        s = main.cuda_stream
-        N = ws["N"]
-        acc = int(bool(accumulate))
-        wsp, wsb = ws["wgrad_ws"].data_ptr(), ws["wgrad_ws_bytes"]
-        bws, bwb = ws["bnb_ws"].data_ptr(), ws["bnb_ws_bytes"]
+        run = self._backward_begin(ws, accumulate, _WGRAD_STREAM and self.wgrad_side_stream)
         bufs = self._grad_buffers(ws)
-        D0, D1, T, DA = (b.data_ptr() for b in bufs[:4])
-        ypool = [b.data_ptr() for b in bufs[4:]]
-        hook = self.grad_ready_hook
-        side = self._wgrad_stream() if (_WGRAD_STREAM and self.wgrad_side_stream) else None
-        ws_side = side.cuda_stream if side is not None else s
-        pending = [None] * len(ypool)     # per pool buffer: event of the last side-stream wgrad reading it
-        state = {"next": 0, "last": None}
-
-        def next_y():
-            k = state["next"]
-            state["next"] = (k + 1) % len(ypool)
-            if pending[k] is not None:
-                main.wait_event(pending[k])
-                pending[k] = None
-            return k
-
-        def wgrad(conv, x_ptr, dy_ptr, n, ih, iw, ybuf=None):
-            d = conv.desc(n, ih, iw)
-            if side is not None:
-                ready = torch.cuda.Event()
-                ready.record(main)
-                side.wait_event(ready)
-            if conv is self.stem_conv:
-                hip.check(lib.icamd_stem7x7s2_wgrad(x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, n, ih, iw, conv.cout_p, ws_side),
-                          conv.name + " wgrad")
-            elif conv.groups > 1:
-                hip.check(lib.icamd_gconv3x3_wgrad(ctypes.byref(d), conv.groups, x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb,
-                                                   ws_side), conv.name + " wgrad")
-            else:
-                hip.check(lib.icamd_conv2d_wgrad(ctypes.byref(d), x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, ws_side),
-                          conv.name + " wgrad")
-            if side is not None:
-                done = torch.cuda.Event()
-                done.record(side)
-                state["last"] = done
-                if ybuf is not None:
-                    pending[ybuf] = done
-
-        def join_side():
-            if state["last"] is not None:
-                main.wait_event(state["last"])
-                state["last"] = None
-
-        def side_events():
-            """Events a gradient consumer on ANOTHER stream (the all-reduce) must wait for besides the main stream: the main
-            stream itself keeps running ahead of the weight gradients."""
-            return () if state["last"] is None else (state["last"],)
-
-        def dgrad(conv, dy_ptr, dx_ptr, addend, n, ih, iw, addend_bits=None):
-            d = conv.desc(n, ih, iw)
-            if conv.groups > 1:
-                assert addend is None
-                hip.check(lib.icamd_gconv3x3_dgrad(ctypes.byref(d), conv.groups, dy_ptr, self._w(conv), dx_ptr, s),
-                          conv.name + " dgrad")
-                return
-            hip.check(lib.icamd_conv2d_dgrad(ctypes.byref(d), dy_ptr, self._wt(conv), dx_ptr, addend, addend_bits, s),
-                      conv.name + " dgrad")
-
-        def bn_bwd(bn, dout_ptr, act_ptr, y, dy_ptr, gout_ptr, relu, maskbits=None):
-            st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-            c = bn.c
-            rows = y.numel() // c
-            hip.check(lib.icamd_bn_bwd(dout_ptr, act_ptr, y.data_ptr(), st, st + 4 * c, st + 8 * c, st + 12 * c,
-                                       self._gf(bn.weight), self._gf(bn.bias), dy_ptr, gout_ptr, maskbits, rows, c, int(relu),
-                                       acc, bws, bwb, s), bn.name + " bwd")
-
-        # classifier
-        dl = ws["dlogits"].data_ptr()
-        wgrad(self.fc, ws["pooled"].data_ptr(), dl, N, 1, 1)
-        hip.check(lib.icamd_colsum(dl, N, self.ncls_p, self.ncls_p, self._gf(self.fc.b), acc, s), "fc bias grad")
-        dgrad(self.fc, dl, ws["dpooled"].data_ptr(), None, N, 1, 1)
-        if hook:
-            hook(self.fc.w.offset, self.n_params, side_events())
-        fh, fw = ws["final_hw"]
-        dout, other = D0, D1
-        hip.check(lib.icamd_avgpool_bwd(ws["dpooled"].data_ptr(), dout, N, fh * fw, self.feat_dim, s), "avgpool bwd")
-
-        # Residual data gradients that ALSO do pass 1 of the previous block's last BatchNorm backward (icamd_conv2d_dgrad_bnred):
-        # `fused_rows` > 0 says `dout` already holds g = masked output gradient of the block about to be processed and
-        # ws["bnb_part"] its partial sums (sum g, sum g*y), so that block starts with the apply pass only
+        dout, other, run.T, run.DA = (b.data_ptr() for b in bufs[:4])
+        run.ypool = itertools.cycle([b.data_ptr() for b in bufs[4:]])
+        self._bwd_classifier(run, dout)
+        # `fused_rows` > 0: the residual data gradient of the block just done also did pass 1 of the next block's last BatchNorm
+        # backward (icamd_conv2d_dgrad_bnred), so `dout` already holds g = that block's masked output gradient and
+        # ws["bnb_part"] its partial sums (sum g, sum g*y): the block starts with the apply pass only
         fused_rows = 0
         for bi in range(len(self.blocks) - 1, -1, -1):
-            blk, b = self.blocks[bi], ws["blocks"][bi]
-            convs, bns = blk["convs"], blk["bns"]
-            h, w = b["in_hw"]
-            xin = b["in"]
-            nconv = len(convs)
-            # spatial sizes seen by each conv's input
-            hw_in = [(h, w)]
-            for conv in convs[:-1]:
-                d = conv.desc(N, *hw_in[-1])
-                hw_in.append((d.OH, d.OW))
-            # last BN (+ residual + ReLU): g = dout * [block output > 0] via the 1-bit mask the forward stored; g itself is
-            # never written: the shortcut consumers below re-apply the same bits to `dout`
-            mask = b["mask"].data_ptr()
-            yk = next_y()
-            y2 = None
-            fused_conv3 = False
-            shortcut_done = False
-            # may this block's conv1 data gradient hand the PREVIOUS block g = its masked output gradient plus the (sum g, sum g*y)
-            # rows of its last BatchNorm (icamd_conv2d_dgrad_bnred)?  Identity blocks always take them; a projection block only
-            # through the fused conv3 + bn3 backward (its other path, icamd_bn_bwd_dual, wants the unmasked gradient and no sums)
-            prev_takes_g = False
-            if bi > 0 and self.block == "bottleneck":
-                pblk = self.blocks[bi - 1]
-                if "down_conv" not in pblk:
-                    prev_takes_g = True
-                else:
-                    dp3 = pblk["convs"][-1].desc(N, h, w)
-                    prev_takes_g = bool(lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(dp3)))
-            d3 = convs[-1].desc(N, *hw_in[-1])
-            fuse3 = (self.block == "bottleneck" and fused_rows > 0
-                     and bool(lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d3))))
+            dy, dy2, shortcut_done = self._bwd_last_bn(run, bi, dout, fused_rows)
+            dy = self._bwd_inner_convs(run, bi, dy)
+            fused_rows = self._bwd_conv1_shortcut(run, bi, dy, dy2, shortcut_done, dout, other)
+            if run.hook:
+                run.hook(self.blocks[bi]["convs"][0].w.offset, None, run.lane.events())
+            dout, other = other, dout
+        self._bwd_stem(run, dout, self._next_y(run), _FUSED_POOL_BWD)
+        if run.hook:
+            run.hook(0, None, run.lane.events())
+        run.lane.join()
 
-            def fused_conv_bn(conv, bn, dsc, partials, nrows, y_t, x_ptr, dx_ptr, bn_ws, bn_ws_bytes):
-                """BatchNorm-backward apply + data gradient + weight gradient of `conv` -> `bn` in one pass over g (= dout, already
-                masked) and y (round 5, icamd_conv1x1_bn_bwd_fused); main stream, its own slab workspace (the side stream's weight
-                gradients own ws["wgrad_ws"])."""
-                st_ = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-                c_ = bn.c
-                need = lib.icamd_conv1x1_bn_bwd_fused_workspace_bytes(ctypes.byref(dsc))
-                fws = ws.get("fused_ws")
-                if fws is None or fws.numel() < need:
-                    fws = ws["fused_ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
-                hip.check(lib.icamd_conv1x1_bn_bwd_fused(ctypes.byref(dsc), partials, nrows, dout, y_t.data_ptr(), st_, st_ + 4 * c_,
-                                                         st_ + 8 * c_, self._gf(bn.weight), self._gf(bn.bias), x_ptr, self._wt(conv),
-                                                         dx_ptr, self._gf(conv.w), acc, bn_ws, bn_ws_bytes, fws.data_ptr(),
-                                                         fws.numel(), s), bn.name + " + " + conv.name + " bwd (fused)")
+    def _backward_begin(self, ws, accumulate, side):
+        """What the steps of one backward pass share; `side`: weight gradients on the side lane."""
+        lane = side_lane(self, "ICAMD_WGRAD_STREAM", True)
+        lane.begin(side)
+        return SimpleNamespace(ws=ws, N=ws["N"], acc=int(bool(accumulate)), lane=lane, s=lane.main.cuda_stream,
+                               hook=self.grad_ready_hook, wsp=ws["wgrad_ws"].data_ptr(), wsb=ws["wgrad_ws_bytes"],
+                               bws=ws["bnb_ws"].data_ptr(), bwb=ws["bnb_ws_bytes"])
 
-            if "down_conv" in blk and fuse3:
-                # projection block whose successor left g and the (sum g, sum g*y3) rows: conv3 + bn3 fused; the shortcut's BatchNorm
-                # takes the same g -- its convolution + BatchNorm fused as well where it is a 1x1 / stride-1 layer of a routed
-                # shape (layer1.0), else its BatchNorm backward alone (no mask: g is masked already)
-                fused_conv_bn(convs[-1], bns[-1], d3, ws["bnb_part"].data_ptr(), fused_rows, b["y"][-1],
-                              b["a"][nconv - 2].data_ptr(), DA, ws["bna_ws"].data_ptr(), ws["bna_ws_bytes"])
-                fused_conv3 = True
+    def _next_y(self, run):
+        """The next output-gradient buffer of the pool, once no pending weight gradient reads it any more."""
+        y = next(run.ypool)
+        run.lane.before_write(y)
+        return y
+
+    def _side_wgrad(self, run, conv, d, x, dy):
+        run.lane.launch(lambda st: self._wgrad(conv, d, x, dy, run.acc, run.wsp, run.wsb, st), reads=(dy,))
+
+    def _bn_bwd(self, run, bn, dout, act, y, dy, gout, relu, maskbits=None):
+        mean, invstd, scale, shift = self._stats(bn)
+        c = bn.c
+        hip.check(self.lib.icamd_bn_bwd(dout, act, y.data_ptr(), mean, invstd, scale, shift, self._gf(bn.weight),
+                                        self._gf(bn.bias), dy, gout, maskbits, y.numel() // c, c, int(relu), run.acc, run.bws,
+                                        run.bwb, run.s), bn.name + " bwd")
+
+    def _fused_conv_bn(self, run, conv, bn, d, partials, nrows, g, y, x, dx, bn_ws, bn_ws_bytes):
+        """BatchNorm-backward apply + data gradient + weight gradient of `conv` -> `bn` in one pass over g (already masked) and y
+        (round 5, icamd_conv1x1_bn_bwd_fused); main stream, its own slab workspace (the side stream's weight gradients own
+        ws["wgrad_ws"])."""
+        lib, ws = self.lib, run.ws
+        mean, invstd, scale, _ = self._stats(bn)
+        need = lib.icamd_conv1x1_bn_bwd_fused_workspace_bytes(ctypes.byref(d))
+        fws = ws.get("fused_ws")
+        if fws is None or fws.numel() < need:
+            fws = ws["fused_ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        hip.check(lib.icamd_conv1x1_bn_bwd_fused(ctypes.byref(d), partials, nrows, g, y.data_ptr(), mean, invstd, scale,
+                                                 self._gf(bn.weight), self._gf(bn.bias), x, self._wt(conv), dx, self._gf(conv.w),
+                                                 run.acc, bn_ws, bn_ws_bytes, fws.data_ptr(), fws.numel(), run.s),
+                  bn.name + " + " + conv.name + " bwd (fused)")
+
+    def _bwd_classifier(self, run, dout):
+        lib, ws, N, s = self.lib, run.ws, run.N, run.s
+        dl = ws["dlogits"].data_ptr()
+        dfc = self.fc.desc(N, 1, 1)
+        self._side_wgrad(run, self.fc, dfc, ws["pooled"].data_ptr(), dl)
+        hip.check(lib.icamd_colsum(dl, N, self.ncls_p, self.ncls_p, self._gf(self.fc.b), run.acc, s), "fc bias grad")
+        self._dgrad(self.fc, dfc, dl, ws["dpooled"].data_ptr(), None, None, s)
+        if run.hook:
+            run.hook(self.fc.w.offset, self.n_params, run.lane.events())
+        fh, fw = ws["final_hw"]
+        hip.check(lib.icamd_avgpool_bwd(ws["dpooled"].data_ptr(), dout, N, fh * fw, self.feat_dim, s), "avgpool bwd")
+
+    def _bwd_last_bn(self, run, bi, dout, fused_rows):
+        """Backward of the block's last BatchNorm (+ residual + ReLU): g = dout * [block output > 0] via the 1-bit mask the forward
+        stored; g itself is never written: the shortcut consumers re-apply the same bits to `dout`.
+        Returns (dy, dy2, shortcut_done).  dy: gradient of the last convolution's output, or None where that convolution's
+        backward came out of the same launch (its input's gradient is in run.DA, its filter gradient in the arena).  dy2: the same
+        for the shortcut convolution where its BatchNorm was done here.  shortcut_done: the shortcut's filter gradient is done and
+        run.T holds its full-size data gradient."""
+        lib, ws, N = self.lib, run.ws, run.N
+        blk, b = self.blocks[bi], ws["blocks"][bi]
+        conv3, bn3, y3 = blk["convs"][-1], blk["bns"][-1], b["y"][-1]
+        down = "down_conv" in blk
+        mask = b["mask"].data_ptr()
+        dy = self._next_y(run)
+        dy2, shortcut_done = None, False
+        d3 = conv3.desc(N, *b["hw"][-1])
+        if (self.block == "bottleneck" and fused_rows > 0 and lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d3))):
+            # conv3 + bn3 backward in one pass over g and y3: BatchNorm finalize from the partial sums, dy3 only in LDS,
+            # d(a2) -> DA and the filter gradient out of the same launch
+            self._fused_conv_bn(run, conv3, bn3, d3, ws["bnb_part"].data_ptr(), fused_rows, dout, y3, b["a"][-2].data_ptr(), run.DA,
+                                ws["bna_ws"].data_ptr(), ws["bna_ws_bytes"])
+            dy = None
+            if down:
+                # the shortcut's BatchNorm takes the same g -- its convolution + BatchNorm fused as well where it is a 1x1 /
+                # stride-1 layer of a routed shape (layer1.0), else its BatchNorm backward alone (no mask: g is masked already)
                 dc = blk["down_conv"]
-                ddc = dc.desc(N, h, w)
+                ddc = dc.desc(N, *b["in_hw"])
                 if dc.stride == 1 and lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(ddc)):
-                    fused_conv_bn(dc, blk["down_bn"], ddc, None, 0, b["yd"], xin.data_ptr(), T, bws, bwb)
+                    self._fused_conv_bn(run, dc, blk["down_bn"], ddc, None, 0, dout, b["yd"], b["in"].data_ptr(), run.T, run.bws,
+                                        run.bwb)
                     shortcut_done = True
                 else:
-                    y2 = next_y()
-                    bn_bwd(blk["down_bn"], dout, None, b["yd"], ypool[y2], None, False)
-            elif "down_conv" in blk and _DUAL_BNBWD:
-                # the block's last BatchNorm and its shortcut's BatchNorm take the same masked gradient: one reduce and one
-                # apply pass for both (dout and the mask bits are read twice instead of four times)
-                y2 = next_y()
-                bnA, bnB = bns[-1], blk["down_bn"]
-                stA = self.stat_arena.data_ptr() + 4 * bnA.stat_offset
-                stB = self.stat_arena.data_ptr() + 4 * bnB.stat_offset
-                c = bnA.c
-                hip.check(lib.icamd_bn_bwd_dual(dout, mask, b["y"][-1].data_ptr(), stA, stA + 4 * c, stA + 8 * c,
-                                                self._gf(bnA.weight), self._gf(bnA.bias), ypool[yk], b["yd"].data_ptr(), stB,
-                                                stB + 4 * c, stB + 8 * c, self._gf(bnB.weight), self._gf(bnB.bias), ypool[y2],
-                                                b["y"][-1].numel() // c, c, acc, bws, ws["bnb_ws2"].data_ptr(), bwb, s),
-                          bnA.name + " + shortcut bwd")
-            elif fused_rows:
-                bnl = bns[-1]
-                stl = self.stat_arena.data_ptr() + 4 * bnl.stat_offset
-                cl = bnl.c
-                if fuse3:
-                    # conv3 + bn3 backward in one pass over g and y3: BatchNorm finalize from the partial sums, dy3 only in LDS,
-                    # d(a2) -> DA and the filter gradient out of the same launch
-                    fused_conv_bn(convs[-1], bnl, d3, ws["bnb_part"].data_ptr(), fused_rows, b["y"][-1],
-                                  b["a"][nconv - 2].data_ptr(), DA, ws["bna_ws"].data_ptr(), ws["bna_ws_bytes"])
-                    fused_conv3 = True
-                else:
-                    hip.check(lib.icamd_bn_bwd_from_gy_partials(ws["bnb_part"].data_ptr(), fused_rows, dout, b["y"][-1].data_ptr(),
-                                                                stl, stl + 4 * cl, stl + 8 * cl, self._gf(bnl.weight),
-                                                                self._gf(bnl.bias), ypool[yk], b["y"][-1].numel() // cl, cl, acc,
-                                                                ws["bna_ws"].data_ptr(), ws["bna_ws_bytes"], s),
-                              bnl.name + " bwd (apply, sums from the data gradient)")
-            else:
-                bn_bwd(bns[-1], dout, None, b["y"][-1], ypool[yk], None, True, mask)
-            fused_rows = 0
-            for i in range(nconv - 1, 0, -1):
-                x_i = b["a"][i - 1]
-                if fused_conv3 and i == nconv - 1:
-                    # conv3's data and weight gradients came out of the fused launch (DA, grad arena)
-                    yk = next_y()
-                    bn_bwd(bns[i - 1], DA, None, b["y"][i - 1], ypool[yk], None, True)
-                    continue
+                    dy2 = self._next_y(run)
+                    self._bn_bwd(run, blk["down_bn"], dout, None, b["yd"], dy2, None, False)
+        elif down and _DUAL_BNBWD:
+            # the block's last BatchNorm and its shortcut's BatchNorm take the same masked gradient: one reduce and one
+            # apply pass for both (dout and the mask bits are read twice instead of four times)
+            dy2 = self._next_y(run)
+            bnB = blk["down_bn"]
+            meanA, invstdA, scaleA, _ = self._stats(bn3)
+            meanB, invstdB, scaleB, _ = self._stats(bnB)
+            c = bn3.c
+            hip.check(lib.icamd_bn_bwd_dual(dout, mask, y3.data_ptr(), meanA, invstdA, scaleA, self._gf(bn3.weight),
+                                            self._gf(bn3.bias), dy, b["yd"].data_ptr(), meanB, invstdB, scaleB,
+                                            self._gf(bnB.weight), self._gf(bnB.bias), dy2, y3.numel() // c, c, run.acc, run.bws,
+                                            ws["bnb_ws2"].data_ptr(), run.bwb, run.s), bn3.name + " + shortcut bwd")
+        elif fused_rows:
+            mean, invstd, scale, _ = self._stats(bn3)
+            c = bn3.c
+            hip.check(lib.icamd_bn_bwd_from_gy_partials(ws["bnb_part"].data_ptr(), fused_rows, dout, y3.data_ptr(), mean, invstd,
+                                                        scale, self._gf(bn3.weight), self._gf(bn3.bias), dy, y3.numel() // c, c,
+                                                        run.acc, ws["bna_ws"].data_ptr(), ws["bna_ws_bytes"], run.s),
+                      bn3.name + " bwd (apply, sums from the data gradient)")
+        else:
+            self._bn_bwd(run, bn3, dout, None, y3, dy, None, True, mask)
+        return dy, dy2, shortcut_done
+
+    def _bwd_inner_convs(self, run, bi, dy):
+        """Every convolution but the first, last to second, each followed by the backward of the BatchNorm + ReLU in front of it
+        (no residual in front of that ReLU: mask recomputed from y).  dy None: the last convolution is done, run.DA holds its
+        data gradient.  Returns the gradient of the first convolution's output."""
+        blk, b = self.blocks[bi], run.ws["blocks"][bi]
+        convs, bns = blk["convs"], blk["bns"]
+        for i in range(len(convs) - 1, 0, -1):
+            if dy is not None:
                 # wgrad first: measured, it overlaps best with the data-gradient kernel of the same layer (issued after it,
                 # i.e. beside the next BatchNorm backward whose 1024 workgroups fill every wave slot, the gain disappears)
-                wgrad(convs[i], x_i.data_ptr(), ypool[yk], N, *hw_in[i], ybuf=yk)
-                dgrad(convs[i], ypool[yk], DA, None, N, *hw_in[i])
-                # BN + ReLU with no residual in front of the ReLU: mask recomputed from y
-                yk = next_y()
-                bn_bwd(bns[i - 1], DA, None, b["y"][i - 1], ypool[yk], None, True)
-            wgrad(convs[0], xin.data_ptr(), ypool[yk], N, h, w, ybuf=yk)
-            if shortcut_done:
-                # the shortcut's filter gradient is done and T holds its (full-size) data gradient
-                dgrad(convs[0], ypool[yk], other, T, N, h, w)
-            elif "down_conv" in blk:
-                if y2 is None:
-                    y2 = next_y()
-                    bn_bwd(blk["down_bn"], dout, None, b["yd"], ypool[y2], None, True, mask)   # "relu" = the block's mask bits
-                dc = blk["down_conv"]
-                wgrad(dc, xin.data_ptr(), ypool[y2], N, h, w, ybuf=y2)
-                if _SUB2_SHORTCUT and dc.k == 1 and dc.stride == 2 and dc.pad == 0:
-                    # a 1x1 stride-2 shortcut sends gradient to the even pixels only: compute it on the [OH][OW] grid (a
-                    # plain pointwise data gradient) and let the main branch's data gradient add it there
-                    # (icamd_conv2d_dgrad_sub2); the 3/4 zeros of the full-size tensor are never written or read
-                    dd = dc.desc(N, h, w)
-                    key = ("sub2", N, dd.OH, dd.OW)
-                    d1 = dc.descs.get(key)
-                    if d1 is None:
-                        d1 = dc.descs[key] = hip.conv_desc(N, dd.OH, dd.OW, dc.cin_p, dc.cout_p, 1, 1, 1, 0)
-                    hip.check(lib.icamd_conv2d_dgrad(ctypes.byref(d1), ypool[y2], self._wt(dc), T, None, None, s),
-                              dc.name + " dgrad (even grid)")
-                    d0 = convs[0].desc(N, h, w)
-                    if (prev_takes_g and self.block == "bottleneck"
-                            and lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d0))):
-                        pb = ws["blocks"][bi - 1]   # (see the identity-shortcut case below)
-                        hip.check(lib.icamd_conv2d_dgrad_bnred(ctypes.byref(d0), ypool[yk], self._wt(convs[0]), other, T, None, 1,
-                                                               pb["y"][-1].data_ptr(), pb["mask"].data_ptr(),
-                                                               ws["bnb_part"].data_ptr(), s),
-                                  convs[0].name + " dgrad + shortcut + bn reduce")
-                        fused_rows = lib.icamd_conv2d_dgrad_stats_rows(ctypes.byref(d0))
-                    else:
-                        hip.check(lib.icamd_conv2d_dgrad_sub2(ctypes.byref(d0), ypool[yk], self._wt(convs[0]), other, T, s),
-                                  convs[0].name + " dgrad + shortcut")
-                else:
-                    dgrad(dc, ypool[y2], T, None, N, h, w)
-                    dgrad(convs[0], ypool[yk], other, T, N, h, w)
-            else:
-                d0 = convs[0].desc(N, h, w)
-                if (prev_takes_g and self.block == "bottleneck"
-                        and lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d0))):
-                    # `other` becomes g of the previous block (its ReLU mask applied, which every consumer of d(block output)
-                    # applies anyway) and the sums its last BatchNorm's backward needs come out of the same launch
-                    pb = ws["blocks"][bi - 1]
-                    hip.check(lib.icamd_conv2d_dgrad_bnred(ctypes.byref(d0), ypool[yk], self._wt(convs[0]), other, dout, mask, 0,
-                                                           pb["y"][-1].data_ptr(), pb["mask"].data_ptr(),
-                                                           ws["bnb_part"].data_ptr(), s), convs[0].name + " dgrad + bn reduce")
-                    fused_rows = lib.icamd_conv2d_dgrad_stats_rows(ctypes.byref(d0))
-                else:
-                    dgrad(convs[0], ypool[yk], other, dout, N, h, w, mask)
-            if hook:
-                hook(convs[0].w.offset, None, side_events())
-            dout, other = other, dout
+                d = convs[i].desc(run.N, *b["hw"][i])
+                self._side_wgrad(run, convs[i], d, b["a"][i - 1].data_ptr(), dy)
+                self._dgrad(convs[i], d, dy, run.DA, None, None, run.s)
+            dy = self._next_y(run)
+            self._bn_bwd(run, bns[i - 1], run.DA, None, b["y"][i - 1], dy, None, True)
+        return dy
 
-        # stem: maxpool -> BN+ReLU -> conv (no data gradient for the image)
-        d0 = self.stem_conv.desc(N, ws["H"], ws["Ws"])
-        yk = next_y()
-        if _FUSED_POOL_BWD:
-            # max-pool backward folded into both BatchNorm-backward passes: the 112x112 gradient is never materialised
-            bn0 = self.stem_bn
-            st = self.stat_arena.data_ptr() + 4 * bn0.stat_offset
-            c = bn0.c
-            hip.check(lib.icamd_bn_bwd_maxpool3x3s2(dout, ws["p0_idx"].data_ptr(), ws["y0"].data_ptr(), st, st + 4 * c,
-                                                    st + 8 * c, st + 12 * c, self._gf(bn0.weight), self._gf(bn0.bias),
-                                                    ypool[yk], N, d0.OH, d0.OW, c, acc, bws, bwb, s), "stem maxpool + bn bwd")
+    def _prev_takes_g(self, N, bi, h, w):
+        """May the conv1 data gradient of block bi (input h x w) hand the PREVIOUS block g = its masked output gradient plus the
+        (sum g, sum g*y) rows of its last BatchNorm (icamd_conv2d_dgrad_bnred)?  Identity blocks always take them; a projection
+        block only through the fused conv3 + bn3 backward (its other path, icamd_bn_bwd_dual, wants the unmasked gradient and no
+        sums)."""
+        if bi == 0 or self.block != "bottleneck":
+            return False
+        pblk = self.blocks[bi - 1]
+        if "down_conv" not in pblk:
+            return True
+        dp3 = pblk["convs"][-1].desc(N, h, w)
+        return bool(self.lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(dp3)))
+
+    def _bwd_conv1_shortcut(self, run, bi, dy, dy2, shortcut_done, dout, other):
+        """The block's first convolution and its shortcut: `other` = gradient of the block input.  Returns fused_rows for the
+        previous block: > 0 when `other` is already its g and ws["bnb_part"] holds the sums of its last BatchNorm."""
+        lib, ws, N, s = self.lib, run.ws, run.N, run.s
+        blk, b = self.blocks[bi], ws["blocks"][bi]
+        conv1 = blk["convs"][0]
+        h, w = b["in_hw"]
+        xin = b["in"].data_ptr()
+        d1 = conv1.desc(N, h, w)
+        self._side_wgrad(run, conv1, d1, xin, dy)
+        if shortcut_done:
+            self._dgrad(conv1, d1, dy, other, run.T, None, s)
+            return 0
+        if "down_conv" not in blk:
+            addend, bits, on_even_grid = dout, b["mask"].data_ptr(), 0
         else:
-            hip.check(lib.icamd_maxpool3x3s2_bwd(dout, ws["p0_idx"].data_ptr(), DA, N, d0.OH, d0.OW, 64, s), "maxpool bwd")
-            bn_bwd(self.stem_bn, DA, None, ws["y0"], ypool[yk], None, True)
-        wgrad(self.stem_conv, ws["x8"].data_ptr(), ypool[yk], N, ws["H"], ws["Ws"], ybuf=yk)
-        for k in range(len(pending)):     # every buffer is free again when the next backward starts
-            pending[k] = None
-        if hook:
-            hook(0, None, side_events())
-        join_side()
+            dc = blk["down_conv"]
+            ddc = dc.desc(N, h, w)
+            if dy2 is None:
+                dy2 = self._next_y(run)
+                # ("relu" = the block's mask bits)
+                self._bn_bwd(run, blk["down_bn"], dout, None, b["yd"], dy2, None, True, b["mask"].data_ptr())
+            self._side_wgrad(run, dc, ddc, xin, dy2)
+            if not (_SUB2_SHORTCUT and dc.k == 1 and dc.stride == 2 and dc.pad == 0):
+                self._dgrad(dc, ddc, dy2, run.T, None, None, s)
+                self._dgrad(conv1, d1, dy, other, run.T, None, s)
+                return 0
+            # a 1x1 stride-2 shortcut sends gradient to the even pixels only: compute it on the [OH][OW] grid (a
+            # plain pointwise data gradient) and let the main branch's data gradient add it there
+            # (icamd_conv2d_dgrad_sub2); the 3/4 zeros of the full-size tensor are never written or read
+            key = ("sub2", N, ddc.OH, ddc.OW)
+            deven = dc.descs.get(key)
+            if deven is None:
+                deven = dc.descs[key] = hip.conv_desc(N, ddc.OH, ddc.OW, dc.cin_p, dc.cout_p, 1, 1, 1, 0)
+            self._dgrad(dc, deven, dy2, run.T, None, None, s)
+            addend, bits, on_even_grid = run.T, None, 1
+        if self._prev_takes_g(N, bi, h, w) and lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d1)):
+            # `other` becomes g of the previous block (its ReLU mask applied, which every consumer of d(block output)
+            # applies anyway) and the sums its last BatchNorm's backward needs come out of the same launch
+            pb = ws["blocks"][bi - 1]
+            hip.check(lib.icamd_conv2d_dgrad_bnred(ctypes.byref(d1), dy, self._wt(conv1), other, addend, bits, on_even_grid,
+                                                   pb["y"][-1].data_ptr(), pb["mask"].data_ptr(), ws["bnb_part"].data_ptr(), s),
+                      conv1.name + " dgrad + bn reduce")
+            return lib.icamd_conv2d_dgrad_stats_rows(ctypes.byref(d1))
+        if on_even_grid:
+            hip.check(lib.icamd_conv2d_dgrad_sub2(ctypes.byref(d1), dy, self._wt(conv1), other, addend, s),
+                      conv1.name + " dgrad + shortcut")
+        else:
+            self._dgrad(conv1, d1, dy, other, addend, bits, s)
+        return 0
 
-    def _wgrad_stream(self):
-        if getattr(self, "_wg_stream", None) is None:
-            self._wg_stream = torch.cuda.Stream(device=self.device)
-        return self._wg_stream
+    def _bwd_stem(self, run, dout, dy, fused_pool):
+        """maxpool -> BN+ReLU -> conv (no data gradient for the image); dy: buffer for the stem convolution's output gradient."""
+        lib, ws, N, s = self.lib, run.ws, run.N, run.s
+        d0 = self.stem_conv.desc(N, ws["H"], ws["Ws"])
+        bn0 = self.stem_bn
+        if fused_pool:
+            # max-pool backward folded into both BatchNorm-backward passes: the 112x112 gradient is never materialised
+            mean, invstd, scale, shift = self._stats(bn0)
+            hip.check(lib.icamd_bn_bwd_maxpool3x3s2(dout, ws["p0_idx"].data_ptr(), ws["y0"].data_ptr(), mean, invstd, scale, shift,
+                                                    self._gf(bn0.weight), self._gf(bn0.bias), dy, N, d0.OH, d0.OW, bn0.c, run.acc,
+                                                    run.bws, run.bwb, s), "stem maxpool + bn bwd")
+        else:
+            hip.check(lib.icamd_maxpool3x3s2_bwd(dout, ws["p0_idx"].data_ptr(), run.DA, N, d0.OH, d0.OW, 64, s), "maxpool bwd")
+            self._bn_bwd(run, bn0, run.DA, None, ws["y0"], dy, None, True)
+        self._side_wgrad(run, self.stem_conv, d0, ws["x8"].data_ptr(), dy)
 
     def _backward_packed_fused(self, ws, accumulate=False):
         """Variant that fuses each BatchNorm backward's mask + reduction pass into the epilogue of the data-gradient
         kernel that produces its output gradient (icamd_conv2d_dgrad_bnbwd + icamd_bn_bwd_from_partials).  Fewer HBM
         bytes, but the un-pipelined epilogue makes it latency-bound on MI355X today (profiles/ r01 notes): opt-in with
-        ICAMD_FUSED_BNBWD=1."""
+        ICAMD_FUSED_BNBWD=1.  One stream: the side lane stays off."""
         lib = self.lib
-        s = hip.stream_ptr()
-        N = ws["N"]
-        acc = int(bool(accumulate))
-        wsp, wsb = ws["wgrad_ws"].data_ptr(), ws["wgrad_ws_bytes"]
-        bws, bwb = ws["bnb_ws"].data_ptr(), ws["bnb_ws_bytes"]
-        D0, D1, G, T, Y, Y2, DA = (b.data_ptr() for b in self._grad_buffers(ws)[:7])
-        hook = self.grad_ready_hook
+        run = self._backward_begin(ws, accumulate, False)
+        N, s, acc = run.N, run.s, run.acc
+        dout, other, G, T, Y, Y2, run.DA = (b.data_ptr() for b in self._grad_buffers(ws)[:7])
+        DA = run.DA
+        P, aws, pw_bytes = ws["bnb_part"].data_ptr(), ws["bna_ws"].data_ptr(), ws["bna_ws_bytes"]
 
-        def wgrad(conv, x_ptr, dy_ptr, n, ih, iw):
-            d = conv.desc(n, ih, iw)
-            if conv is self.stem_conv:
-                hip.check(lib.icamd_stem7x7s2_wgrad(x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, n, ih, iw, conv.cout_p, s),
-                          conv.name + " wgrad")
-                return
-            if conv.groups > 1:
-                hip.check(lib.icamd_gconv3x3_wgrad(ctypes.byref(d), conv.groups, x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, s),
-                          conv.name + " wgrad")
-                return
-            hip.check(lib.icamd_conv2d_wgrad(ctypes.byref(d), x_ptr, dy_ptr, self._gf(conv.w), acc, wsp, wsb, s),
-                      conv.name + " wgrad")
-
-        def dgrad(conv, dy_ptr, dx_ptr, addend, n, ih, iw):
-            d = conv.desc(n, ih, iw)
-            hip.check(lib.icamd_conv2d_dgrad(ctypes.byref(d), dy_ptr, self._wt(conv), dx_ptr, addend, None, s),
-                      conv.name + " dgrad")
-
-        def bn_bwd(bn, dout_ptr, act_ptr, y, dy_ptr, gout_ptr, relu):
-            st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-            c = bn.c
-            rows = y.numel() // c
-            hip.check(lib.icamd_bn_bwd(dout_ptr, act_ptr, y.data_ptr(), st, st + 4 * c, st + 8 * c, st + 12 * c,
-                                       self._gf(bn.weight), self._gf(bn.bias), dy_ptr, gout_ptr, None, rows, c, int(relu), acc,
-                                       bws, bwb, s), bn.name + " bwd")
-
-        P, pw_bytes = ws["bnb_part"].data_ptr(), ws["bna_ws_bytes"]
-        aws = ws["bna_ws"].data_ptr()
-
-        def dgrad_bnbwd(conv, dy_ptr, g_ptr, addend, n, ih, iw, bn, y, mask_src, relu):
-            """data gradient whose output is the output-gradient of `bn`(+ReLU): fused mask + pass-1 reductions."""
-            d = conv.desc(n, ih, iw)
-            st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-            c = bn.c
-            f = hip.BnBwdFuse(y.data_ptr(), mask_src, st, st + 4 * c, st + 8 * c, st + 12 * c, P, int(relu))
+        def dgrad_bnbwd(conv, d, dy_ptr, g_ptr, addend, bn, y, mask_src):
+            """data gradient whose output is the output-gradient of `bn` + ReLU: fused mask + pass-1 reductions."""
+            f = hip.BnBwdFuse(y.data_ptr(), mask_src, *self._stats(bn), P, 1)
             hip.check(lib.icamd_conv2d_dgrad_bnbwd(ctypes.byref(d), dy_ptr, self._wt(conv), g_ptr, addend, ctypes.byref(f), s),
                       conv.name + " dgrad+bnbwd")
             return lib.icamd_conv2d_dgrad_stats_rows(ctypes.byref(d))
 
         def bn_bwd_from_partials(bn, nrows, g_ptr, y, dy_ptr):
-            st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-            c = bn.c
-            hip.check(lib.icamd_bn_bwd_from_partials(P, nrows, g_ptr, y.data_ptr(), st, st + 4 * c, st + 8 * c,
-                                                     self._gf(bn.weight), self._gf(bn.bias), dy_ptr, y.numel() // c, c, acc,
+            mean, invstd, scale, _ = self._stats(bn)
+            hip.check(lib.icamd_bn_bwd_from_partials(P, nrows, g_ptr, y.data_ptr(), mean, invstd, scale,
+                                                     self._gf(bn.weight), self._gf(bn.bias), dy_ptr, y.numel() // bn.c, bn.c, acc,
                                                      aws, pw_bytes, s), bn.name + " bwd(apply)")
 
-        # classifier
-        dl = ws["dlogits"].data_ptr()
-        wgrad(self.fc, ws["pooled"].data_ptr(), dl, N, 1, 1)
-        hip.check(lib.icamd_colsum(dl, N, self.ncls_p, self.ncls_p, self._gf(self.fc.b), acc, s), "fc bias grad")
-        dgrad(self.fc, dl, ws["dpooled"].data_ptr(), None, N, 1, 1)
-        if hook:
-            hook(self.fc.w.offset, self.n_params)
-        fh, fw = ws["final_hw"]
-        dout, other = D0, D1
-        hip.check(lib.icamd_avgpool_bwd(ws["dpooled"].data_ptr(), dout, N, fh * fw, self.feat_dim, s), "avgpool bwd")
-
+        self._bwd_classifier(run, dout)
         nblk = len(self.blocks)
         pending_rows = 0   # partial rows left in P by the previous block's fused data gradient (for this block's last BN)
         for bi in range(nblk - 1, -1, -1):
             blk, b = self.blocks[bi], ws["blocks"][bi]
             convs, bns = blk["convs"], blk["bns"]
             h, w = b["in_hw"]
-            xin = b["in"]
-            nconv = len(convs)
-            hw_in = [(h, w)]
-            for conv in convs[:-1]:
-                d = conv.desc(N, *hw_in[-1])
-                hw_in.append((d.OH, d.OW))
+            xin = b["in"].data_ptr()
             if bi == nblk - 1:
                 # last block: its output gradient comes from the average pool: two-pass BN backward with the mask
-                bn_bwd(bns[-1], dout, b["a"][-1].data_ptr(), b["y"][-1], Y, G, True)
+                self._bn_bwd(run, bns[-1], dout, b["a"][-1].data_ptr(), b["y"][-1], Y, G, True)
                 g_ptr = G
             else:
                 # `dout` already holds g = masked output gradient and P its pass-1 sums (fused in the producer)
                 bn_bwd_from_partials(bns[-1], pending_rows, dout, b["y"][-1], Y)
                 g_ptr = dout
-            for i in range(nconv - 1, 0, -1):
-                x_i = b["a"][i - 1]
-                wgrad(convs[i], x_i.data_ptr(), Y, N, *hw_in[i])
+            for i in range(len(convs) - 1, 0, -1):
+                d = convs[i].desc(N, *b["hw"][i])
+                self._side_wgrad(run, convs[i], d, b["a"][i - 1].data_ptr(), Y)
                 if convs[i].groups > 1:
                     # the grouped data gradient has no fused BatchNorm reduction: plain data gradient, two-pass BatchNorm backward
-                    dg = convs[i].desc(N, *hw_in[i])
-                    hip.check(lib.icamd_gconv3x3_dgrad(ctypes.byref(dg), convs[i].groups, Y, self._w(convs[i]), DA, s),
-                              convs[i].name + " dgrad")
-                    bn_bwd(bns[i - 1], DA, None, b["y"][i - 1], Y, None, True)
+                    self._dgrad(convs[i], d, Y, DA, None, None, s)
+                    self._bn_bwd(run, bns[i - 1], DA, None, b["y"][i - 1], Y, None, True)
                     continue
-                nrows = dgrad_bnbwd(convs[i], Y, DA, None, N, *hw_in[i], bns[i - 1], b["y"][i - 1], None, True)
+                nrows = dgrad_bnbwd(convs[i], d, Y, DA, None, bns[i - 1], b["y"][i - 1], None)
                 bn_bwd_from_partials(bns[i - 1], nrows, DA, b["y"][i - 1], Y)
-            wgrad(convs[0], xin.data_ptr(), Y, N, h, w)
+            d1 = convs[0].desc(N, h, w)
+            self._side_wgrad(run, convs[0], d1, xin, Y)
             if "down_conv" in blk:
-                bn_bwd(blk["down_bn"], g_ptr, None, b["yd"], Y2, None, False)
-                wgrad(blk["down_conv"], xin.data_ptr(), Y2, N, h, w)
-                dgrad(blk["down_conv"], Y2, T, None, N, h, w)
+                dc = blk["down_conv"]
+                ddc = dc.desc(N, h, w)
+                self._bn_bwd(run, blk["down_bn"], g_ptr, None, b["yd"], Y2, None, False)
+                self._side_wgrad(run, dc, ddc, xin, Y2)
+                self._dgrad(dc, ddc, Y2, T, None, None, s)
                 addend = T
             else:
                 addend = g_ptr
             if bi > 0:
                 pb, pblk = ws["blocks"][bi - 1], self.blocks[bi - 1]
-                pending_rows = dgrad_bnbwd(convs[0], Y, other, addend, N, h, w, pblk["bns"][-1], pb["y"][-1],
-                                           xin.data_ptr(), True)
+                pending_rows = dgrad_bnbwd(convs[0], d1, Y, other, addend, pblk["bns"][-1], pb["y"][-1], xin)
             else:
-                dgrad(convs[0], Y, other, addend, N, h, w)
-            if hook:
-                hook(convs[0].w.offset, None)
+                self._dgrad(convs[0], d1, Y, other, addend, None, s)
+            if run.hook:
+                run.hook(convs[0].w.offset, None, ())
             dout, other = other, dout
-
-        # stem: maxpool -> BN+ReLU -> conv (no data gradient for the image)
-        d0 = self.stem_conv.desc(N, ws["H"], ws["Ws"])
-        hip.check(lib.icamd_maxpool3x3s2_bwd(dout, ws["p0_idx"].data_ptr(), DA, N, d0.OH, d0.OW, 64, s), "maxpool bwd")
-        bn_bwd(self.stem_bn, DA, None, ws["y0"], Y, None, True)
-        wgrad(self.stem_conv, ws["x8"].data_ptr(), Y, N, ws["H"], ws["Ws"])
-        if hook:
-            hook(0, None)
+        self._bwd_stem(run, dout, Y, False)
+        if run.hook:
+            run.hook(0, None, ())

@@ -5,6 +5,8 @@ needs its result, so it can run beside the main stream's data-gradient / normali
 MFMA- and latency-bound, the chain's LayerNorm / GELU / BatchNorm passes are HBM-bound, and together they fill both.
 `SideLane` keeps the bookkeeping: an event orders each side launch after the main-stream producer of its inputs, and a
 per-buffer event stops the main stream from overwriting a buffer a pending side launch still reads."""
+import os
+
 import torch
 
 
@@ -15,7 +17,9 @@ class SideLane:
         self._pending = {}    # data_ptr -> event of the last side launch reading that buffer
         self._last = None
 
-    def begin(self):
+    def begin(self, enabled=True):
+        """Start of one backward pass on the current stream; enabled=False keeps this pass on that stream alone."""
+        self.enabled = self.side is not None and bool(enabled)
         self.main = torch.cuda.current_stream()
         self._pending.clear()
         self._last = None
@@ -56,3 +60,13 @@ class SideLane:
             self.main.wait_event(self._last)
             self._last = None
         self._pending.clear()
+
+
+def side_lane(model, env, default):
+    """The model's SideLane, made on first use.  Environment variable `env` decides whether it has a second stream at all: a lane
+    that is on by default is turned off by "0", one that is off by default is turned on by "1"."""
+    lane = getattr(model, "_lane", None)
+    if lane is None:
+        v = os.environ.get(env)
+        lane = model._lane = SideLane(model.device, v != "0" if default else v == "1")
+    return lane

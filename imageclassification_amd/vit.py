@@ -12,7 +12,6 @@ residual add fused in the epilogue); LayerNorm / GELU / attention are the token 
 Same flat-arena design as nets.ResNet (fp32 parameters and gradients, bf16 shadow weights and their transposes).
 """
 import ctypes
-import os
 import math
 from collections import OrderedDict
 
@@ -20,6 +19,7 @@ import torch
 
 from . import hip
 from .checkpoint import PicklableModel
+from .streams import side_lane
 
 LN_EPS = 1e-6
 
@@ -400,9 +400,10 @@ class VisionTransformer(PicklableModel):
         csp, csb = ws["cs_ws"].data_ptr(), ws["cs_bytes"]
         scale = 64 ** -0.5
 
-        lane = self._side_lane()
-        lane.enabled = lane.side is not None and getattr(self, "wgrad_side_stream", True)
-        lane.begin()
+        # opt-in for ViT: its main-stream chain is itself MFMA-bound GEMMs + attention, so concurrent weight-gradient
+        # GEMMs only compete with it (measured 54.1 -> 54.7 ms/step at batch 256); the CNNs default to on
+        lane = side_lane(self, "ICAMD_WGRAD_STREAM_VIT", False)
+        lane.begin(getattr(self, "wgrad_side_stream", True))
 
         def lin_bwd(l, x, dy, rows, dx, gelu_z=None):
             """weight, bias gradients (+ data gradient into dx when given) of y = x W^T + b.  The weight gradient goes to
@@ -469,10 +470,3 @@ class VisionTransformer(PicklableModel):
         if hook:
             hook(0, None)
 
-    def _side_lane(self):
-        if getattr(self, "_lane", None) is None:
-            from .streams import SideLane
-            # opt-in for ViT: its main-stream chain is itself MFMA-bound GEMMs + attention, so concurrent weight-gradient
-            # GEMMs only compete with it (measured 54.1 -> 54.7 ms/step at batch 256); the CNNs default to on
-            self._lane = SideLane(self.device, os.environ.get("ICAMD_WGRAD_STREAM_VIT", "0") == "1")
-        return self._lane

@@ -696,12 +696,7 @@ def test_filter_transposes_of_the_models_own_tables(lib, models, model):
 
 
 def resnet_pairs(m):
-    pairs = [(m.stem_conv, m.stem_bn)]
-    for blk in m.blocks:
-        pairs += list(zip(blk["convs"], blk["bns"]))
-        if "down_conv" in blk:
-            pairs.append((blk["down_conv"], blk["down_bn"]))
-    return pairs
+    return m.conv_bn_pairs()
 
 
 def test_resnet50_batchnorm_fold(lib, models):
