@@ -108,6 +108,22 @@ int icamd_layerscale_bwd_launch(const bf16_t* dout, const bf16_t* z, const float
                                 float* part, long long rows, int C, long long rows_per_image, hipStream_t s);
 int icamd_filter_transpose_tiled_launch(const bf16_t* src_base, bf16_t* dst_base, const long long* descs, const int* jobs,
                                         int njobs, hipStream_t s);
+// squeeze-and-excitation tail (se_ops.hip)
+bool icamd_se_shape_ok(int N, int HW, int C, int rd);
+size_t icamd_se_squeeze_bytes(int N, int HW, int C);
+int icamd_se_squeeze_launch(const bf16_t* y, float* ysum, int N, int HW, int C, float* part, hipStream_t s);
+int icamd_se_excite_fwd_launch(const float* ysum, const float* scale, const float* shift, float inv_hw, const float* w1,
+                               const float* b1, const float* w2, const float* b2, float* s_out, float* h_out, float* e_out,
+                               int N, int C, int rd, hipStream_t s);
+int icamd_se_bn_apply_launch(const bf16_t* y, const float* scale, const float* shift, const float* gate, const bf16_t* residual,
+                             const float* res_scale, const float* res_shift, bf16_t* out, unsigned char* maskbits, int N, int HW,
+                             int C, int relu, hipStream_t s);
+size_t icamd_se_bn_bwd_bytes(int N, int HW, int C);
+int icamd_se_bn_bwd_launch(const bf16_t* dout, const unsigned char* maskbits, const bf16_t* y, const float* mean,
+                           const float* invstd, const float* gamma, const float* beta, const float* ysum, const float* sv,
+                           const float* h, const float* e, const float* w1, const float* w2, float* dgamma, float* dbeta,
+                           float* dw1, float* db1, float* dw2, float* db2, bf16_t* dy, int N, int HW, int C, int rd,
+                           int accumulate, void* workspace, hipStream_t s);
 
 
 // ---- optional in-process kernel timing (HIP events on the launch stream), used by bench.py ------------------
@@ -663,6 +679,70 @@ int icamd_bn_apply_res_bn(const void* y, const float* scale, const float* shift,
     return ICAMD_ERR_BAD_ARG;
   return icamd_bn_apply_launch((const bf16_t*)y, scale, shift, (const bf16_t*)res_y, (bf16_t*)out, maskbits, numel, C, relu,
                                (hipStream_t)stream, res_scale, res_shift);
+}
+
+// ---- squeeze-and-excitation tail (se_ops.hip) ----
+size_t icamd_se_squeeze_workspace_bytes(int N, int HW, int C) {
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return 0;
+  return icamd_se_squeeze_bytes(N, HW, C);
+}
+
+int icamd_se_squeeze(const void* y, float* ysum, int N, int HW, int C, void* workspace, size_t workspace_bytes, void* stream) {
+  if (y == nullptr || ysum == nullptr || workspace == nullptr || N <= 0 || HW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace_bytes < icamd_se_squeeze_bytes(N, HW, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work(2.0 * N * HW * C + 4.0 * N * C);
+  return icamd_se_squeeze_launch((const bf16_t*)y, ysum, N, HW, C, (float*)workspace, (hipStream_t)stream);
+}
+
+int icamd_se_excite_fwd(const float* ysum, const float* scale, const float* shift, float inv_hw, const float* w1, const float* b1,
+                        const float* w2, const float* b2, float* s, float* h, float* e, int N, int C, int rd, void* stream) {
+  if (ysum == nullptr || scale == nullptr || shift == nullptr || w1 == nullptr || b1 == nullptr || w2 == nullptr || b2 == nullptr ||
+      s == nullptr || h == nullptr || e == nullptr || N <= 0 || C <= 0 || rd <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, 1, C, rd)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_MISC, stream);
+  _prof.work(4.0 * N * (3.0 * C + rd) + 4.0 * (2.0 * C * rd + C + rd), 4.0 * N * C * rd);
+  return icamd_se_excite_fwd_launch(ysum, scale, shift, inv_hw, w1, b1, w2, b2, s, h, e, N, C, rd, (hipStream_t)stream);
+}
+
+int icamd_se_bn_apply(const void* y, const float* scale, const float* shift, const float* e, const void* residual,
+                      const float* res_scale, const float* res_shift, void* out, uint8_t* maskbits, int N, int HW, int C, int relu,
+                      void* stream) {
+  if (y == nullptr || scale == nullptr || shift == nullptr || e == nullptr || out == nullptr || N <= 0 || HW <= 0 || C <= 0 ||
+      (res_scale == nullptr) != (res_shift == nullptr) || (res_scale != nullptr && residual == nullptr))
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_BN_APPLY, stream);
+  const double numel = (double)N * HW * C;
+  _prof.work(numel * (4 + (residual ? 2 : 0)) + (maskbits ? numel / 8.0 : 0) + 4.0 * N * C);
+  return icamd_se_bn_apply_launch((const bf16_t*)y, scale, shift, e, (const bf16_t*)residual, res_scale, res_shift, (bf16_t*)out,
+                                  maskbits, N, HW, C, relu, (hipStream_t)stream);
+}
+
+size_t icamd_se_bn_bwd_workspace_bytes(int N, int HW, int C) {
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return 0;
+  return icamd_se_bn_bwd_bytes(N, HW, C);
+}
+
+int icamd_se_bn_bwd(const void* dout, const uint8_t* maskbits, const void* y, const float* mean, const float* invstd,
+                    const float* gamma, const float* beta, const float* ysum, const float* s, const float* h, const float* e,
+                    const float* w1, const float* w2, float* dgamma, float* dbeta, float* dw1, float* db1, float* dw2, float* db2,
+                    void* dy, int N, int HW, int C, int rd, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dout == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || gamma == nullptr || beta == nullptr ||
+      ysum == nullptr || s == nullptr || h == nullptr || e == nullptr || w1 == nullptr || w2 == nullptr || dgamma == nullptr ||
+      dbeta == nullptr || dw1 == nullptr || db1 == nullptr || dw2 == nullptr || db2 == nullptr || dy == nullptr ||
+      workspace == nullptr || N <= 0 || HW <= 0 || C <= 0 || rd <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, HW, C, rd)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace_bytes < icamd_se_bn_bwd_bytes(N, HW, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_BN_BWD, stream);
+  const double numel = (double)N * HW * C;
+  _prof.work(numel * (2 * 4 + 2) + (maskbits ? numel / 4.0 : 0) + 4.0 * N * (8.0 * C + 2.0 * rd) + 16.0 * C * rd, 8.0 * N * C * rd);
+  return icamd_se_bn_bwd_launch((const bf16_t*)dout, maskbits, (const bf16_t*)y, mean, invstd, gamma, beta, ysum, s, h, e, w1, w2,
+                                dgamma, dbeta, dw1, db1, dw2, db2, (bf16_t*)dy, N, HW, C, rd, accumulate, workspace,
+                                (hipStream_t)stream);
 }
 
 // bwd workspace: partial rows [nblk][2][C] floats | chunks [64][2][C] doubles | c1,c2 [2][C] floats

@@ -104,6 +104,13 @@ _SIGNATURES = {
                                   _P, _P, c_size_t, _P]),
     "icamd_bn_bwd_apply_workspace_bytes": (c_size_t, [c_int]),
     "icamd_bn_bwd_from_partials": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_longlong, c_int, c_int, _P, c_size_t, _P]),
+    # squeeze-and-excitation tail of a bottleneck block (csrc/se_ops.hip)
+    "icamd_se_squeeze_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "icamd_se_squeeze": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "icamd_se_excite_fwd": (c_int, [_P, _P, _P, c_float, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "icamd_se_bn_apply": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "icamd_se_bn_bwd_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "icamd_se_bn_bwd": (c_int, [_P] * 20 + [c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "icamd_layernorm_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_longlong, c_int, c_float, _P]),
     "icamd_layernorm_bwd_workspace_bytes": (c_size_t, [c_longlong, c_int]),
     "icamd_layernorm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_longlong, c_int, c_int, _P, c_size_t, _P]),

@@ -1,5 +1,5 @@
-"""The ResNet family (ResNet-18/34/50/101/152, wide ResNet-50/101-2, ResNeXt-50/101 32x4d) on the gfx950 kernels: static layer
-lists with hand-written forward and backward.
+"""The ResNet family (ResNet-18/34/50/101/152, wide ResNet-50/101-2, ResNeXt-50/101 32x4d, SE-ResNet-50/101/152,
+SE-ResNeXt-50/101 32x4d) on the gfx950 kernels: static layer lists with hand-written forward and backward.
 
 The reference builds its network with timm.create_model (/root/reference/train.py:194) and runs it through
 autograd (engine.py:48,51,64,72); there is no model code in the reference tree.  Here a model is a flat list
@@ -53,13 +53,27 @@ ARCHS = {
     "wide_resnet101_2": ("bottleneck", [3, 4, 23, 3], 1, 128),
     "resnext50_32x4d": ("bottleneck", [3, 4, 6, 3], 32, 4),
     "resnext101_32x4d": ("bottleneck", [3, 4, 23, 3], 32, 4),
+    # a fifth entry True: squeeze-and-excitation on the output of every block's last BatchNorm (timm attn_layer='se')
+    "seresnet50": ("bottleneck", [3, 4, 6, 3], 1, 64, True),
+    "seresnet101": ("bottleneck", [3, 4, 23, 3], 1, 64, True),
+    "seresnet152": ("bottleneck", [3, 8, 36, 3], 1, 64, True),
+    "seresnext50_32x4d": ("bottleneck", [3, 4, 6, 3], 32, 4, True),
+    "seresnext101_32x4d": ("bottleneck", [3, 4, 23, 3], 32, 4, True),
 }
+SE_REDUCTION = 16   # timm SEModule: rd_channels = make_divisible(C / 16, 8, round_limit=0) = C / 16 for C in 256 .. 2048
+
+
+def has_se(arch):
+    row = ARCHS[arch]
+    return len(row) > 4 and bool(row[4])
 
 
 def block_specs(arch):
     """The residual blocks of `arch` as plain data (no GPU, no arenas): one dict per block with
-    convs: [(name, cin, cout, k, stride, pad, groups)], bns: [(name, channels)], down: None or ((conv tuple), (bn tuple))."""
-    block, layers, cardinality, base_width = ARCHS[arch]
+    convs: [(name, cin, cout, k, stride, pad, groups)], bns: [(name, channels)], down: None or ((conv tuple), (bn tuple)),
+    se: None or (name, channels, reduced channels)."""
+    block, layers, cardinality, base_width = ARCHS[arch][:4]
+    se = has_se(arch)
     expansion = 4 if block == "bottleneck" else 1
     specs = []
     inplanes = 64
@@ -81,7 +95,8 @@ def block_specs(arch):
             down = None
             if stride != 1 or inplanes != outplanes:
                 down = ((f"{name}.downsample.0", inplanes, outplanes, 1, stride, 0, 1), (f"{name}.downsample.1", outplanes))
-            specs.append({"name": name, "stride": stride, "convs": convs, "bns": bns, "down": down})
+            specs.append({"name": name, "stride": stride, "convs": convs, "bns": bns, "down": down,
+                          "se": (f"{name}.se", outplanes, outplanes // SE_REDUCTION) if se else None})
             inplanes = outplanes
     return specs
 
@@ -99,10 +114,18 @@ def param_shapes(arch, num_classes=1000):
     for blk in block_specs(arch):
         for c, b in zip(blk["convs"], blk["bns"]):
             out += conv(*c) + bn(*b)
+        if blk["se"] is not None:
+            out += se_shapes(*blk["se"])
         if blk["down"] is not None:
             out += conv(*blk["down"][0]) + bn(*blk["down"][1])
         feat = blk["convs"][-1][2]
     return out + [("fc.weight", (num_classes, feat)), ("fc.bias", (num_classes,))]
+
+
+def se_shapes(name, c, rd):
+    """The four tensors of a block's SE module (two 1x1 nn.Conv2d with bias), in module order."""
+    return [(name + ".fc1.weight", (rd, c, 1, 1)), (name + ".fc1.bias", (rd,)),
+            (name + ".fc2.weight", (c, rd, 1, 1)), (name + ".fc2.bias", (c,))]
 
 
 def _align(n, a):
@@ -152,6 +175,16 @@ class _BN:
         self.stat_offset = None         # mean, invstd, scale, shift in the per-model stat arena (4*c floats)
 
 
+class _SE:
+    """Squeeze-and-excitation record: fc1 [rd][C] + bias, fc2 [C][rd] + bias, fp32 in the parameter arena in torch layout.  The
+    excite kernels read the fp32 masters.  The bf16 shadow arena mirrors the whole parameter arena, so it holds a slice for these
+    tensors too (written by the optimizer kernel with every other element); nothing reads it, and there is no transposed copy."""
+
+    def __init__(self, name, c, rd):
+        self.name, self.c, self.rd = name, c, rd
+        self.w1 = self.b1 = self.w2 = self.b2 = None  # _Param
+
+
 class ResNet(PicklableModel):
     """HIP ResNet. `model(x)` runs the forward and returns bf16 logits [B, num_classes] (a view)."""
 
@@ -167,6 +200,7 @@ class ResNet(PicklableModel):
         self.fold_eval = os.environ.get("ICAMD_EVAL_FOLD", "1") != "0"
         block = ARCHS[arch][0]
         self.block = block
+        self.se = has_se(arch)
         self.expansion = 4 if block == "bottleneck" else 1
         self.ncls_p = _align(num_classes, 64)
         self._build_graph()
@@ -193,6 +227,8 @@ class ResNet(PicklableModel):
             # (record order: the block's convolutions, its BatchNorms, then the shortcut pair -- as before the specs existed)
             blk["convs"] = [self._conv(n, cin, cout, k, st, pad, groups=g) for n, cin, cout, k, st, pad, g in spec["convs"]]
             blk["bns"] = [self._bn(n, c) for n, c in spec["bns"]]
+            if spec["se"] is not None:
+                blk["se"] = _SE(*spec["se"])
             if spec["down"] is not None:
                 (n, cin, cout, k, st, pad, g), (bn_name, bn_c) = spec["down"]
                 blk["down_conv"] = self._conv(n, cin, cout, k, st, pad, groups=g)
@@ -223,8 +259,15 @@ class ResNet(PicklableModel):
 
     def _allocate(self):
         dev = self.device
-        # parameter order = timm/torchvision module order (conv, bn, ..., downsample, fc)
-        order = [m for pair in self.conv_bn_pairs() for m in pair] + [self.fc]
+        # parameter order = timm/torchvision module order (conv, bn, ..., se, downsample, fc)
+        order = [self.stem_conv, self.stem_bn]
+        for blk in self.blocks:
+            order += [m for pair in zip(blk["convs"], blk["bns"]) for m in pair]
+            if "se" in blk:
+                order.append(blk["se"])
+            if "down_conv" in blk:
+                order += [blk["down_conv"], blk["down_bn"]]
+        order.append(self.fc)
         self.params = OrderedDict()
         off = 0
 
@@ -246,6 +289,12 @@ class ResNet(PicklableModel):
                 m.w = add(wname, (m.cout, m.cin // m.groups, m.k, m.k), "conv", (m.cout_p, m.k_p, m.k_p, m.cin_p // m.groups))
                 if m.has_bias:
                     m.b = add(m.name + ".bias", (m.cout,), "vec", (m.cout_p,))
+            elif isinstance(m, _SE):
+                (n1, s1), (nb1, sb1), (n2, s2), (nb2, sb2) = se_shapes(m.name, m.c, m.rd)
+                m.w1 = add(n1, s1, "conv", (m.rd, 1, 1, m.c))     # [rd][1][1][C] is torch's (rd, C, 1, 1) memory
+                m.b1 = add(nb1, sb1, "vec", sb1)
+                m.w2 = add(n2, s2, "conv", (m.c, 1, 1, m.rd))
+                m.b2 = add(nb2, sb2, "vec", sb2)
             else:
                 m.weight = add(m.name + ".weight", (m.c,), "vec", (m.c,))
                 m.bias = add(m.name + ".bias", (m.c,), "vec", (m.c,))
@@ -291,7 +340,7 @@ class ResNet(PicklableModel):
 
     def init_weights(self, zero_init_last=True, seed=None):
         """timm ResNet.init_weights: Kaiming-normal (fan_out, relu) convs, BN weight 1 / bias 0, zero-init of the
-        last BN weight of each residual block, nn.Linear default init for the classifier."""
+        last BN weight of each residual block, nn.Linear default init for the classifier; SE convolutions as every nn.Conv2d."""
         g = torch.Generator()
         if seed is not None:
             g.manual_seed(seed)
@@ -309,6 +358,9 @@ class ResNet(PicklableModel):
             elif name == "fc.bias":
                 bound = 1.0 / math.sqrt(self.feat_dim)
                 sd[name] = (torch.rand(p.torch_shape, generator=g) * 2 - 1) * bound
+            elif ".se." in name:      # the biases of the SE convolutions keep nn.Conv2d's default: U(+-1 / sqrt(fan_in))
+                fan_in = self.params[name[:-len("bias")] + "weight"].torch_shape[1]
+                sd[name] = (torch.rand(p.torch_shape, generator=g) * 2 - 1) / math.sqrt(fan_in)
             elif name.endswith(".weight"):
                 sd[name] = torch.ones(p.torch_shape)
             else:
@@ -475,8 +527,14 @@ class ResNet(PicklableModel):
             cur, ch, cw = x, h, w
             n = len(blk["convs"])
             for i, (conv, bn) in enumerate(zip(blk["convs"], blk["bns"])):
-                d = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, b["a"][i],
-                                        idn.data_ptr() if i == n - 1 else None, True, s)
+                if i == n - 1 and "se" in blk:
+                    # the folded convolution alone (z = conv + shift, no activation), then the SE tail with identity coefficients
+                    d = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, b["y"][i], None, False, s)
+                    one = ws["se_ident"].data_ptr()
+                    self._se_tail(ws, blk, b, one, one + 4 * 4096, idn.data_ptr(), None, N, d.OH * d.OW, s)
+                else:
+                    d = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, b["a"][i],
+                                            idn.data_ptr() if i == n - 1 else None, True, s)
                 cur, ch, cw = b["a"][i], d.OH, d.OW
             x, h, w = cur, ch, cw
         hip.check(lib.icamd_avgpool_fwd(x.data_ptr(), ws["pooled"].data_ptr(), N, h * w, self.feat_dim, s), "avgpool")
@@ -521,6 +579,7 @@ class ResNet(PicklableModel):
         max_bnb = lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, 64)
         h, w = PH, PW
         blocks_ws = []
+        max_se = 0
         for blk in self.blocks:
             b = {}
             ih, iw = h, w
@@ -546,6 +605,13 @@ class ResNet(PicklableModel):
                 max_stats = max(max_stats, lib.icamd_conv2d_stats_rows(ctypes.byref(d)) * 2 * conv.cout_p)
                 max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d))
                 max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d.OH * d.OW, conv.cout_p))
+            if "se" in blk:
+                se = blk["se"]
+                hw_out = ih * iw
+                for key, width in (("se_ysum", se.c), ("se_s", se.c), ("se_h", se.rd), ("se_e", se.c)):
+                    b[key] = torch.empty(N, width, dtype=torch.float32, device=dev)
+                max_se = max(max_se, lib.icamd_se_squeeze_workspace_bytes(N, hw_out, se.c),
+                             lib.icamd_se_bn_bwd_workspace_bytes(N, hw_out, se.c))
             blocks_ws.append(b)
             h, w = ih, iw
         ws["blocks"] = blocks_ws
@@ -565,6 +631,10 @@ class ResNet(PicklableModel):
         ws["bnb_ws2"] = torch.zeros(max_bnb, dtype=torch.uint8, device=dev)   # second BatchNorm of icamd_bn_bwd_dual
         ws["bnb_ws_bytes"] = max_bnb
         ws["max_act"] = max_act
+        if self.se:
+            ws["se_ws"] = torch.empty(max_se, dtype=torch.uint8, device=dev)
+            ws["se_ws_bytes"] = max_se
+            ws["se_ident"] = torch.cat([torch.ones(4096, device=dev), torch.zeros(4096, device=dev)])   # scale 1 | shift 0
         # loss / metric scratch
         ws["loss_rows"] = torch.empty(N, dtype=torch.float32, device=dev)
         ws["pred"] = torch.empty(N, dtype=torch.int32, device=dev)
@@ -679,6 +749,19 @@ class ResNet(PicklableModel):
                                      s), bn.name)
         return d
 
+    def _se_tail(self, ws, blk, b, scale, shift, res, res_bn, N, HW, s):
+        """The SE block's tail on the raw output y of its last convolution: per-sample sums of y, the excitation from them, then
+        out = relu((y * scale + shift) * e[n, c] + shortcut) in one pass (the BatchNorm output itself is never stored)."""
+        lib, se, y = self.lib, blk["se"], b["y"][-1]
+        hip.check(lib.icamd_se_squeeze(y.data_ptr(), b["se_ysum"].data_ptr(), N, HW, se.c, ws["se_ws"].data_ptr(),
+                                       ws["se_ws_bytes"], s), se.name + " squeeze")
+        hip.check(lib.icamd_se_excite_fwd(b["se_ysum"].data_ptr(), scale, shift, 1.0 / HW, self._pf(se.w1), self._pf(se.b1),
+                                          self._pf(se.w2), self._pf(se.b2), b["se_s"].data_ptr(), b["se_h"].data_ptr(),
+                                          b["se_e"].data_ptr(), N, se.c, se.rd, s), se.name + " excite")
+        hip.check(lib.icamd_se_bn_apply(y.data_ptr(), scale, shift, b["se_e"].data_ptr(), res, res_bn[0] if res_bn else None,
+                                        res_bn[1] if res_bn else None, b["a"][-1].data_ptr(),
+                                        b["mask"].data_ptr() if self.training else None, N, HW, se.c, 1, s), se.name + " apply")
+
     # ------------------------------------------------------------------ forward
     def pack(self, x_nchw, mix=None):
         """fp32 NCHW device tensor -> packed NHWC bf16 (channels zero-padded to 8), with optional mixup/cutmix."""
@@ -752,6 +835,12 @@ class ResNet(PicklableModel):
                     cur, ch, cw = b["a"][i], d.OH, d.OW
                     continue
                 defer = False
+                if last and "se" in blk:
+                    # conv3 + statistics + finalize (or the eval coefficients), then the gated apply: no deferral into the next block
+                    d, sc3, sh3 = self._conv_bn_fwd(ws, conv, bn, cur.data_ptr(), N, ch, cw, b["y"][i], None, None, True, s)
+                    self._se_tail(ws, blk, b, sc3, sh3, idn.data_ptr(), res_bn, N, d.OH * d.OW, s)
+                    cur, ch, cw = b["a"][i], d.OH, d.OW
+                    continue
                 if last and self.training and self.block == "bottleneck" and bi + 1 < nblocks:
                     dn = self.blocks[bi + 1]["convs"][0].desc(N, ch, cw)
                     defer = bool(lib.icamd_bn_apply_conv1x1_fused_supported(ctypes.byref(dn)))
@@ -791,6 +880,8 @@ class ResNet(PicklableModel):
         they fill both.  The output-gradient buffers rotate through a small pool so the main stream can run ahead; an
         event per buffer keeps it from overwriting one a pending wgrad still reads."""
         if _FUSED_BNBWD:
+            if self.se:
+                raise hip.IcamdError("ICAMD_FUSED_BNBWD=1 has no squeeze-and-excitation backward")
             return self._backward_packed_fused(ws, accumulate)
         run = self._backward_begin(ws, accumulate, _WGRAD_STREAM and self.wgrad_side_stream)
         bufs = self._grad_buffers(ws)
@@ -879,6 +970,19 @@ class ResNet(PicklableModel):
         dy = self._next_y(run)
         dy2, shortcut_done = None, False
         d3 = conv3.desc(N, *b["hw"][-1])
+        if "se" in blk:
+            # gated BatchNorm + excitation backward: a reduce and an apply pass over (dout, mask bits, y3) with the [N, C]-sized
+            # work between them; the SE gradients are final on the main stream when the call returns.  A projection shortcut's
+            # BatchNorm takes the same dout + mask through icamd_bn_bwd (_bwd_conv1_shortcut)
+            se = blk["se"]
+            mean, invstd, _, _ = self._stats(bn3)
+            hip.check(lib.icamd_se_bn_bwd(dout, mask, y3.data_ptr(), mean, invstd, self._pf(bn3.weight), self._pf(bn3.bias),
+                                          b["se_ysum"].data_ptr(), b["se_s"].data_ptr(), b["se_h"].data_ptr(),
+                                          b["se_e"].data_ptr(), self._pf(se.w1), self._pf(se.w2), self._gf(bn3.weight),
+                                          self._gf(bn3.bias), self._gf(se.w1), self._gf(se.b1), self._gf(se.w2), self._gf(se.b2),
+                                          dy, N, d3.OH * d3.OW, se.c, se.rd, run.acc, ws["se_ws"].data_ptr(), ws["se_ws_bytes"],
+                                          run.s), se.name + " + " + bn3.name + " bwd")
+            return dy, None, False
         if (self.block == "bottleneck" and fused_rows > 0 and lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d3))):
             # conv3 + bn3 backward in one pass over g and y3: BatchNorm finalize from the partial sums, dy3 only in LDS,
             # d(a2) -> DA and the filter gradient out of the same launch
@@ -945,6 +1049,8 @@ class ResNet(PicklableModel):
         if bi == 0 or self.block != "bottleneck":
             return False
         pblk = self.blocks[bi - 1]
+        if "se" in pblk:      # its backward reduces per sample and applies the gate: it takes the unmasked gradient
+            return False
         if "down_conv" not in pblk:
             return True
         dp3 = pblk["convs"][-1].desc(N, h, w)

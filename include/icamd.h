@@ -337,6 +337,35 @@ int icamd_attention_fwd(const void* qkv, void* out, float* lse, int B, int T, in
 int icamd_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                         int B, int T, int H, int D, float scale, void* stream);
 
+/* ---- squeeze-and-excitation tail of a bottleneck block (timm Bottleneck with attn_layer='se') ------------
+ *   z = y*scale[c] + shift[c]   s = mean_hw(z)   h = relu(W1 s + b1)   e = sigmoid(W2 h + b2)   out = relu(z*e[n,c] + shortcut)
+ * y, out, residual, dout, dy: NHWC bf16 [N][HW][C]; every [N,C] / [N,rd] array and all parameters and their gradients fp32
+ * (16-byte aligned); W1 [rd][C], W2 [C][rd] in torch layout.  z is never stored: s comes from the per-sample sums of the raw
+ * convolution output, and the backward needs two per-sample sums of g = dout * maskbits.  All entries: C % 8 == 0, C <= 4096,
+ * rd <= 256, else ICAMD_ERR_UNSUPPORTED; the workspace sizes are 0 for such shapes.  Every output is bitwise repeatable. */
+size_t icamd_se_squeeze_workspace_bytes(int N, int HW, int C);
+/* ysum[n][c] = sum_hw y[n][hw][c] */
+int icamd_se_squeeze(const void* y, float* ysum, int N, int HW, int C, void* workspace, size_t workspace_bytes, void* stream);
+/* s = scale*ysum*inv_hw + shift, h, e as above (all three are kept for the backward) */
+int icamd_se_excite_fwd(const float* ysum, const float* scale, const float* shift, float inv_hw, const float* w1, const float* b1,
+                        const float* w2, const float* b2, float* s, float* h, float* e, int N, int C, int rd, void* stream);
+/* out = act((y*scale[c] + shift[c]) * e[n][c] (+ residual)); residual, res_scale / res_shift (residual = raw shortcut
+ * convolution output, normalised on the fly), relu and maskbits exactly as icamd_bn_apply and icamd_bn_apply_res_bn have them. */
+int icamd_se_bn_apply(const void* y, const float* scale, const float* shift, const float* e, const void* residual,
+                      const float* res_scale, const float* res_shift, void* out, uint8_t* maskbits, int N, int HW, int C, int relu,
+                      void* stream);
+size_t icamd_se_bn_bwd_workspace_bytes(int N, int HW, int C);
+/* Backward of the gated BatchNorm and the excitation in two passes over (dout, maskbits, y) with [N,C]-sized work between them.
+ * With g = dout * maskbits (maskbits NULL: g = dout), A = sum_hw g, B = sum_hw g*xhat, Shat = (ysum - HW*mean)*invstd, M = N*HW:
+ *   de = gamma*B + beta*A   dp2 = de*e*(1-e)   dW2 = dp2^T h   db2 = sum_n dp2   dh = (dp2 W2)*[h>0]   dW1 = dh^T s   db1 = sum_n dh
+ *   ds = dh W1   dbeta = sum_n (e*A + ds)   dgamma = sum_n (e*B + ds*Shat/HW)
+ *   dy = gamma*invstd*(g*e[n][c] + ds[n][c]/HW - dbeta/M - xhat*dgamma/M)
+ * accumulate: the six gradient outputs are added to instead of overwritten. */
+int icamd_se_bn_bwd(const void* dout, const uint8_t* maskbits, const void* y, const float* mean, const float* invstd,
+                    const float* gamma, const float* beta, const float* ysum, const float* s, const float* h, const float* e,
+                    const float* w1, const float* w2, float* dgamma, float* dbeta, float* dw1, float* db1, float* dw2, float* db2,
+                    void* dy, int N, int HW, int C, int rd, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- pooling ---------------------------------------------------------------------------------------- */
 int icamd_maxpool3x3s2_fwd(const void* x, void* out, uint8_t* argmax, int N, int IH, int IW, int C, void* stream);
 /* ResNet stem in training: BatchNorm-apply + ReLU + max-pool 3x3/2 in one pass over the conv output y.  Bit-identical

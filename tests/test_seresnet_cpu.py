@@ -1,0 +1,156 @@
+"""SE-ResNet / SE-ResNeXt (seresnet50/101/152, seresnext50/101_32x4d), the parts that need no GPU: the tests-side reference has the
+published parameter counts and timm's key order, the product's ARCHS rows describe the same graph, the nine older names are
+unchanged, the host-only entries of the SE ABI answer, and the backward-in-sums identity the kernels implement agrees with
+autograd in fp64."""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from _resnext_ref import FAMILY, ResNetFamilyRef  # noqa: E402
+from _seresnet_ref import SE_FAMILY, SEResNetRef  # noqa: E402
+
+PUBLISHED = {
+    "seresnet50": 28088024,
+    "seresnet101": 49326872,
+    "seresnet152": 66821848,
+    "seresnext50_32x4d": 27559896,
+    "seresnext101_32x4d": 48955416,
+}
+SE_SYMBOLS = ("icamd_se_squeeze_workspace_bytes", "icamd_se_squeeze", "icamd_se_excite_fwd", "icamd_se_bn_apply",
+              "icamd_se_bn_bwd_workspace_bytes", "icamd_se_bn_bwd")
+# ResNet-50's four tail shapes at batch 256: (C, HW)
+TAILS = [(256, 3136), (512, 784), (1024, 196), (2048, 49)]
+
+
+def _named_shapes(model):
+    return [(n, tuple(p.shape)) for n, p in model.named_parameters()]
+
+
+@pytest.mark.parametrize("arch", sorted(PUBLISHED))
+def test_reference_parameter_counts(arch):
+    ref = SEResNetRef(arch, 1000)
+    assert sum(p.numel() for p in ref.parameters()) == PUBLISHED[arch]
+    plain = ResNetFamilyRef(arch[2:], 1000)
+    extra = sum(2 * c * (c // 16) + c // 16 + c for c, n in zip([256, 512, 1024, 2048], SE_FAMILY[arch][1]) for _ in range(n))
+    assert PUBLISHED[arch] == sum(p.numel() for p in plain.parameters()) + extra
+
+
+def test_reference_key_names_and_order():
+    sd = SEResNetRef("seresnet50", 10).state_dict()
+    keys = list(sd)
+    i = keys.index("layer1.0.bn3.num_batches_tracked")
+    assert keys[i + 1:i + 6] == ["layer1.0.se.fc1.weight", "layer1.0.se.fc1.bias", "layer1.0.se.fc2.weight", "layer1.0.se.fc2.bias",
+                                 "layer1.0.downsample.0.weight"]
+    i = keys.index("layer1.1.bn3.num_batches_tracked")
+    assert keys[i + 1:i + 6] == ["layer1.1.se.fc1.weight", "layer1.1.se.fc1.bias", "layer1.1.se.fc2.weight", "layer1.1.se.fc2.bias",
+                                 "layer1.2.conv1.weight"]
+    assert tuple(sd["layer1.0.se.fc1.weight"].shape) == (16, 256, 1, 1) and tuple(sd["layer1.0.se.fc1.bias"].shape) == (16,)
+    assert tuple(sd["layer4.2.se.fc2.weight"].shape) == (2048, 128, 1, 1) and tuple(sd["layer4.2.se.fc2.bias"].shape) == (2048,)
+    # timm's init: Kaiming-normal (fan_out) on both SE weights, nn.Conv2d's default U(+-1/sqrt(fan_in)) on the biases
+    torch.manual_seed(0)
+    ref = SEResNetRef("seresnet50", 10)
+    w = ref.layer3[0].se.fc2.weight
+    assert abs(float(w.detach().std()) / (2.0 / 1024) ** 0.5 - 1.0) <= 0.05
+    b = ref.layer3[0].se.fc1.bias
+    assert 0.0 < float(b.detach().abs().max()) <= 1.0 / 1024 ** 0.5
+
+
+@pytest.mark.parametrize("arch", sorted(PUBLISHED))
+def test_product_archs_describe_the_same_graph(arch):
+    from imageclassification_amd import nets
+    assert arch in nets.ARCHS and nets.has_se(arch)
+    assert nets.param_shapes(arch, 1000) == _named_shapes(SEResNetRef(arch, 1000))
+    assert sum(torch.Size(s).numel() for _, s in nets.param_shapes(arch, 1000)) == PUBLISHED[arch]
+    specs = nets.block_specs(arch)
+    assert all(blk["se"] == (blk["name"] + ".se", blk["convs"][-1][2], blk["convs"][-1][2] // 16) for blk in specs)
+    groups = {c[0]: c[6] for blk in specs for c in blk["convs"]}
+    assert all(g == (SE_FAMILY[arch][2] if n.endswith(".conv2") else 1) for n, g in groups.items())
+
+
+@pytest.mark.parametrize("arch", sorted(FAMILY))
+def test_existing_names_unchanged(arch):
+    from imageclassification_amd import nets
+    assert not nets.has_se(arch)
+    assert nets.param_shapes(arch, 1000) == _named_shapes(ResNetFamilyRef(arch, 1000))
+    assert all(blk["se"] is None for blk in nets.block_specs(arch))
+    assert tuple(nets.ARCHS[arch][:4]) == tuple(FAMILY[arch])
+
+
+def test_train_cli_lists_the_new_names():
+    import train
+    with pytest.raises(ValueError) as e:
+        train.create_model("nope", 10)
+    for arch in PUBLISHED:
+        assert arch in str(e.value)
+
+
+def test_se_abi_host_side():
+    from imageclassification_amd import hip
+    lib = hip.load()
+    for name in SE_SYMBOLS:
+        assert name in hip.EXPORTED_SYMBOLS
+    assert lib.icamd_abi_version() == 6
+    for C, HW in TAILS:
+        assert lib.icamd_se_bn_bwd_workspace_bytes(256, HW, C) > 0
+        assert lib.icamd_se_squeeze_workspace_bytes(256, HW, C) > 0
+        assert lib.icamd_se_bn_bwd_workspace_bytes(256, HW, C) >= 4 * 256 * C * 5     # the [N, C] tables alone
+    for C in (12, 4, 2052):
+        assert lib.icamd_se_bn_bwd_workspace_bytes(4, 49, C) == 0
+        assert lib.icamd_se_squeeze_workspace_bytes(4, 49, C) == 0
+    assert lib.icamd_se_bn_bwd_workspace_bytes(4, 49, 8192) == 0       # C > 4096
+    assert lib.icamd_se_bn_bwd_workspace_bytes(0, 49, 256) == 0 and lib.icamd_se_bn_bwd_workspace_bytes(4, 0, 256) == 0
+
+
+def test_backward_in_sums_identity_fp64():
+    """The backward the kernels implement -- two per-sample sums A = sum_hw g, B = sum_hw g*xhat, everything else [N, C]-sized --
+    against autograd on the block tail in fp64 at N 3, C 32, 5 x 7, rd 2: every tensor to 1e-12."""
+    torch.manual_seed(3)
+    N, C, H, W, rd = 3, 32, 5, 7, 2
+    HW, M, eps = H * W, N * H * W, 1e-5
+    dd = torch.float64
+    y = torch.randn(N, C, H, W, dtype=dd, requires_grad=True)
+    gamma = (torch.rand(C, dtype=dd) + 0.5).requires_grad_()
+    beta = (torch.randn(C, dtype=dd) * 0.3).requires_grad_()
+    W1 = (torch.randn(rd, C, dtype=dd) * 0.3).requires_grad_()
+    b1 = (torch.randn(rd, dtype=dd) * 0.3 + 0.5).requires_grad_()
+    W2 = (torch.randn(C, rd, dtype=dd) * 0.8).requires_grad_()
+    b2 = (torch.randn(C, dtype=dd) * 0.3).requires_grad_()
+    shortcut = torch.randn(N, C, H, W, dtype=dd, requires_grad=True)
+    dout = torch.randn(N, C, H, W, dtype=dd)
+    mu = y.mean((0, 2, 3))
+    invstd = 1.0 / torch.sqrt(y.var((0, 2, 3), unbiased=False) + eps)
+    yhat = (y - mu[None, :, None, None]) * invstd[None, :, None, None]
+    z = yhat * gamma[None, :, None, None] + beta[None, :, None, None]
+    s = z.mean((2, 3))
+    h = torch.relu(s @ W1.t() + b1)
+    e = torch.sigmoid(h @ W2.t() + b2)
+    out = torch.relu(z * e[:, :, None, None] + shortcut)
+    out.backward(dout)
+    with torch.no_grad():
+        g = dout * (out > 0)
+        A = g.sum((2, 3))
+        B = (g * yhat).sum((2, 3))
+        Shat = (y.sum((2, 3)) - HW * mu) * invstd
+        s_lin = gamma * invstd * (y.sum((2, 3)) / HW - mu) + beta          # the forward's s from the sums of the raw y
+        de = gamma * B + beta * A
+        dp2 = de * e * (1 - e)
+        dW2, db2 = dp2.t() @ h, dp2.sum(0)
+        dh = (dp2 @ W2) * (h > 0)
+        dW1, db1 = dh.t() @ s, dh.sum(0)
+        ds = dh @ W1
+        dbeta = (e * A + ds).sum(0)
+        dgamma = (e * B + ds * Shat / HW).sum(0)
+        dy = (gamma * invstd)[None, :, None, None] * (g * e[:, :, None, None] + (ds / HW)[:, :, None, None]
+                                                      - (dbeta / M)[None, :, None, None] - yhat * (dgamma / M)[None, :, None, None])
+        assert float((s_lin - s).abs().max()) <= 1e-12
+        for name, got, want in (("dy", dy, y.grad), ("dgamma", dgamma, gamma.grad), ("dbeta", dbeta, beta.grad), ("dW1", dW1, W1.grad),
+                                ("db1", db1, b1.grad), ("dW2", dW2, W2.grad), ("db2", db2, b2.grad), ("dshortcut", g, shortcut.grad)):
+            assert float(want.abs().max()) > 0.0, name
+            assert float((got - want).abs().max()) <= 1e-12, (name, float((got - want).abs().max()))
+        # gamma = beta = 0: de, and with it the four SE gradients, are exact zeros
+        de0 = 0.0 * B + 0.0 * A
+        assert float(de0.abs().max()) == 0.0
