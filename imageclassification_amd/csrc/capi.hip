@@ -615,6 +615,90 @@ int icamd_gconv3x3_wgrad(const icamd_conv_desc* d, int groups, const void* x, co
   return icamd_slab_reduce_launch(p.slab, dw, (long long)d->Cin * 9 * (d->Cin / groups), p.S, accumulate, (hipStream_t)stream);
 }
 
+// ---- ResNet-D: 2x2 average pool of the shortcut and the thin 3x3 convolutions of the deep stem (conv_stem_deep.hip).  Arguments are
+// validated before any profiling work is booked.
+int icamd_avgpool2x2_fwd(const void* x, void* out, int N, int IH, int IW, int C, void* stream) {
+  if (x == nullptr || out == nullptr || !icamd_avgpool2x2_ok(N, IH, IW, C)) return ICAMD_ERR_BAD_ARG;
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work(2.0 * N * IH * IW * C + 2.0 * N * ((IH + 1) / 2) * ((IW + 1) / 2) * C);
+  Pool2x2Params p;
+  memset(&p, 0, sizeof(p));
+  p.in = (const bf16_t*)x; p.out = (bf16_t*)out; p.N = N; p.IH = IH; p.IW = IW; p.C8 = C / 8;
+  return icamd_avgpool2x2_launch(p, 0, (hipStream_t)stream);
+}
+
+int icamd_avgpool2x2_bwd(const void* dout, const void* addend, void* dx, int N, int IH, int IW, int C, void* stream) {
+  if (dout == nullptr || dx == nullptr || !icamd_avgpool2x2_ok(N, IH, IW, C)) return ICAMD_ERR_BAD_ARG;
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work((addend ? 4.0 : 2.0) * N * IH * IW * C + 2.0 * N * ((IH + 1) / 2) * ((IW + 1) / 2) * C);
+  Pool2x2Params p;
+  memset(&p, 0, sizeof(p));
+  p.in = (const bf16_t*)dout; p.addend = (const bf16_t*)addend; p.out = (bf16_t*)dx; p.N = N; p.IH = IH; p.IW = IW; p.C8 = C / 8;
+  return icamd_avgpool2x2_launch(p, 1, (hipStream_t)stream);
+}
+
+static bool thin_ok(const icamd_conv_desc* d) {
+  if (!conv_desc_ok(d)) return false;
+  if (d->KH != 3 || d->KW != 3 || d->pad != 1 || d->stride != 1) return false;
+  return icamd_thin3x3_ok(d->N, d->IH, d->IW, d->Cin, d->Cout);
+}
+static ThinConvParams thin_params(const icamd_conv_desc* d) {
+  ThinConvParams p;
+  memset(&p, 0, sizeof(p));
+  p.N = d->N; p.H = d->IH; p.W = d->IW; p.Cout = d->Cout;
+  return p;
+}
+static void thin_work(ProfScope& prof, const icamd_conv_desc* d, double filter_bytes_per_element) {
+  const ConvWork cw = conv_work(d);
+  prof.work(cw.in + cw.out + filter_bytes_per_element * cw.w, cw.flops);
+}
+
+int icamd_conv3x3_thin_supported(const icamd_conv_desc* d) { return thin_ok(d) ? 1 : 0; }
+
+int icamd_conv3x3_thin_stats_rows(const icamd_conv_desc* d) {
+  return thin_ok(d) ? icamd_thin3x3_stats_rows(d->N, d->IH, d->IW, d->Cout) : 0;
+}
+
+int icamd_conv3x3_thin_fwd(const icamd_conv_desc* d, const void* x, const void* w, void* y, const float* bias, float* stats, int relu,
+                           void* stream) {
+  if (d == nullptr || x == nullptr || w == nullptr || y == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!thin_ok(d)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_IGEMM_FWD, stream);
+  thin_work(_prof, d, 2.0);
+  ThinConvParams p = thin_params(d);
+  p.in = (const bf16_t*)x; p.w = (const bf16_t*)w; p.out = (bf16_t*)y; p.bias = bias; p.stats = stats; p.relu = relu ? 1 : 0;
+  return icamd_thin3x3_fwd_launch(p, (hipStream_t)stream);
+}
+
+int icamd_conv3x3_thin_dgrad(const icamd_conv_desc* d, const void* dy, const void* w, void* dx, void* stream) {
+  if (d == nullptr || dy == nullptr || w == nullptr || dx == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!thin_ok(d)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_IGEMM_DGRAD, stream);
+  thin_work(_prof, d, 2.0);
+  ThinConvParams p = thin_params(d);
+  p.in = (const bf16_t*)dy; p.w = (const bf16_t*)w; p.out = (bf16_t*)dx;
+  return icamd_thin3x3_dgrad_launch(p, (hipStream_t)stream);
+}
+
+size_t icamd_conv3x3_thin_wgrad_workspace_bytes(const icamd_conv_desc* d) {
+  return thin_ok(d) ? icamd_thin3x3_wgrad_bytes(d->N, d->IH, d->IW, d->Cout) : 0;
+}
+
+int icamd_conv3x3_thin_wgrad(const icamd_conv_desc* d, const void* x, const void* dy, float* dw, int accumulate, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  if (d == nullptr || x == nullptr || dy == nullptr || dw == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!thin_ok(d)) return ICAMD_ERR_UNSUPPORTED;
+  const size_t need = icamd_conv3x3_thin_wgrad_workspace_bytes(d);
+  if (workspace == nullptr || need == 0 || workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_WGRAD, stream);
+  thin_work(_prof, d, 4.0);
+  ThinConvParams p = thin_params(d);
+  p.in = (const bf16_t*)x; p.dy = (const bf16_t*)dy; p.slab = (float*)workspace;
+  const int rc = icamd_thin3x3_wgrad_launch(p, (hipStream_t)stream);
+  if (rc) return rc;
+  return icamd_slab_reduce_launch(p.slab, dw, (long long)d->Cout * 9 * 32, p.S, accumulate, (hipStream_t)stream);
+}
+
 int icamd_filter_transpose(const void* src_base, void* dst_base, const int64_t* descs, const int32_t* jobs, int njobs,
                            void* stream) {
   ProfScope _prof(PC_OPTIM, stream);

@@ -76,6 +76,40 @@ int icamd_gconv3x3_dgrad_launch(GConvParams& p, hipStream_t stream);
 size_t icamd_gconv3x3_wgrad_bytes(int N, int IH, int IW, int OH, int OW, int C, int groups, int stride);
 int icamd_gconv3x3_wgrad_launch(GConvParams& p, hipStream_t stream);   // fills p.S; the caller folds the slabs
 
+// 2x2 / stride 2 average pool, ceil_mode, count_include_pad=False, and the thin 3x3 convolution of the deep stem (conv_stem_deep.hip)
+struct Pool2x2Params {
+  const bf16_t* in;      // forward: x [N][IH][IW][C]; backward: dout [N][OH][OW][C]
+  const bf16_t* addend;  // backward, optional: [N][IH][IW][C]
+  bf16_t* out;           // forward: [N][OH][OW][C]; backward: dx [N][IH][IW][C]
+  int N, IH, IW, C8;     // C8 = C / 8
+  int OH, OW;            // filled by the launcher
+  unsigned int total;
+  FastDiv divC8, divOW, divOH;
+};
+bool icamd_avgpool2x2_ok(int N, int IH, int IW, int C);
+int icamd_avgpool2x2_launch(Pool2x2Params& p, int backward, hipStream_t stream);
+
+struct ThinConvParams {
+  const bf16_t* in;      // forward / weight gradient: x [N][H][W][32]; data gradient: dy [N][H][W][Cout]
+  const bf16_t* w;       // [Cout][3][3][32], the forward layout for every launch
+  bf16_t* out;           // forward: y [N][H][W][Cout]; data gradient: dx [N][H][W][32]
+  const bf16_t* dy;      // weight gradient only
+  float* slab;           // weight gradient: [S][Cout][3][3][32] partial sums
+  const float* bias;     // optional [Cout] (forward)
+  float* stats;          // optional [icamd_thin3x3_stats_rows][2][Cout] (forward)
+  int relu;
+  int N, H, W, Cout;
+  int M, nalloc, ntiles;               // filled by the launcher
+  int S, tiles_per_split;              // filled by the launcher (weight gradient)
+  FastDiv divHW, divW;
+};
+bool icamd_thin3x3_ok(int N, int H, int W, int Cin, int Cout);
+int icamd_thin3x3_stats_rows(int N, int H, int W, int Cout);
+int icamd_thin3x3_fwd_launch(ThinConvParams& p, hipStream_t stream);
+int icamd_thin3x3_dgrad_launch(ThinConvParams& p, hipStream_t stream);
+size_t icamd_thin3x3_wgrad_bytes(int N, int H, int W, int Cout);
+int icamd_thin3x3_wgrad_launch(ThinConvParams& p, hipStream_t stream);   // fills p.S; the caller folds the slabs
+
 // Dense NT GEMM for big pointwise problems: out[m][n] = sum_k A[m][k] * B[n][k] (+ bias[n]) (+ addend[m][n])
 struct GemmNtParams {
   const bf16_t* A;       // [M][K]

@@ -90,6 +90,15 @@ _SIGNATURES = {
     "icamd_gconv3x3_dgrad": (c_int, [POINTER(ConvDesc), c_int, _P, _P, _P, _P]),
     "icamd_gconv3x3_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvDesc), c_int]),
     "icamd_gconv3x3_wgrad": (c_int, [POINTER(ConvDesc), c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
+    # ResNet-D (csrc/conv_stem_deep.hip): 2x2 average pool of the shortcut, thin 3x3 convolutions (Cin 32) of the deep stem
+    "icamd_avgpool2x2_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "icamd_avgpool2x2_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "icamd_conv3x3_thin_supported": (c_int, [POINTER(ConvDesc)]),
+    "icamd_conv3x3_thin_stats_rows": (c_int, [POINTER(ConvDesc)]),
+    "icamd_conv3x3_thin_fwd": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, c_int, _P]),
+    "icamd_conv3x3_thin_dgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P]),
+    "icamd_conv3x3_thin_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvDesc)]),
+    "icamd_conv3x3_thin_wgrad": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P, c_size_t, _P]),
     "icamd_filter_transpose": (c_int, [_P, _P, _P, _P, c_int, _P]),
     "icamd_filter_transpose_tiled": (c_int, [_P, _P, _P, _P, c_int, _P]),
     "icamd_bn_workspace_bytes": (c_size_t, [c_int]),

@@ -1,5 +1,6 @@
 """The ResNet family (ResNet-18/34/50/101/152, wide ResNet-50/101-2, ResNeXt-50/101 32x4d, SE-ResNet-50/101/152,
-SE-ResNeXt-50/101 32x4d) on the gfx950 kernels: static layer lists with hand-written forward and backward.
+SE-ResNeXt-50/101 32x4d, and the "D" variants ResNet-18d/34d/26d/50d/101d/152d/200d, SE-ResNet-152d, SE-ResNeXt-26d 32x4d) on
+the gfx950 kernels: static layer lists with hand-written forward and backward.
 
 The reference builds its network with timm.create_model (/root/reference/train.py:194) and runs it through
 autograd (engine.py:48,51,64,72); there is no model code in the reference tree.  Here a model is a flat list
@@ -39,6 +40,16 @@ _SUB2_SHORTCUT = os.environ.get("ICAMD_SUB2_SHORTCUT", "1") != "0"
 # 17.78 against 18.06 ms per step.  (Round 2, gather from global memory: -0.20 ms of pooling, +0.27 ms of BatchNorm backward.)
 # ICAMD_FUSED_POOL_BWD=0 forces the two-call route.
 _FUSED_POOL_BWD = os.environ.get("ICAMD_FUSED_POOL_BWD", "1") != "0"
+# The thin 3x3 kernels (csrc/conv_stem_deep.hip) under the second and third convolution of a D variant's deep stem, per operation.
+# ICAMD_STEM_THIN (read once per process): unset / 1 = the defaults below, wherever icamd_conv3x3_thin_supported says so; 0 = every
+# operation on icamd_conv2d_fwd / _dgrad / _wgrad; 2 = every operation on the thin kernels.  A default is False where the thin
+# kernel measured slower than the general route (tools/bench_stem_deep.py, profiles/resnet_d.txt): at batch 256,
+# 112 x 112 the thin forward is 2.0x / 1.4x (32 -> 32 / 32 -> 64) and the thin data gradient 2.2x / 1.7x faster than the general
+# route, the thin weight gradient 0.71x / 0.66x (401 / 474 us against 286 / 311 us) -- so the weight gradient stays on
+# icamd_conv2d_wgrad unless ICAMD_STEM_THIN=2.
+_STEM_THIN_DEFAULT = {"fwd": True, "dgrad": True, "wgrad": False}
+_STEM_THIN_ENV = os.environ.get("ICAMD_STEM_THIN", "1")
+_STEM_THIN = {op: (_STEM_THIN_ENV == "2" or (_STEM_THIN_ENV != "0" and on)) for op, on in _STEM_THIN_DEFAULT.items()}
 BN_MOMENTUM = 0.1
 
 # name -> (block, blocks per stage, cardinality, base width), as timm / torchvision: a bottleneck's inner width is
@@ -59,6 +70,18 @@ ARCHS = {
     "seresnet152": ("bottleneck", [3, 8, 36, 3], 1, 64, True),
     "seresnext50_32x4d": ("bottleneck", [3, 4, 6, 3], 32, 4, True),
     "seresnext101_32x4d": ("bottleneck", [3, 4, 23, 3], 32, 4, True),
+    # a sixth entry True: the "D" variant of "Bag of Tricks" (timm stem_width=32, stem_type='deep', avg_down=True): the 7x7 stem
+    # becomes three 3x3 convolutions (3 -> 32 stride 2, 32 -> 32, 32 -> 64), and a projection shortcut becomes
+    # AvgPool2d(2, stride, ceil_mode=True, count_include_pad=False) -> 1x1 stride-1 convolution -> BatchNorm
+    "resnet18d": ("basic", [2, 2, 2, 2], 1, 64, False, True),
+    "resnet34d": ("basic", [3, 4, 6, 3], 1, 64, False, True),
+    "resnet26d": ("bottleneck", [2, 2, 2, 2], 1, 64, False, True),
+    "resnet50d": ("bottleneck", [3, 4, 6, 3], 1, 64, False, True),
+    "resnet101d": ("bottleneck", [3, 4, 23, 3], 1, 64, False, True),
+    "resnet152d": ("bottleneck", [3, 8, 36, 3], 1, 64, False, True),
+    "resnet200d": ("bottleneck", [3, 24, 36, 3], 1, 64, False, True),
+    "seresnet152d": ("bottleneck", [3, 8, 36, 3], 1, 64, True, True),
+    "seresnext26d_32x4d": ("bottleneck", [2, 2, 2, 2], 32, 4, True, True),
 }
 SE_REDUCTION = 16   # timm SEModule: rd_channels = make_divisible(C / 16, 8, round_limit=0) = C / 16 for C in 256 .. 2048
 
@@ -68,12 +91,29 @@ def has_se(arch):
     return len(row) > 4 and bool(row[4])
 
 
+def is_d(arch):
+    row = ARCHS[arch]
+    return len(row) > 5 and bool(row[5])
+
+
+def stem_specs(arch):
+    """The stem as [((conv tuple), (bn tuple))] in module order; conv tuple as in block_specs."""
+    if not is_d(arch):
+        return [(("conv1", 3, 64, 7, 2, 3, 1), ("bn1", 64))]
+    # nn.Sequential(conv, bn, relu, conv, bn, relu, conv) named conv1, then bn1: indices 2 and 5 are the ReLUs
+    return [(("conv1.0", 3, 32, 3, 2, 1, 1), ("conv1.1", 32)), (("conv1.3", 32, 32, 3, 1, 1, 1), ("conv1.4", 32)),
+            (("conv1.6", 32, 64, 3, 1, 1, 1), ("bn1", 64))]
+
+
 def block_specs(arch):
     """The residual blocks of `arch` as plain data (no GPU, no arenas): one dict per block with
     convs: [(name, cin, cout, k, stride, pad, groups)], bns: [(name, channels)], down: None or ((conv tuple), (bn tuple)),
-    se: None or (name, channels, reduced channels)."""
+    se: None or (name, channels, reduced channels).  D variants only: the shortcut is Sequential(pool or Identity, conv, bn) --
+    its convolution is 1x1 / stride 1 under the names downsample.1 / downsample.2 -- and every dict has pool: True where the
+    shortcut starts with the 2x2 average pool (the stride-2 blocks), False elsewhere."""
     block, layers, cardinality, base_width = ARCHS[arch][:4]
     se = has_se(arch)
+    deep = is_d(arch)
     expansion = 4 if block == "bottleneck" else 1
     specs = []
     inplanes = 64
@@ -93,10 +133,14 @@ def block_specs(arch):
                          (f"{name}.conv2", planes, planes, 3, 1, 1, 1)]
                 bns = [(f"{name}.bn1", planes), (f"{name}.bn2", planes)]
             down = None
-            if stride != 1 or inplanes != outplanes:
+            if (stride != 1 or inplanes != outplanes) and deep:
+                down = ((f"{name}.downsample.1", inplanes, outplanes, 1, 1, 0, 1), (f"{name}.downsample.2", outplanes))
+            elif stride != 1 or inplanes != outplanes:
                 down = ((f"{name}.downsample.0", inplanes, outplanes, 1, stride, 0, 1), (f"{name}.downsample.1", outplanes))
             specs.append({"name": name, "stride": stride, "convs": convs, "bns": bns, "down": down,
                           "se": (f"{name}.se", outplanes, outplanes // SE_REDUCTION) if se else None})
+            if deep:
+                specs[-1]["pool"] = down is not None and stride != 1
             inplanes = outplanes
     return specs
 
@@ -109,7 +153,9 @@ def param_shapes(arch, num_classes=1000):
     def conv(name, cin, cout, k, stride, pad, groups):
         return [(name + ".weight", (cout, cin // groups, k, k))]
 
-    out = conv("conv1", 3, 64, 7, 2, 3, 1) + bn("bn1", 64)
+    out = []
+    for c, b in stem_specs(arch):
+        out += conv(*c) + bn(*b)
     feat = 64
     for blk in block_specs(arch):
         for c, b in zip(blk["convs"], blk["bns"]):
@@ -157,6 +203,8 @@ class _Conv:
         self.b = None
         self.wt_offset = None  # offset into the transposed shadow arena (None: no data gradient needed)
         self.descs = {}    # (N, IH, IW) -> ConvDesc
+        self.thin = False  # 3x3 / stride 1 with 32 input channels (deep stem): the icamd_conv3x3_thin_* entries where routed
+        self.stem7 = False # the 7x7 / stride 2 stem on the rgb4 layout: the icamd_stem7x7s2_* entries
 
     def desc(self, N, IH, IW):
         key = (N, IH, IW)
@@ -201,6 +249,7 @@ class ResNet(PicklableModel):
         block = ARCHS[arch][0]
         self.block = block
         self.se = has_se(arch)
+        self.deep = is_d(arch)
         self.expansion = 4 if block == "bottleneck" else 1
         self.ncls_p = _align(num_classes, 64)
         self._build_graph()
@@ -218,8 +267,22 @@ class ResNet(PicklableModel):
         self.convs, self.bns = [], []
         # stem filters live as [64][8][8][4] (row 7, column 7, channel 3 zero): the layout icamd_stem7x7s2_fwd / _wgrad
         # reduce over, on the [N][H][W+8][4] image icamd_pack_input_rgb4 writes
-        self.stem_conv = self._conv("conv1", 3, 64, 7, 2, 3, cin_p=4, k_p=8)
-        self.stem_bn = self._bn("bn1", 64)
+        if self.deep:
+            # deep stem: three conv + BatchNorm pairs; the first convolution reads the 8-channel packed image (icamd_pack_input) on
+            # the general entries, the other two are the thin 3x3 problems.  stem_conv is the first of them (what reads the image);
+            # stem_bn is bn1, whose apply is fused with the max-pool as for the plain stem
+            self.stem_pairs = []
+            for (n, cin, cout, k, st, pad, g), (bn_name, bn_c) in stem_specs(self.arch):
+                conv = self._conv(n, cin, cout, k, st, pad, cin_p=8 if cin == 3 else None)
+                conv.thin = cin == 32
+                self.stem_pairs.append((conv, self._bn(bn_name, bn_c)))
+            self.stem_conv = self.stem_pairs[0][0]
+            self.stem_bn = self.stem_pairs[-1][1]
+        else:
+            self.stem_conv = self._conv("conv1", 3, 64, 7, 2, 3, cin_p=4, k_p=8)
+            self.stem_conv.stem7 = True
+            self.stem_bn = self._bn("bn1", 64)
+            self.stem_pairs = [(self.stem_conv, self.stem_bn)]
         self.blocks = []
         inplanes = 64
         for spec in block_specs(self.arch):
@@ -233,6 +296,8 @@ class ResNet(PicklableModel):
                 (n, cin, cout, k, st, pad, g), (bn_name, bn_c) = spec["down"]
                 blk["down_conv"] = self._conv(n, cin, cout, k, st, pad, groups=g)
                 blk["down_bn"] = self._bn(bn_name, bn_c)
+            if spec.get("pool"):
+                blk["pool"] = True     # 2x2 average pool in front of the shortcut convolution (which is then 1x1 / stride 1)
             self.blocks.append(blk)
             inplanes = spec["convs"][-1][2]
         self.feat_dim = inplanes
@@ -250,7 +315,7 @@ class ResNet(PicklableModel):
 
     def conv_bn_pairs(self):
         """[(conv, bn)] in module order: the stem, then each block's convolutions, then its shortcut pair."""
-        pairs = [(self.stem_conv, self.stem_bn)]
+        pairs = list(self.stem_pairs)
         for blk in self.blocks:
             pairs += zip(blk["convs"], blk["bns"])
             if "down_conv" in blk:
@@ -260,7 +325,7 @@ class ResNet(PicklableModel):
     def _allocate(self):
         dev = self.device
         # parameter order = timm/torchvision module order (conv, bn, ..., se, downsample, fc)
-        order = [self.stem_conv, self.stem_bn]
+        order = [m for pair in self.stem_pairs for m in pair]
         for blk in self.blocks:
             order += [m for pair in zip(blk["convs"], blk["bns"]) for m in pair]
             if "se" in blk:
@@ -308,8 +373,9 @@ class ResNet(PicklableModel):
         self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev)
         self.buffer_arena = torch.zeros(max(boff, 64), dtype=torch.float32, device=dev)
         self.stat_arena = torch.zeros(max(soff, 64), dtype=torch.float32, device=dev)
-        # transposed filters for the data-gradient kernels (every conv except the stem and the grouped ones, whose data gradient
-        # reads the forward layout)
+        # transposed filters for the data-gradient kernels (every conv except the stem's first and the grouped ones, whose data
+        # gradient reads the forward layout; so does the thin route of the deep stem's other two, but those keep their 2 x 18 KB:
+        # ICAMD_STEM_THIN=0 and images too wide for the thin kernels' LDS tile run on icamd_conv2d_dgrad)
         toff = 0
         descs, jobs, tjobs = [], [], []
         for m in self.convs:
@@ -513,14 +579,18 @@ class ResNet(PicklableModel):
         N, H, W = ws["N"], ws["H"], ws["Ws"]
         if self._fold_dirty:
             self.fold_batchnorm()
-        d0 = self._conv_act_eval(self.stem_conv, self.stem_bn, ws["x8"].data_ptr(), N, H, W, ws["a0"], None, True, s)
+        cur, ch, cw = ws["x8"], H, W
+        for (conv, bn), out in zip(self.stem_pairs, ws.get("stem_a", []) + [ws["a0"]]):
+            d0 = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, out, None, True, s)
+            cur, ch, cw = out, d0.OH, d0.OW
         hip.check(lib.icamd_maxpool3x3s2_fwd(ws["a0"].data_ptr(), ws["p0"].data_ptr(), None, N, d0.OH, d0.OW, 64, s),
                   "maxpool")
         x = ws["p0"]
         h, w = x.shape[1], x.shape[2]
         for blk, b in zip(self.blocks, ws["blocks"]):
             if "down_conv" in blk:
-                self._conv_act_eval(blk["down_conv"], blk["down_bn"], x.data_ptr(), N, h, w, b["ad"], None, False, s)
+                xs, sh_, sw_ = self._shortcut_input(blk, b, x, N, h, w, s)
+                self._conv_act_eval(blk["down_conv"], blk["down_bn"], xs.data_ptr(), N, sh_, sw_, b["ad"], None, False, s)
                 idn = b["ad"]
             else:
                 idn = x
@@ -564,19 +634,44 @@ class ResNet(PicklableModel):
 
         # the rgb4 stem layout (3 + 5 zero columns per row); an odd width gets one more zero column -- part of the
         # convolution's own padding -- and the stem kernels run on the even width Ws
-        Ws = W + (W & 1)
-        ws["Ws"] = Ws
-        ws["x8"] = act(N, H, Ws + 8, 4)
-        d0 = self.stem_conv.desc(N, H, Ws)
-        ws["y0"] = act(N, d0.OH, d0.OW, 64)
+        if self.deep:
+            # deep stem: the 8-channel packed image; stem_in[i] / stem_y[i] = input / raw output of the i-th stem convolution,
+            # stem_a[i] = its BatchNorm + ReLU output (the third one's goes through the fused max-pool and is never stored:
+            # y0 is stem_y[2]); the batch statistics sit in the stat arena (_stats(bn))
+            Ws = W
+            ws["Ws"] = Ws
+            ws["x8"] = act(N, H, W, 8)
+            ws["stem_y"], ws["stem_a"], ws["stem_in"], ws["stem_hw"] = [], [], [ws["x8"]], []
+            max_act, max_stats, max_wg, max_bnb = ws["x8"].numel(), 0, 0, 0
+            sh_, sw_ = H, W
+            for i, (conv, bn) in enumerate(self.stem_pairs):
+                d0 = conv.desc(N, sh_, sw_)
+                ws["stem_hw"].append((sh_, sw_))
+                ws["stem_y"].append(act(N, d0.OH, d0.OW, conv.cout_p))
+                if i + 1 < len(self.stem_pairs):
+                    ws["stem_a"].append(act(N, d0.OH, d0.OW, conv.cout_p))
+                    ws["stem_in"].append(ws["stem_a"][-1])
+                max_act = max(max_act, ws["stem_y"][-1].numel())
+                max_stats = max(max_stats, self._stats_rows(conv, d0) * 2 * conv.cout_p)
+                max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d0))
+                max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, conv.cout_p))
+                sh_, sw_ = d0.OH, d0.OW
+            ws["y0"] = ws["stem_y"][-1]
+        else:
+            Ws = W + (W & 1)
+            ws["Ws"] = Ws
+            ws["x8"] = act(N, H, Ws + 8, 4)
+            d0 = self.stem_conv.desc(N, H, Ws)
+            ws["y0"] = act(N, d0.OH, d0.OW, 64)
         ws["a0"] = act(N, d0.OH, d0.OW, 64)
         PH, PW = (d0.OH - 1) // 2 + 1, (d0.OW - 1) // 2 + 1
         ws["p0"] = act(N, PH, PW, 64)
         ws["p0_idx"] = torch.empty(N, PH, PW, 64, dtype=torch.uint8, device=dev)
-        max_act = max(ws["y0"].numel(), ws["x8"].numel())
-        max_stats = lib.icamd_conv2d_stats_rows(ctypes.byref(d0)) * 2 * 64
-        max_wg = self._wgrad_workspace_bytes(self.stem_conv, d0)
-        max_bnb = lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, 64)
+        if not self.deep:
+            max_act = max(ws["y0"].numel(), ws["x8"].numel())
+            max_stats = lib.icamd_conv2d_stats_rows(ctypes.byref(d0)) * 2 * 64
+            max_wg = self._wgrad_workspace_bytes(self.stem_conv, d0)
+            max_bnb = lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, 64)
         h, w = PH, PW
         blocks_ws = []
         max_se = 0
@@ -595,14 +690,19 @@ class ResNet(PicklableModel):
             b["hw"] = [(d.IH, d.IW) for _, d in launches]     # input size of each convolution
             b["mask"] = torch.empty(acts[-1].numel() // 8, dtype=torch.uint8, device=dev)   # ReLU mask of the block output
             if "down_conv" in blk:
-                dd = blk["down_conv"].desc(N, h, w)
+                sh_, sw_ = h, w
+                if blk.get("pool"):
+                    sh_, sw_ = (h + 1) // 2, (w + 1) // 2
+                    b["xp"] = act(N, sh_, sw_, blk["down_conv"].cin_p)     # pooled block input: what the shortcut convolution reads
+                b["short_hw"] = (sh_, sw_)
+                dd = blk["down_conv"].desc(N, sh_, sw_)
                 b["yd"] = act(N, dd.OH, dd.OW, blk["down_conv"].cout_p)
                 b["ad"] = act(N, dd.OH, dd.OW, blk["down_conv"].cout_p)
                 launches.append((blk["down_conv"], dd))
             for conv, d in launches:      # every convolution of the block, shortcut included
                 if conv.groups > 1 and not lib.icamd_gconv3x3_supported(ctypes.byref(d), conv.groups):
                     raise hip.IcamdError(f"{conv.name}: no grouped 3x3 kernel for {d.key()} with {conv.groups} groups")
-                max_stats = max(max_stats, lib.icamd_conv2d_stats_rows(ctypes.byref(d)) * 2 * conv.cout_p)
+                max_stats = max(max_stats, self._stats_rows(conv, d) * 2 * conv.cout_p)
                 max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d))
                 max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d.OH * d.OW, conv.cout_p))
             if "se" in blk:
@@ -652,6 +752,13 @@ class ResNet(PicklableModel):
             ws["gbuf"] = [torch.empty(n, dtype=torch.bfloat16, device=self.device) for _ in range(8)]
         return ws["gbuf"]
 
+    def _grad_view(self, ws, ptr, like):
+        """The scratch buffer of _grad_buffers that starts at `ptr`, viewed with the shape of the activation `like`."""
+        for buf in ws["gbuf"]:
+            if buf.data_ptr() == ptr:
+                return buf[:like.numel()].view(like.shape)
+        raise KeyError(ptr)
+
     # ------------------------------------------------------------------ primitive wrappers
     def _w(self, conv):
         return self.shadow.data_ptr() + 2 * conv.w.offset
@@ -672,12 +779,34 @@ class ResNet(PicklableModel):
         return st, st + 4 * c, st + 8 * c, st + 12 * c
 
     # The stem / grouped / dense dispatch on a convolution, once per kind of launch.  `d` is conv.desc(...) of the input shape.
+    def _thin(self, conv, d, op):
+        """Does `op` ("fwd", "dgrad", "wgrad") of this convolution run on the thin 3x3 kernels?"""
+        return conv.thin and _STEM_THIN[op] and bool(self.lib.icamd_conv3x3_thin_supported(ctypes.byref(d)))
+
+    def _stats_rows(self, conv, d):
+        """Rows of the BatchNorm partial sums the forward of `conv` writes."""
+        if self._thin(conv, d, "fwd"):
+            return self.lib.icamd_conv3x3_thin_stats_rows(ctypes.byref(d))
+        return self.lib.icamd_conv2d_stats_rows(ctypes.byref(d))
+
+    def _shortcut_input(self, blk, b, x, N, h, w, s):
+        """What a projection shortcut's convolution reads, with its size: the block input, or (D variants, stride-2 blocks) its
+        2x2 average into b["xp"]."""
+        if not blk.get("pool"):
+            return x, h, w
+        hip.check(self.lib.icamd_avgpool2x2_fwd(x.data_ptr(), b["xp"].data_ptr(), N, h, w, blk["down_conv"].cin_p, s),
+                  blk["name"] + " shortcut pool")
+        return (b["xp"],) + b["short_hw"]
+
     def _conv_fwd(self, conv, d, x, w, y, s, stats=None, shift=None, residual=None, relu=0):
         """y = conv(x) with filters `w`.  Training form (shift None): the raw output, BatchNorm statistic rows to `stats`.  Folded
         eval form: + shift (+ residual) (+ ReLU) in the epilogue."""
         lib = self.lib
-        if conv is self.stem_conv:
+        if conv.stem7:
             rc = lib.icamd_stem7x7s2_fwd(x, w, y, shift, stats, relu, d.N, d.IH, d.IW, conv.cout_p, s)
+        elif self._thin(conv, d, "fwd"):
+            assert residual is None
+            rc = lib.icamd_conv3x3_thin_fwd(ctypes.byref(d), x, w, y, shift, stats, relu, s)
         elif conv.groups > 1 and shift is None:
             rc = lib.icamd_gconv3x3_fwd(ctypes.byref(d), conv.groups, x, w, y, stats, s)
         elif conv.groups > 1:
@@ -691,16 +820,20 @@ class ResNet(PicklableModel):
 
     def _wgrad_workspace_bytes(self, conv, d):
         lib = self.lib
-        if conv is self.stem_conv:
+        if conv.stem7:
             return lib.icamd_stem7x7s2_wgrad_workspace_bytes(d.N, d.IH, d.IW, conv.cout_p)
+        if self._thin(conv, d, "wgrad"):
+            return lib.icamd_conv3x3_thin_wgrad_workspace_bytes(ctypes.byref(d))
         if conv.groups > 1:
             return lib.icamd_gconv3x3_wgrad_workspace_bytes(ctypes.byref(d), conv.groups)
         return lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(d))
 
     def _wgrad(self, conv, d, x, dy, acc, wsp, wsb, s):
         lib = self.lib
-        if conv is self.stem_conv:
+        if conv.stem7:
             rc = lib.icamd_stem7x7s2_wgrad(x, dy, self._gf(conv.w), acc, wsp, wsb, d.N, d.IH, d.IW, conv.cout_p, s)
+        elif self._thin(conv, d, "wgrad"):
+            rc = lib.icamd_conv3x3_thin_wgrad(ctypes.byref(d), x, dy, self._gf(conv.w), acc, wsp, wsb, s)
         elif conv.groups > 1:
             rc = lib.icamd_gconv3x3_wgrad(ctypes.byref(d), conv.groups, x, dy, self._gf(conv.w), acc, wsp, wsb, s)
         else:
@@ -709,7 +842,10 @@ class ResNet(PicklableModel):
 
     def _dgrad(self, conv, d, dy, dx, addend, addend_bits, s):
         """dx = data gradient of conv (+ addend, where the 1-bit mask `addend_bits` is set when given)."""
-        if conv.groups > 1:
+        if self._thin(conv, d, "dgrad"):
+            assert addend is None
+            rc = self.lib.icamd_conv3x3_thin_dgrad(ctypes.byref(d), dy, self._w(conv), dx, s)
+        elif conv.groups > 1:
             assert addend is None
             rc = self.lib.icamd_gconv3x3_dgrad(ctypes.byref(d), conv.groups, dy, self._w(conv), dx, s)
         else:
@@ -730,7 +866,7 @@ class ResNet(PicklableModel):
         rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
         if self.training:
             mean, invstd, scale, shift = self._stats(bn)
-            rows = lib.icamd_conv2d_stats_rows(ctypes.byref(d))
+            rows = self._stats_rows(conv, d)
             hip.check(lib.icamd_bn_train_finalize(stats, rows, c, float(N * d.OH * d.OW), self._pf(bn.weight),
                                                   self._pf(bn.bias), rm, rm + 4 * c, BN_MOMENTUM, BN_EPS, mean, invstd,
                                                   scale, shift, ws["bn_ws"].data_ptr(), s), bn.name)
@@ -768,6 +904,10 @@ class ResNet(PicklableModel):
         N, C, H, W = x_nchw.shape
         ws = self._workspace(N, H, W)
         mode, lam, box = (0, 1.0, (0, 0, 0, 0)) if mix is None else mix
+        if self.deep:      # the deep stem's first convolution reads the plain 8-channel packed image
+            hip.check(self.lib.icamd_pack_input(x_nchw.data_ptr(), ws["x8"].data_ptr(), N, C, H, W, mode, float(lam),
+                                                int(box[0]), int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
+            return ws
         hip.check(self.lib.icamd_pack_input_rgb4(x_nchw.data_ptr(), ws["x8"].data_ptr(), N, C, H, W, mode, float(lam),
                                                  int(box[0]), int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
         return ws
@@ -782,8 +922,19 @@ class ResNet(PicklableModel):
             self.num_batches_tracked += 1
         # stem: conv -> BatchNorm + ReLU + max-pool in one pass over the conv output (the 112x112 activation is never
         # stored: backward recomputes the ReLU mask from y0 and the pooling argmax is recorded)
-        d0, sc0, sh0 = self._conv_bn_fwd(ws, self.stem_conv, self.stem_bn, ws["x8"].data_ptr(), N, H, W, ws["y0"], None, None,
-                                         True, s)
+        if self.deep:
+            # deep stem: conv -> statistics -> finalize -> BatchNorm + ReLU twice, then the third convolution into the same fused
+            # BatchNorm + ReLU + max-pool pass as the plain stem
+            sh_, sw_ = H, W
+            for i, (conv, bn) in enumerate(self.stem_pairs[:-1]):
+                d0 = self._conv_bn_fwd(ws, conv, bn, ws["stem_in"][i].data_ptr(), N, sh_, sw_, ws["stem_y"][i], ws["stem_a"][i],
+                                       None, True, s)
+                sh_, sw_ = d0.OH, d0.OW
+            d0, sc0, sh0 = self._conv_bn_fwd(ws, self.stem_pairs[-1][0], self.stem_bn, ws["stem_in"][-1].data_ptr(), N, sh_, sw_,
+                                             ws["y0"], None, None, True, s)
+        else:
+            d0, sc0, sh0 = self._conv_bn_fwd(ws, self.stem_conv, self.stem_bn, ws["x8"].data_ptr(), N, H, W, ws["y0"], None,
+                                             None, True, s)
         hip.check(lib.icamd_bn_relu_maxpool3x3s2_fwd(ws["y0"].data_ptr(), sc0, sh0, ws["p0"].data_ptr(),
                                                      ws["p0_idx"].data_ptr() if self.training else None, N, d0.OH, d0.OW, 64,
                                                      s), "stem bn+relu+maxpool")
@@ -818,11 +969,13 @@ class ResNet(PicklableModel):
             if "down_conv" in blk and self.training:
                 # shortcut conv + statistics only: its BatchNorm is applied inside the block's last BatchNorm pass, the
                 # normalised shortcut is never stored (backward needs yd and the block mask, not it)
-                _, scd, shd = self._conv_bn_fwd(ws, blk["down_conv"], blk["down_bn"], x.data_ptr(), N, h, w, b["yd"], None,
+                xs, sh_, sw_ = self._shortcut_input(blk, b, x, N, h, w, s)
+                _, scd, shd = self._conv_bn_fwd(ws, blk["down_conv"], blk["down_bn"], xs.data_ptr(), N, sh_, sw_, b["yd"], None,
                                                 None, False, s)
                 idn, res_bn = b["yd"], (scd, shd)
             elif "down_conv" in blk:
-                self._conv_bn_fwd(ws, blk["down_conv"], blk["down_bn"], x.data_ptr(), N, h, w, b["yd"], b["ad"], None,
+                xs, sh_, sw_ = self._shortcut_input(blk, b, x, N, h, w, s)
+                self._conv_bn_fwd(ws, blk["down_conv"], blk["down_bn"], xs.data_ptr(), N, sh_, sw_, b["yd"], b["ad"], None,
                                   False, s)
                 idn = b["ad"]
             else:
@@ -882,6 +1035,8 @@ class ResNet(PicklableModel):
         if _FUSED_BNBWD:
             if self.se:
                 raise hip.IcamdError("ICAMD_FUSED_BNBWD=1 has no squeeze-and-excitation backward")
+            if self.deep:
+                raise hip.IcamdError("ICAMD_FUSED_BNBWD=1 has no average-pool shortcut backward")
             return self._backward_packed_fused(ws, accumulate)
         run = self._backward_begin(ws, accumulate, _WGRAD_STREAM and self.wgrad_side_stream)
         bufs = self._grad_buffers(ws)
@@ -993,10 +1148,11 @@ class ResNet(PicklableModel):
                 # the shortcut's BatchNorm takes the same g -- its convolution + BatchNorm fused as well where it is a 1x1 /
                 # stride-1 layer of a routed shape (layer1.0), else its BatchNorm backward alone (no mask: g is masked already)
                 dc = blk["down_conv"]
-                ddc = dc.desc(N, *b["in_hw"])
+                ddc = dc.desc(N, *b.get("short_hw", b["in_hw"]))
                 if dc.stride == 1 and lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(ddc)):
-                    self._fused_conv_bn(run, dc, blk["down_bn"], ddc, None, 0, dout, b["yd"], b["in"].data_ptr(), run.T, run.bws,
-                                        run.bwb)
+                    # (run.T: on the pooled grid where the shortcut starts with the average pool)
+                    self._fused_conv_bn(run, dc, blk["down_bn"], ddc, None, 0, dout, b["yd"], b.get("xp", b["in"]).data_ptr(),
+                                        run.T, run.bws, run.bwb)
                     shortcut_done = True
                 else:
                     dy2 = self._next_y(run)
@@ -1066,6 +1222,22 @@ class ResNet(PicklableModel):
         xin = b["in"].data_ptr()
         d1 = conv1.desc(N, h, w)
         self._side_wgrad(run, conv1, d1, xin, dy)
+        if blk.get("pool"):
+            # D variant, stride-2 block: the shortcut convolution lives on the pooled grid.  Its weight gradient reads the pooled
+            # input, its data gradient is a plain pointwise one there (run.T), and the average pool's backward spreads that over the
+            # 1, 2 or 4 pixels of each window ON TOP of the main branch's data gradient (run.DA is free here), which finishes the
+            # block-input gradient.  No even-grid / BatchNorm-reduce fusion: their addend would have to be the spread gradient.
+            dc = blk["down_conv"]
+            ddc = dc.desc(N, *b["short_hw"])
+            if not shortcut_done:
+                if dy2 is None:
+                    dy2 = self._next_y(run)
+                    self._bn_bwd(run, blk["down_bn"], dout, None, b["yd"], dy2, None, True, b["mask"].data_ptr())
+                self._side_wgrad(run, dc, ddc, b["xp"].data_ptr(), dy2)
+                self._dgrad(dc, ddc, dy2, run.T, None, None, s)
+            self._dgrad(conv1, d1, dy, run.DA, None, None, s)
+            hip.check(lib.icamd_avgpool2x2_bwd(run.T, run.DA, other, N, h, w, dc.cin_p, s), blk["name"] + " shortcut pool bwd")
+            return 0
         if shortcut_done:
             self._dgrad(conv1, d1, dy, other, run.T, None, s)
             return 0
@@ -1110,7 +1282,8 @@ class ResNet(PicklableModel):
     def _bwd_stem(self, run, dout, dy, fused_pool):
         """maxpool -> BN+ReLU -> conv (no data gradient for the image); dy: buffer for the stem convolution's output gradient."""
         lib, ws, N, s = self.lib, run.ws, run.N, run.s
-        d0 = self.stem_conv.desc(N, ws["H"], ws["Ws"])
+        last = self.stem_pairs[-1][0]
+        d0 = last.desc(N, *ws["stem_hw"][-1]) if self.deep else last.desc(N, ws["H"], ws["Ws"])
         bn0 = self.stem_bn
         if fused_pool:
             # max-pool backward folded into both BatchNorm-backward passes: the 112x112 gradient is never materialised
@@ -1121,7 +1294,30 @@ class ResNet(PicklableModel):
         else:
             hip.check(lib.icamd_maxpool3x3s2_bwd(dout, ws["p0_idx"].data_ptr(), run.DA, N, d0.OH, d0.OW, 64, s), "maxpool bwd")
             self._bn_bwd(run, bn0, run.DA, None, ws["y0"], dy, None, True)
-        self._side_wgrad(run, self.stem_conv, d0, ws["x8"].data_ptr(), dy)
+        if not self.deep:
+            self._side_wgrad(run, self.stem_conv, d0, ws["x8"].data_ptr(), dy)
+            return
+        # deep stem, last convolution to first: weight gradient (side lane) + data gradient, then the BatchNorm + ReLU in front
+        # (mask recomputed from y); the first convolution reads the image: weight gradient only.  The two data gradients go to
+        # different scratch buffers (run.DA, run.T) and ws["stem_dy"][i] / ws["stem_dx"][i] name the gradient of the i-th
+        # convolution's output / input, so that all of them can be read back after the pass (tests/test_resnet_d_gpu.py)
+        name_views = "stem_dy" not in ws      # once per workspace: the scratch buffers rotate the same way in every pass
+        if name_views:
+            ws["stem_dy"], ws["stem_dx"] = [None] * len(self.stem_pairs), [None] * len(self.stem_pairs)
+        for i in range(len(self.stem_pairs) - 1, -1, -1):
+            conv = self.stem_pairs[i][0]
+            d = conv.desc(N, *ws["stem_hw"][i])
+            if name_views:
+                ws["stem_dy"][i] = self._grad_view(ws, dy, ws["stem_y"][i])
+            self._side_wgrad(run, conv, d, ws["stem_in"][i].data_ptr(), dy)
+            if i == 0:
+                break
+            dx = run.DA if i == len(self.stem_pairs) - 1 else run.T
+            if name_views:
+                ws["stem_dx"][i] = self._grad_view(ws, dx, ws["stem_in"][i])
+            self._dgrad(conv, d, dy, dx, None, None, s)
+            dy = self._next_y(run)
+            self._bn_bwd(run, self.stem_pairs[i - 1][1], dx, None, ws["stem_y"][i - 1], dy, None, True)
 
     def _backward_packed_fused(self, ws, accumulate=False):
         """Variant that fuses each BatchNorm backward's mask + reduction pass into the epilogue of the data-gradient

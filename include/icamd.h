@@ -377,6 +377,32 @@ int icamd_maxpool3x3s2_bwd(const void* dout, const uint8_t* argmax, void* dx, in
 int icamd_avgpool_fwd(const void* x, void* out, int N, int HW, int C, void* stream);
 int icamd_avgpool_bwd(const void* dout, void* dx, int N, int HW, int C, void* stream);
 
+/* ---- ResNet-D (timm resnet50d and siblings: stem_type='deep', avg_down=True) ------------------------------------
+ * 2x2 / stride 2 average pool in front of a projection shortcut: nn.AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False).
+ * x, addend, dx: NHWC bf16 [N][IH][IW][C]; out, dout: [N][ceil(IH/2)][ceil(IW/2)][C]; C % 8 == 0 and N*IH*IW*C/8 < 2^31, else
+ * ICAMD_ERR_BAD_ARG (nothing is written).  A window that hangs over the edge averages the 1 or 2 elements it has.
+ * fwd: fp32 sum, one rounding.  bwd: dx = addend + dout[oh][ow] / count(oh, ow) at every pixel of each window, fp32, one rounding;
+ * addend (optional) is the main branch's gradient of the block input, so the block-input gradient is finished in this pass. */
+int icamd_avgpool2x2_fwd(const void* x, void* out, int N, int IH, int IW, int C, void* stream);
+int icamd_avgpool2x2_bwd(const void* dout, const void* addend, void* dx, int N, int IH, int IW, int C, void* stream);
+
+/* Thin 3x3 convolution of the deep stem: KH = KW = 3, pad 1, stride 1, Cin == 32, Cout in {32, 64}; any N, IH, IW with
+ * N*IH*IW < 2^30 whose staged tile fits the LDS (64 + 2 IW + 3 rows of up to 128 B in 64 KB: image widths up to ~220 pixels at
+ * Cout 64, ~480 at Cout 32).  Everything else: _supported returns 0, the launches ICAMD_ERR_UNSUPPORTED (nothing is written).
+ * The filter is bf16 [Cout][3][3][32] for EVERY entry: the data gradient re-indexes the forward layout itself.
+ * fwd: y = [relu](conv(x, w) (+ bias[co])), one rounding; stats (optional): float [_stats_rows(d)][2][Cout], partial sum / sum of
+ * squares of the ROUNDED y, consumed by icamd_bn_train_finalize with nrows = _stats_rows(d).
+ * wgrad: dw fp32 [Cout][3][3][32] = (accumulate ? dw : 0) + sum over pixels; fp32 partial slabs in the workspace, folded in a
+ * fixed order.  Every output is bitwise repeatable. */
+int icamd_conv3x3_thin_supported(const icamd_conv_desc* d);
+int icamd_conv3x3_thin_stats_rows(const icamd_conv_desc* d);
+int icamd_conv3x3_thin_fwd(const icamd_conv_desc* d, const void* x, const void* w, void* y, const float* bias, float* stats, int relu,
+                           void* stream);
+int icamd_conv3x3_thin_dgrad(const icamd_conv_desc* d, const void* dy, const void* w, void* dx, void* stream);
+size_t icamd_conv3x3_thin_wgrad_workspace_bytes(const icamd_conv_desc* d);
+int icamd_conv3x3_thin_wgrad(const icamd_conv_desc* d, const void* x, const void* dy, float* dw, int accumulate, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- input packing + mixup/cutmix (replaces samples.to(device) + timm Mixup.__call__, engine.py:40-44) -- */
 /* x: fp32 NCHW [B,Cin,H,W] (device) -> out: bf16 NHWC [B,H,W,8]; mode 0 none, 1 mixup(lam), 2 cutmix(box) */
 int icamd_pack_input(const float* x, void* out, int B, int Cin, int H, int W, int mode, float lam, int yl, int yh,

@@ -1,0 +1,146 @@
+"""The ResNet-D variants (resnet18d/34d/26d/50d/101d/152d/200d, seresnet152d, seresnext26d_32x4d), the parts that need no GPU:
+the tests-side reference has the expected parameter counts and timm's key order, the product's ARCHS rows describe the same
+graph, block_specs marks the pooled shortcuts, the 14 older names are unchanged, and the new ABI entries are declared."""
+import os
+import sys
+
+import pytest
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from _resnext_ref import FAMILY, ResNetFamilyRef  # noqa: E402
+from _seresnet_ref import SE_FAMILY, SEResNetRef  # noqa: E402
+from _resnetd_ref import D_FAMILY, ResNetDRef  # noqa: E402
+
+# the plain sibling's count + 19 232 (deep stem 28 768 against the 7x7 stem's 9 536)
+COUNTS = {
+    "resnet18d": 11708744,
+    "resnet34d": 21816904,
+    "resnet26d": 16014408,
+    "resnet50d": 25576264,
+    "resnet101d": 44568392,
+    "resnet152d": 60212040,
+    "resnet200d": 64693064,
+    "seresnet152d": 66841080,
+    "seresnext26d_32x4d": 16809512,
+}
+D_SYMBOLS = ("icamd_avgpool2x2_fwd", "icamd_avgpool2x2_bwd", "icamd_conv3x3_thin_supported", "icamd_conv3x3_thin_stats_rows",
+             "icamd_conv3x3_thin_fwd", "icamd_conv3x3_thin_dgrad", "icamd_conv3x3_thin_wgrad_workspace_bytes",
+             "icamd_conv3x3_thin_wgrad")
+
+
+def _named_shapes(model):
+    return [(n, tuple(p.shape)) for n, p in model.named_parameters()]
+
+
+@pytest.mark.parametrize("arch", sorted(COUNTS))
+def test_reference_parameter_counts(arch):
+    ref = ResNetDRef(arch, 1000)
+    assert sum(p.numel() for p in ref.parameters()) == COUNTS[arch]
+
+
+def test_reference_key_names_and_order():
+    sd = ResNetDRef("resnet50d", 10).state_dict()
+    keys = list(sd)
+    assert keys[:3] == ["conv1.0.weight", "conv1.1.weight", "conv1.1.bias"]
+    i = keys.index("conv1.4.num_batches_tracked")
+    assert keys[i + 1:i + 3] == ["conv1.6.weight", "bn1.weight"]
+    assert tuple(sd["conv1.0.weight"].shape) == (32, 3, 3, 3)
+    assert tuple(sd["conv1.3.weight"].shape) == (32, 32, 3, 3)
+    assert tuple(sd["conv1.6.weight"].shape) == (64, 32, 3, 3)
+    i = keys.index("layer1.0.bn3.num_batches_tracked")
+    assert keys[i + 1:i + 3] == ["layer1.0.downsample.1.weight", "layer1.0.downsample.2.weight"]
+    assert tuple(sd["layer2.0.downsample.1.weight"].shape) == (512, 256, 1, 1)
+    ref = ResNetDRef("seresnext26d_32x4d", 10)
+    keys = list(ref.state_dict())
+    i = keys.index("layer2.0.se.fc2.bias")
+    assert keys[i + 1] == "layer2.0.downsample.1.weight"
+    assert isinstance(ref.layer1[0].downsample[0], nn.Identity)
+    pool = ref.layer2[0].downsample[0]
+    assert isinstance(pool, nn.AvgPool2d) and pool.ceil_mode and not pool.count_include_pad
+    assert ref.layer2[0].downsample[1].stride == (1, 1)
+
+
+def test_reference_forward_backward_and_double_copy():
+    import copy
+    torch.manual_seed(0)
+    ref = ResNetDRef("resnet26d", 10, bf16_points=True)
+    x = torch.randn(2, 3, 40, 40)      # odd sizes downstream: 20 -> 10 -> 5 -> 3 -> 2
+    tr = {}
+    ref.set_trace(tr)
+    out = ref(x)
+    out.sum().backward()
+    assert out.shape == (2, 10) and torch.isfinite(out).all()
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in ref.parameters())
+    assert tr["stem_y0"].shape == (2, 32, 20, 20) and tr["y0"].shape == (2, 64, 20, 20)
+    assert tr["layer3.0.down.x"].shape == (2, 512, 3, 3) and "layer1.0.down.x" not in tr
+    d = copy.deepcopy(ref).double()
+    d.set_trace({})
+    assert float((d(x.double()).detach() - out.detach().double()).abs().max()) < 0.1
+
+
+@pytest.mark.parametrize("arch", sorted(COUNTS))
+def test_product_archs_describe_the_same_graph(arch):
+    from imageclassification_amd import nets
+    assert arch in nets.ARCHS and nets.is_d(arch)
+    assert nets.param_shapes(arch, 1000) == _named_shapes(ResNetDRef(arch, 1000))
+    assert sum(torch.Size(s).numel() for _, s in nets.param_shapes(arch, 1000)) == COUNTS[arch]
+    kind, layers, cardinality, base_width, se = D_FAMILY[arch]
+    assert tuple(nets.ARCHS[arch][:4]) == (kind, layers, cardinality, base_width)
+    specs = nets.block_specs(arch)
+    for blk in specs:
+        li, bi = blk["name"].split(".")
+        first = bi == "0"
+        if first and li != "layer1":
+            # stride-2 first block: pooled projection shortcut, 1x1 / stride 1 under downsample.1 / .2
+            assert blk["stride"] == 2 and blk["pool"] is True
+            assert blk["down"][0][0] == blk["name"] + ".downsample.1" and blk["down"][0][3:6] == (1, 1, 0)
+            assert blk["down"][1][0] == blk["name"] + ".downsample.2"
+        elif first and kind == "bottleneck":
+            # layer1.0: projection without a pool
+            assert blk["pool"] is False and blk["down"] is not None and blk["down"][0][3:6] == (1, 1, 0)
+            assert blk["down"][0][0] == "layer1.0.downsample.1"
+        else:
+            # a plain block (layer1.0 of the basic archs included)
+            assert blk["pool"] is False and blk["down"] is None
+    groups = {c[0]: c[6] for blk in specs for c in blk["convs"]}
+    assert all(g == (cardinality if n.endswith(".conv2") and kind == "bottleneck" else 1) for n, g in groups.items())
+
+
+def test_has_se_and_is_d_for_all_23_names():
+    from imageclassification_amd import nets
+    assert len(nets.ARCHS) == 23
+    assert set(nets.ARCHS) == set(FAMILY) | set(SE_FAMILY) | set(D_FAMILY)
+    for arch in nets.ARCHS:
+        se = arch in SE_FAMILY or (arch in D_FAMILY and D_FAMILY[arch][4])
+        assert nets.has_se(arch) == se, arch
+        assert nets.is_d(arch) == (arch in D_FAMILY), arch
+        assert all((blk["se"] is not None) == se for blk in nets.block_specs(arch))
+
+
+@pytest.mark.parametrize("arch", sorted(FAMILY) + sorted(SE_FAMILY))
+def test_existing_names_unchanged(arch):
+    from imageclassification_amd import nets
+    ref = SEResNetRef(arch, 1000) if arch in SE_FAMILY else ResNetFamilyRef(arch, 1000)
+    assert nets.param_shapes(arch, 1000) == _named_shapes(ref)
+    assert len(nets.ARCHS[arch]) <= 5
+    for blk in nets.block_specs(arch):
+        assert set(blk) == {"name", "stride", "convs", "bns", "down", "se"}
+        if blk["down"] is not None:
+            assert blk["down"][0][0].endswith(".downsample.0") and blk["down"][0][4] == blk["stride"]
+    assert nets.stem_specs(arch) == [(("conv1", 3, 64, 7, 2, 3, 1), ("bn1", 64))]
+
+
+def test_abi_declares_the_new_entries_and_keeps_its_version():
+    from imageclassification_amd import hip
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(here, "include", "icamd.h")).read()
+    for sym in D_SYMBOLS:
+        assert sym in hip.EXPORTED_SYMBOLS
+        assert sym + "(" in header
+    assert hip.ABI_VERSION == 6
+    unit = open(os.path.join(here, "imageclassification_amd", "csrc", "conv_stem_deep.hip")).read()
+    assert "atomicAdd" not in unit
+    assert "conv_stem_deep" in open(os.path.join(here, "imageclassification_amd", "csrc", "build.sh")).read()
