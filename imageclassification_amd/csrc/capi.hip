@@ -32,6 +32,23 @@ int icamd_bn_bwd_finalize_launch(const float* part, int nrows, const float* mean
                                  long long rows, int C, int accumulate, double* chunks, float* c1c2, hipStream_t s, int sums_are_gy);
 int icamd_bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* mean, const float* invstd, float* part, long long rows,
                                int C, int* nblk_out, hipStream_t s);
+// Swin: window attention, relative-position bias, patch merging (window_attention.hip)
+bool icamd_window_attention_ok(int Hs, int Ws, int ws, int D);
+int icamd_window_attention_bwd_chunks(long long nwin, int H);
+int icamd_window_attention_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
+                                      int ws, int shift, float scale, hipStream_t s);
+int icamd_window_attention_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout, const float* lse,
+                                      bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs, int Ws, int H, int ws,
+                                      int shift, float scale, hipStream_t s);
+int icamd_relpos_bias_gather_launch(const float* table, float* bias, int H, int ws, hipStream_t s);
+int icamd_relpos_bias_scatter_launch(const float* dbias, float* dtable, int H, int ws, int accumulate, hipStream_t s);
+bool icamd_patch_merge_ln_ok(int N, int H, int W, int C);
+int icamd_patch_merge_ln_bwd_blocks(long long rows);
+int icamd_patch_merge_ln_fwd_launch(const bf16_t* x, const float* gamma, const float* beta, bf16_t* y, float* mean, float* rstd,
+                                    int N, int H, int W, int C, float eps, hipStream_t s);
+int icamd_patch_merge_ln_bwd_launch(const bf16_t* dy, const bf16_t* x, const float* mean, const float* rstd, const float* gamma,
+                                    bf16_t* dx, float* dgamma, float* dbeta, int N, int H, int W, int C, int accumulate, float* part,
+                                    hipStream_t s);
 int icamd_maxpool_fwd_launch(const bf16_t* x, bf16_t* out, unsigned char* idx, int N, int IH, int IW, int C, int OH, int OW,
                              hipStream_t s);
 int icamd_bn_relu_maxpool_fwd_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out, unsigned char* idx,
@@ -1306,6 +1323,87 @@ int icamd_attention_bwd(const void* qkv, const void* out, const void* dout, cons
   if (D != 64) return ICAMD_ERR_UNSUPPORTED;
   return icamd_attention_bwd_launch((const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B,
                                     T, H, scale, (hipStream_t)stream);
+}
+
+// ---- Swin: window attention, relative-position bias, patch merging (window_attention.hip) ---------------------------
+int icamd_window_attention_supported(int Hs, int Ws, int ws, int D) { return icamd_window_attention_ok(Hs, Ws, ws, D) ? 1 : 0; }
+
+int icamd_window_attention_fwd(const void* qkv, const float* bias, void* out, float* lse, int B, int Hs, int Ws, int H, int D,
+                               int ws, int shift, float scale, void* stream) {
+  ProfScope _prof(PC_ATTN_FWD, stream);
+  _prof.work(8.0 * B * Hs * Ws * H * D, 4.0 * B * Hs * Ws * H * (double)ws * ws * D);
+  if (qkv == nullptr || bias == nullptr || out == nullptr || lse == nullptr || B <= 0 || H <= 0) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_window_attention_ok(Hs, Ws, ws, D) || shift < 0 || shift >= ws || (long long)B * Hs * Ws >= (1ll << 31))
+    return ICAMD_ERR_UNSUPPORTED;
+  return icamd_window_attention_fwd_launch((const bf16_t*)qkv, bias, (bf16_t*)out, lse, B, Hs, Ws, H, ws, shift, scale,
+                                           (hipStream_t)stream);
+}
+
+size_t icamd_window_attention_bwd_workspace_bytes(int B, int Hs, int Ws, int H, int ws) {
+  if (B <= 0 || H <= 0 || !icamd_window_attention_ok(Hs, Ws, ws, 32)) return 0;
+  const long long nwin = (long long)B * (Hs / ws) * (Ws / ws);
+  return align_up((size_t)icamd_window_attention_bwd_chunks(nwin, H) * H * ws * ws * ws * ws * sizeof(float), 256);
+}
+
+int icamd_window_attention_bwd(const void* qkv, const float* bias, const void* out, const void* dout, const float* lse,
+                               void* dqkv, float* dbias, int accumulate, void* workspace, size_t workspace_bytes, int B, int Hs,
+                               int Ws, int H, int D, int ws, int shift, float scale, void* stream) {
+  ProfScope _prof(PC_ATTN_BWD, stream);
+  _prof.work(18.0 * B * Hs * Ws * H * D, 14.0 * B * Hs * Ws * H * (double)ws * ws * D);
+  if (qkv == nullptr || bias == nullptr || out == nullptr || dout == nullptr || lse == nullptr || dqkv == nullptr ||
+      dbias == nullptr || B <= 0 || H <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_window_attention_ok(Hs, Ws, ws, D) || shift < 0 || shift >= ws || (long long)B * Hs * Ws >= (1ll << 31))
+    return ICAMD_ERR_UNSUPPORTED;
+  if (workspace == nullptr || workspace_bytes < icamd_window_attention_bwd_workspace_bytes(B, Hs, Ws, H, ws))
+    return ICAMD_ERR_WORKSPACE;
+  return icamd_window_attention_bwd_launch((const bf16_t*)qkv, bias, (const bf16_t*)out, (const bf16_t*)dout, lse, (bf16_t*)dqkv,
+                                           dbias, accumulate, (float*)workspace, B, Hs, Ws, H, ws, shift, scale,
+                                           (hipStream_t)stream);
+}
+
+int icamd_relpos_bias_gather(const float* table, float* bias, int H, int ws, void* stream) {
+  ProfScope _prof(PC_MISC, stream);
+  if (table == nullptr || bias == nullptr || H <= 0) return ICAMD_ERR_BAD_ARG;
+  if (ws < 2 || ws > 8) return ICAMD_ERR_UNSUPPORTED;
+  return icamd_relpos_bias_gather_launch(table, bias, H, ws, (hipStream_t)stream);
+}
+
+int icamd_relpos_bias_scatter(const float* dbias, float* dtable, int H, int ws, int accumulate, void* stream) {
+  ProfScope _prof(PC_MISC, stream);
+  if (dbias == nullptr || dtable == nullptr || H <= 0) return ICAMD_ERR_BAD_ARG;
+  if (ws < 2 || ws > 8) return ICAMD_ERR_UNSUPPORTED;
+  return icamd_relpos_bias_scatter_launch(dbias, dtable, H, ws, accumulate, (hipStream_t)stream);
+}
+
+int icamd_patch_merge_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int N, int H,
+                             int W, int C, float eps, void* stream) {
+  ProfScope _prof(PC_LN_FWD, stream);
+  _prof.work(4.0 * N * H * W * C + 2.0 * N * H * W);
+  if (x == nullptr || gamma == nullptr || beta == nullptr || y == nullptr || mean == nullptr || rstd == nullptr)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_patch_merge_ln_ok(N, H, W, C)) return ICAMD_ERR_UNSUPPORTED;
+  return icamd_patch_merge_ln_fwd_launch((const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, N, H, W, C, eps,
+                                         (hipStream_t)stream);
+}
+
+size_t icamd_patch_merge_ln_bwd_workspace_bytes(int N, int H, int W, int C) {
+  if (!icamd_patch_merge_ln_ok(N, H, W, C)) return 0;
+  return align_up((size_t)icamd_patch_merge_ln_bwd_blocks((long long)N * (H / 2) * (W / 2)) * 8 * C * sizeof(float), 256);
+}
+
+int icamd_patch_merge_ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx,
+                             float* dgamma, float* dbeta, int N, int H, int W, int C, int accumulate, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+  ProfScope _prof(PC_LN_BWD, stream);
+  _prof.work(6.0 * N * H * W * C + 2.0 * N * H * W);
+  if (dy == nullptr || x == nullptr || mean == nullptr || rstd == nullptr || gamma == nullptr || dx == nullptr ||
+      dgamma == nullptr || dbeta == nullptr)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_patch_merge_ln_ok(N, H, W, C)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace == nullptr || workspace_bytes < icamd_patch_merge_ln_bwd_workspace_bytes(N, H, W, C)) return ICAMD_ERR_WORKSPACE;
+  return icamd_patch_merge_ln_bwd_launch((const bf16_t*)dy, (const bf16_t*)x, mean, rstd, gamma, (bf16_t*)dx, dgamma, dbeta, N, H, W,
+                                         C, accumulate, (float*)workspace, (hipStream_t)stream);
 }
 
 int icamd_maxpool3x3s2_fwd(const void* x, void* out, uint8_t* argmax, int N, int IH, int IW, int C, void* stream) {

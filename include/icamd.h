@@ -337,6 +337,44 @@ int icamd_attention_fwd(const void* qkv, void* out, float* lse, int B, int T, in
 int icamd_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                         int B, int T, int H, int D, float scale, void* stream);
 
+/* ---- Swin Transformer (timm swin_*_patch4_window7_224 under the same reference calls; csrc/window_attention.hip) --------
+ * Shifted-window attention over ws x ws windows of a [B][Hs][Ws] token grid, H heads of D = 32:
+ *   qkv  bf16 [B][Hs][Ws][3*H*D] in the NATURAL token order (q | k | v, each [head][D]: timm's reshape(B_, N, 3, heads, -1));
+ *   bias fp32 [H][ws^2][ws^2] (the gathered relative-position bias);  out bf16 [B][Hs][Ws][H*D], natural order;
+ *   lse  fp32 [B*nW][H][ws^2], nW = (Hs/ws)*(Ws/ws), window number = (image, window row, window column).
+ * scores = scale * q k^T + bias[h] + mask, softmax in fp32.  The roll by (-shift, -shift), the window partition / reverse and
+ * the roll back are address arithmetic in the kernel; for shift > 0 two tokens of a window get -100 added to their score when
+ * their region ids on the rolled grid differ (per axis the slices [0, L-ws), [L-ws, L-shift), [L-shift, L); id = 3 * row slice
+ * + column slice: timm's img_mask) -- computed from the coordinates, no mask tensor is read.
+ * _supported: 1 for D == 32, 2 <= ws <= 8, Hs % ws == 0, Ws % ws == 0; the calls also need 0 <= shift < ws.  Anything else
+ * returns ICAMD_ERR_UNSUPPORTED and writes nothing.
+ * bwd: dqkv bf16 in the layout of qkv; dbias fp32 [H][ws^2][ws^2] (+)= the sum over all images and windows of dS (the gradient
+ * of the scores after the scale, taken in fp32 before dS is rounded for its products).  workspace: _bwd_workspace_bytes, no
+ * initialisation needed (per-workgroup partials, folded in a fixed order by a second launch).  No atomics: bitwise repeatable. */
+int icamd_window_attention_supported(int Hs, int Ws, int ws, int D);
+int icamd_window_attention_fwd(const void* qkv, const float* bias, void* out, float* lse, int B, int Hs, int Ws, int H, int D,
+                               int ws, int shift, float scale, void* stream);
+size_t icamd_window_attention_bwd_workspace_bytes(int B, int Hs, int Ws, int H, int ws);
+int icamd_window_attention_bwd(const void* qkv, const float* bias, const void* out, const void* dout, const float* lse,
+                               void* dqkv, float* dbias, int accumulate, void* workspace, size_t workspace_bytes, int B, int Hs,
+                               int Ws, int H, int D, int ws, int shift, float scale, void* stream);
+/* table fp32 [(2 ws - 1)^2][H] (timm relative_position_bias_table) <-> bias fp32 [H][ws^2][ws^2]:
+ * bias[h][i][j] = table[(dr + ws - 1) * (2 ws - 1) + (dc + ws - 1)][h], (dr, dc) = coordinates of i minus coordinates of j.
+ * scatter: dtable (+)= the transpose of the gather applied to dbias, pairs summed in increasing (i, j) order.  2 <= ws <= 8. */
+int icamd_relpos_bias_gather(const float* table, float* bias, int H, int ws, void* stream);
+int icamd_relpos_bias_scatter(const float* dbias, float* dtable, int H, int ws, int accumulate, void* stream);
+/* Patch merging + LayerNorm: x bf16 [N][H][W][C] (H, W even) -> y bf16 [N*H/2*W/2][4C] = LayerNorm over 4C of the gathered row,
+ * whose channel block j = 2 * (w parity) + (h parity) is x[n][2r + hpar][2c + wpar][:] (timm's x0 | x1 | x2 | x3); mean / rstd
+ * fp32 [N*H/2*W/2] are saved.  C % 8 == 0 and 4C <= 2048, else ICAMD_ERR_UNSUPPORTED with nothing written.
+ * bwd: xhat is recomputed from x, mean, rstd; dx bf16 [N][H][W][C] (every element written once); dgamma / dbeta fp32 [4C] (+)=,
+ * reduced through per-workgroup partials in a fixed order (workspace needs no initialisation). */
+int icamd_patch_merge_ln_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int N, int H,
+                             int W, int C, float eps, void* stream);
+size_t icamd_patch_merge_ln_bwd_workspace_bytes(int N, int H, int W, int C);
+int icamd_patch_merge_ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx,
+                             float* dgamma, float* dbeta, int N, int H, int W, int C, int accumulate, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- squeeze-and-excitation tail of a bottleneck block (timm Bottleneck with attn_layer='se') ------------
  *   z = y*scale[c] + shift[c]   s = mean_hw(z)   h = relu(W1 s + b1)   e = sigmoid(W2 h + b2)   out = relu(z*e[n,c] + shortcut)
  * y, out, residual, dout, dy: NHWC bf16 [N][HW][C]; every [N,C] / [N,rd] array and all parameters and their gradients fp32

@@ -1,0 +1,202 @@
+"""The Swin Transformer family (swin_tiny / small / base _patch4_window7_224 and swin_test), the parts that need no GPU: parameter
+counts, timm's key names and order, the product's shape listing against the tests-side reference, the host-side window geometry and
+relative-position index against the way timm builds them (roll + window_partition, img_mask by slices, the index buffer), the
+command-line surface, and the declaration of the new ABI entries."""
+import os
+import sys
+
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from _swin_ref import SwinRef, relative_position_index as ref_index, shifted_window_mask, window_partition  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+COUNTS = {
+    "swin_tiny_patch4_window7_224": 28288354,
+    "swin_small_patch4_window7_224": 49606258,
+    "swin_base_patch4_window7_224": 87768224,
+}
+SIZES = {"swin_tiny_patch4_window7_224": 224, "swin_small_patch4_window7_224": 224, "swin_base_patch4_window7_224": 224,
+         "swin_test": 56}
+SWIN_SYMBOLS = ("icamd_window_attention_supported", "icamd_window_attention_fwd", "icamd_window_attention_bwd_workspace_bytes",
+                "icamd_window_attention_bwd", "icamd_relpos_bias_gather", "icamd_relpos_bias_scatter", "icamd_patch_merge_ln_fwd",
+                "icamd_patch_merge_ln_bwd_workspace_bytes", "icamd_patch_merge_ln_bwd")
+GEOMETRIES = [(14, 14, 7, 3), (14, 21, 7, 3), (7, 7, 7, 0), (8, 16, 4, 2), (16, 8, 8, 4)]
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
+@pytest.mark.parametrize("arch", sorted(COUNTS))
+def test_parameter_counts(arch):
+    from imageclassification_amd import swin
+    shapes = swin.param_shapes(arch, 1000)
+    assert sum(_numel(s) for s in shapes.values()) == COUNTS[arch]
+
+
+def test_swin_test_parameter_count():
+    """swin_test (dims 32 / 64, depths 2 / 2, heads 1 / 2, 10 classes), counted term by term"""
+    from imageclassification_amd import swin
+
+    def block(d, h):
+        return 2 * d + 169 * h + (3 * d * d + 3 * d) + (d * d + d) + 2 * d + (4 * d * d + 4 * d) + (4 * d * d + d)
+
+    want = (32 * 3 * 16 + 32) + 64 + 2 * block(32, 1) + (2 * 128 + 64 * 128) + 2 * block(64, 2) + 128 + (10 * 64 + 10)
+    shapes = swin.param_shapes("swin_test", 10, 56)
+    assert sum(_numel(s) for s in shapes.values()) == want
+    ref = SwinRef("swin_test", 10, 56)
+    assert sum(p.numel() for p in ref.parameters()) == want
+
+
+def test_key_names_and_order():
+    from imageclassification_amd import swin
+    keys = list(swin.param_shapes("swin_tiny_patch4_window7_224", 1000))
+    assert keys[:4] == ["patch_embed.proj.weight", "patch_embed.proj.bias", "patch_embed.norm.weight", "patch_embed.norm.bias"]
+    b = "layers.1.blocks.0."
+    i = keys.index(b + "norm1.weight")
+    assert keys[i:i + 13] == [b + k for k in (
+        "norm1.weight", "norm1.bias", "attn.relative_position_bias_table", "attn.qkv.weight", "attn.qkv.bias", "attn.proj.weight",
+        "attn.proj.bias", "norm2.weight", "norm2.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+    # the downsample opens its stage: right behind the last block of stage 0, in front of the first block of stage 1
+    assert keys[i - 3:i] == ["layers.1.downsample.norm.weight", "layers.1.downsample.norm.bias",
+                             "layers.1.downsample.reduction.weight"]
+    assert keys[i - 4] == "layers.0.blocks.1.mlp.fc2.bias"
+    assert not any(k.startswith("layers.0.downsample") for k in keys)
+    assert keys[-4:] == ["norm.weight", "norm.bias", "head.fc.weight", "head.fc.bias"]
+    shapes = swin.param_shapes("swin_tiny_patch4_window7_224", 1000)
+    assert shapes[b + "attn.relative_position_bias_table"] == (169, 6)
+    assert shapes["layers.1.downsample.reduction.weight"] == (192, 384)
+
+
+def test_state_holds_parameters_only():
+    from imageclassification_amd import swin
+    for arch in swin.CONFIGS:
+        keys = list(swin.param_shapes(arch, 10, SIZES[arch]))
+        assert not any("index" in k or "mask" in k for k in keys)
+    ref = SwinRef("swin_test", 10, 56)
+    assert list(ref.state_dict()) == list(swin.param_shapes("swin_test", 10, 56))     # the reference's buffers are not persistent
+
+
+@pytest.mark.parametrize("arch", sorted(SIZES))
+def test_param_shapes_equal_the_reference(arch):
+    from imageclassification_amd import swin
+    assert set(swin.CONFIGS) == set(SIZES)
+    ref = SwinRef(arch, 1000, SIZES[arch])
+    want = [(n, tuple(p.shape)) for n, p in ref.named_parameters()]
+    assert list(swin.param_shapes(arch, 1000, SIZES[arch]).items()) == want
+
+
+@pytest.mark.parametrize("Hs,Ws,ws,shift", GEOMETRIES)
+def test_window_geometry_matches_roll_and_partition(Hs, Ws, ws, shift):
+    from imageclassification_amd import swin
+    win, slot, region = swin.window_geometry(Hs, Ws, ws, shift)
+    g = torch.Generator().manual_seed(Hs * 100 + Ws)
+    B, C = 2, 5
+    x = torch.randn(B, Hs, Ws, C, generator=g)
+    sh = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2)) if shift else x
+    want = window_partition(sh, ws).view(B, -1, ws * ws, C)                      # [B, nW, T, C]
+    nW = (Hs // ws) * (Ws // ws)
+    got = torch.zeros(B, nW, ws * ws, C)
+    got[:, win, slot] = x.view(B, Hs * Ws, C)
+    assert torch.equal(got, want)
+    # every (window, slot) is hit exactly once
+    assert sorted((win * ws * ws + slot).tolist()) == list(range(Hs * Ws))
+    # region ids against timm's mask
+    mask = shifted_window_mask(Hs, Ws, ws, shift)
+    rw = torch.zeros(nW, ws * ws, dtype=torch.int64)
+    rw[win, slot] = region
+    differ = rw.unsqueeze(1) != rw.unsqueeze(2)
+    if mask is None:
+        assert not bool(differ.any())
+    else:
+        assert torch.equal(differ, mask != 0)
+        assert torch.equal(mask[differ], torch.full_like(mask[differ], -100.0))
+
+
+def test_window_geometry_refuses_what_does_not_tile():
+    from imageclassification_amd import swin
+    for bad in ((14, 15, 7, 3), (14, 14, 7, 7), (14, 14, 7, -1)):
+        with pytest.raises(ValueError):
+            swin.window_geometry(*bad)
+
+
+@pytest.mark.parametrize("ws", [4, 7, 8])
+def test_relative_position_index_matches_the_reference_buffer(ws):
+    from imageclassification_amd import swin
+    idx = swin.relative_position_index(ws)
+    assert idx.dtype == torch.int64 and torch.equal(idx, ref_index(ws))
+    assert int(idx.min()) == 0 and int(idx.max()) == (2 * ws - 1) ** 2 - 1
+
+
+def test_create_model_surface(monkeypatch):
+    sys.path.insert(0, ROOT)
+    import train as T
+    built = []
+
+    class Recorder:
+        def __init__(self, name, num_classes, **kw):
+            built.append((name, num_classes, kw))
+
+    monkeypatch.setattr(T, "SwinTransformer", Recorder)            # no model is constructed on a GPU-less host
+    for name in COUNTS:
+        assert isinstance(T.create_model(name, 1000, 224, 0.05), Recorder)
+        assert isinstance(T.create_model(name, 1000, 448, 0.05), Recorder)
+    assert [b[0] for b in built] == [n for n in COUNTS for _ in (0, 1)]
+    assert built[0][2] == {"img_size": 224}                        # --drop_path is not passed on: the class default (0.1) holds
+    monkeypatch.undo()                                             # the real class: its size check comes before any GPU use
+    with pytest.raises(ValueError, match="multiple of the window, or <= the window"):
+        T.create_model("swin_tiny_patch4_window7_224", 1000, 384, 0.05)
+    with pytest.raises(ValueError) as e:
+        T.create_model("swin_giant_nothing", 1000, 224, 0.05)
+    for name in COUNTS:
+        assert name in str(e.value)
+    assert T.get_args_parser().parse_args([]).model == "resnet50"
+    from imageclassification_amd.nets import ARCHS
+    assert len(ARCHS) == 23
+
+
+def test_constructor_default_drop_path_and_size_check():
+    import inspect
+    from imageclassification_amd import swin
+    sig = inspect.signature(swin.SwinTransformer.__init__)
+    assert sig.parameters["drop_path_rate"].default == 0.1
+    with pytest.raises(ValueError, match="multiple of the window, or <= the window"):
+        swin.SwinTransformer("swin_tiny_patch4_window7_224", 10, img_size=384)     # raised before the GPU is asked for
+    assert swin.stage_plan("swin_tiny_patch4_window7_224", 224) == [(56, 7, 3), (28, 7, 3), (14, 7, 3), (7, 7, 0)]
+    assert swin.stage_plan("swin_test", 56) == [(14, 7, 3), (7, 7, 0)]
+
+
+def test_abi_declares_the_new_entries_and_keeps_its_version():
+    from imageclassification_amd import hip
+    header = open(os.path.join(ROOT, "include", "icamd.h")).read()
+    for sym in SWIN_SYMBOLS:
+        assert sym in hip.EXPORTED_SYMBOLS
+        assert sym + "(" in header
+    assert hip.ABI_VERSION == 6
+    unit = open(os.path.join(ROOT, "imageclassification_amd", "csrc", "window_attention.hip")).read()
+    assert "atomicAdd" not in unit
+    assert "window_attention" in open(os.path.join(ROOT, "imageclassification_amd", "csrc", "build.sh")).read()
+
+
+def test_supported_and_workspace_queries_host_side():
+    from imageclassification_amd import hip
+    lib = hip.load()
+    for Hs, Ws, ws in ((56, 56, 7), (7, 7, 7), (8, 16, 4), (16, 8, 8), (4, 4, 2)):
+        assert lib.icamd_window_attention_supported(Hs, Ws, ws, 32) == 1
+    for Hs, Ws, ws, D in ((56, 56, 7, 64), (18, 18, 9, 32), (15, 14, 7, 32), (14, 15, 7, 32), (7, 7, 1, 32)):
+        assert lib.icamd_window_attention_supported(Hs, Ws, ws, D) == 0
+    # one fp32 [heads][T][T] partial per workgroup, at most 1024 workgroups, never more than windows / 4 per head
+    for (B, Hs, H), chunks in (((256, 56, 3), 341), ((1, 7, 24), 1), ((2, 14, 3), 2)):
+        need = chunks * H * 2401 * 4
+        assert need <= lib.icamd_window_attention_bwd_workspace_bytes(B, Hs, Hs, H, 7) < need + 256
+    assert lib.icamd_window_attention_bwd_workspace_bytes(1, 9, 9, 3, 9) == 0
+    assert lib.icamd_patch_merge_ln_bwd_workspace_bytes(2, 14, 14, 384) > 0
+    assert lib.icamd_patch_merge_ln_bwd_workspace_bytes(1, 8, 8, 516) == 0
+    assert lib.icamd_patch_merge_ln_bwd_workspace_bytes(1, 7, 8, 96) == 0

@@ -26,6 +26,7 @@ from imageclassification_amd.mixup import CrossEntropyLoss, LabelSmoothingCrossE
 from imageclassification_amd.nets import ARCHS, ResNet
 from imageclassification_amd.vit import CONFIGS as VIT_CONFIGS, NATIVE_SIZE as VIT_NATIVE_SIZE, VisionTransformer
 from imageclassification_amd.convnext import CONFIGS as CNX_CONFIGS, ConvNeXt
+from imageclassification_amd.swin import CONFIGS as SWIN_CONFIGS, SwinTransformer
 from imageclassification_amd.optim_factory import create_optimizer
 from imageclassification_amd.utils import NativeScalerWithGradNormCount as NativeScaler
 
@@ -90,7 +91,11 @@ def create_model(name, num_classes, input_size=None, drop_path=0.0):
         return VisionTransformer(name, num_classes, img_size=input_size)   # None: the name's own size (224 unless it says 384)
     if name in CNX_CONFIGS:
         return ConvNeXt(name, num_classes, drop_path_rate=drop_path)   # reference train.py:189-192
-    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS)})")
+    if name in SWIN_CONFIGS:
+        # the reference passes --drop_path to convnext* / efficientvit* only (train.py:189-192): Swin keeps its own default (timm: 0.1)
+        # a size the 7x7 windows do not tile (384) is the constructor's ValueError, raised before any device work
+        return SwinTransformer(name, num_classes, img_size=input_size)
+    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS)})")
 
 
 def main(args):
