@@ -234,7 +234,7 @@ def window_attention_ref(qkv, bias, B, Hs, Ws, H, ws, shift, dout=None, acc=torc
     mask = shifted_window_mask(Hs, Ws, ws, shift)
     if mask is not None:
         nW = mask.shape[0]
-        att = (att.view(-1, nW, H, N, N) + mask.to(acc).unsqueeze(1).unsqueeze(0)).view(-1, H, N, N)
+        att = (att.view(-1, nW, H, N, N) + mask.to(att).unsqueeze(1).unsqueeze(0)).view(-1, H, N, N)
     lse = torch.logsumexp(att, dim=-1)
     o = (torch.softmax(att, dim=-1) @ v).transpose(1, 2).reshape(B_, N, H * D)
     o = window_reverse(o.view(-1, ws, ws, H * D), ws, Hs, Ws)

@@ -57,8 +57,8 @@ def _tail(c, dt, mask=None):
     return r
 
 
-@functools.lru_cache(maxsize=None)
-def _case(N, HW, C, rd):
+def _inputs(N, HW, C, rd):
+    """The (rounded) inputs of a case, without references"""
     g = torch.Generator().manual_seed(1000 + N * 7 + HW + C)
     c = {"shape": (N, HW, C, rd)}
     # a raw convolution output with per-channel offsets and widths and a per-sample shift (so that s differs between samples)
@@ -78,6 +78,12 @@ def _case(N, HW, C, rd):
     c["b2"] = torch.randn(C, generator=g) * 1.2
     c["res"] = R.bf16_round(torch.randn(N, HW, C, generator=g))              # both signs
     c["dout"] = R.bf16_round(torch.randn(N, HW, C, generator=g) * 0.1)
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def _case(N, HW, C, rd):
+    c = _inputs(N, HW, C, rd)
     c["ref"] = _tail(c, torch.float32)
     c["ref64"] = _tail(c, torch.float64, c["ref"]["mask"])
     c["ysum64"] = c["y"].double().sum(1)

@@ -40,7 +40,8 @@ CASES = [
     (3, 7, 7, 2, 7, 0),       # one window
     (2, 8, 16, 2, 4, 2),      # T = 16
     (1, 16, 8, 2, 8, 4),      # T = 64 exactly, no padded columns
-    (8, 56, 56, 3, 7, 3),     # 1536 (window, head) pairs: several rounds of every CU
+    (8, 56, 56, 3, 7, 3),     # 512 windows x 3 heads: 128 workgroups per head, under both caps (682 forward, 341 backward), so
+                              # still ONE trip per workgroup; tests/test_multitrip_gpu.py has the multi-trip cases
 ]
 
 
