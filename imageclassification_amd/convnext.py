@@ -6,7 +6,8 @@ Linear -> gamma -> drop_path -> residual; stem 4x4/4 conv + channels-first LN :7
 :85-88; layer-scale init 1e-6 :32,39); the classification model itself comes from timm (train.py:194), whose parameter
 names are used here: `stem.{0,1}`, `stages.S.downsample.{0,1}`, `stages.S.blocks.B.{conv_dw,norm,mlp.fc1,mlp.fc2,gamma}`,
 `head.{norm,fc}`.  Stochastic depth follows timm: linearly increasing rates up to `drop_path_rate`
-(train.py:189-192 passes --drop_path, default 0.05), per-sample masks drawn on the host from torch's RNG.
+(train.py:189-192 passes --drop_path, default 0.05), per-sample masks drawn on the host from torch's RNG.  The flat arenas are
+arena.py's.
 
 NHWC activations make every "channels-first LayerNorm" an ordinary row LayerNorm over pixels, and every Linear a 1x1
 convolution on the same tensor (bias fused); the depthwise stencil and the layer-scale tail are dedicated kernels.
@@ -18,9 +19,8 @@ from collections import OrderedDict
 import torch
 
 from . import hip
-from .checkpoint import PicklableModel
+from .arena import ArenaModel, Layout, align
 from .streams import side_lane
-from .vit import _P, _align
 
 LN_EPS = 1e-6
 # Round 5: the layer scale (and timm drop_path's 1 / keep_prob) folded into fc2's filter and bias, the residual added in fc2's store
@@ -54,39 +54,20 @@ class _Conv:
         return d
 
 
-class ConvNeXt(PicklableModel):
+class ConvNeXt(ArenaModel):
     def __init__(self, arch="convnext_tiny", num_classes=1000, device="cuda", drop_path_rate=0.0, seed=None):
-        hip.require_gpu()
-        self.lib = hip.load()
-        self.arch, self.num_classes = arch, num_classes
-        self.device = torch.device(device)
-        self.training = True
+        super().__init__(arch, num_classes, device)
         self.depths, self.dims = CONFIGS[arch]
         self.drop_path_rate = drop_path_rate
-        self.ncls_p = _align(num_classes, 64)
-        self.num_batches_tracked = 0
-        self.grad_ready_hook = None
         self.injected_keep = None     # tests: list of per-block keep tensors (float [B]) to use instead of drawing
-        self._ws = {}
         self._build()
         self.init_weights(seed)
 
     # ------------------------------------------------------------------ structure / arenas
     def _build(self):
         dev = self.device
-        self.params = OrderedDict()
-        off = 0
-
-        def add(name, torch_shape, kind, padded_shape):
-            nonlocal off
-            numel = 1
-            for s in padded_shape:
-                numel *= s
-            p = _P(name, off, numel, tuple(torch_shape), kind, tuple(padded_shape))
-            self.params[name] = p
-            off = _align(off + numel, 64)
-            return p
-
+        layout = Layout()
+        add = layout.add
         self.gemms = []   # layers that need a transposed shadow (data gradient)
 
         def conv(name, cin, cout, k, stride, cin_p=None, cout_p=None, needs_dgrad=True, lin=False):
@@ -131,28 +112,7 @@ class ConvNeXt(PicklableModel):
         self.head_nw = add("head.norm.weight", (dl,), "vec", (dl,))
         self.head_nb = add("head.norm.bias", (dl,), "vec", (dl,))
         self.head = conv("head.fc", dl, self.num_classes, 1, 1, cout_p=self.ncls_p, lin=True)
-        self.n_params = off
-        self.param_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.grad_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev)
-        self.buffer_arena = torch.zeros(64, dtype=torch.float32, device=dev)
-        toff, descs, tjobs, jobs = 0, [], [], []
-        for c in self.gemms:
-            c.wt_offset = toff
-            T = c.k * c.k
-            descs.append([c.w.offset, toff, c.cout_p, T, c.cin_p, 0, 0, 0])
-            if c.cout_p % 64 == 0 and c.cin_p % 64 == 0:
-                tjobs += [[len(descs) - 1, t, a, b] for t in range(T) for a in range(0, c.cout_p, 64)
-                          for b in range(0, c.cin_p, 64)]
-            else:
-                jobs += [[len(descs) - 1, s] for s in range(0, c.w.numel, 4096)]
-            toff = _align(toff + c.w.numel, 128)
-        self.shadow_t = torch.zeros(toff, dtype=torch.bfloat16, device=dev)
-        self._tr_descs = torch.tensor(descs, dtype=torch.int64, device=dev)
-        self._tr_tjobs = torch.tensor(tjobs if tjobs else [[0, 0, 0, 0]], dtype=torch.int32, device=dev)
-        self._tr_ntjobs = len(tjobs)
-        self._tr_jobs = torch.tensor(jobs if jobs else [[0, 0]], dtype=torch.int32, device=dev)
-        self._tr_njobs = len(jobs)
+        self._allocate(layout, [(c, c.cout_p, c.k * c.k, c.cin_p) for c in self.gemms])
         # folded layer scale: one folded fc2 bias per block; the folded filter takes fc2's place in the bf16 shadow (and, through
         # refresh_transposed, in the transposed shadow), so _w(fc2) / _wt(fc2) are the folded operands
         self.fused_ls = _FUSED_LS
@@ -160,7 +120,7 @@ class ConvNeXt(PicklableModel):
         for st in self.stages:
             for blk in st["blocks"]:
                 blk["fb_off"] = fb
-                fb = _align(fb + blk["fc2"].cout_p, 64)
+                fb = align(fb + blk["fc2"].cout_p, 64)
         self.fold_bias = torch.zeros(max(fb, 64), dtype=torch.float32, device=dev)
         self._ls_cbs = None          # the per-block constants the shadow is currently folded with
         self._ls_jobs = None
@@ -183,62 +143,6 @@ class ConvNeXt(PicklableModel):
             else:
                 sd[name] = torch.zeros(p.torch_shape)
         self.load_state_dict(sd)
-
-    def _to_arena(self, p, t):
-        t = t.detach().to(torch.float32).cpu()
-        full = torch.zeros(p.padded_shape)
-        if p.kind == "conv":
-            full[: t.shape[0], :, :, : t.shape[1]] = t.permute(0, 2, 3, 1)
-        elif p.kind == "lin":
-            full[: t.shape[0], :] = t.reshape(t.shape[0], -1)
-        elif p.kind == "dw":
-            full[:] = t.reshape(t.shape[0], 7, 7).permute(1, 2, 0)
-        else:
-            full.view(-1)[: t.numel()] = t.flatten()
-        return full.flatten()
-
-    def _from_arena(self, p, flat):
-        t = flat.reshape(p.padded_shape)
-        if p.kind == "conv":
-            return t[: p.torch_shape[0], :, :, : p.torch_shape[1]].permute(0, 3, 1, 2).contiguous()
-        if p.kind == "lin":
-            return t[: p.torch_shape[0], :].clone()
-        if p.kind == "dw":
-            return t.permute(2, 0, 1).reshape(p.torch_shape).contiguous()
-        return t.flatten()[: p.torch_shape[0]].clone()
-
-    def load_state_dict(self, sd, strict=True):
-        host = self.param_arena.cpu()
-        missing = [n for n in self.params if n not in sd]
-        if strict and missing:
-            raise KeyError(f"missing keys in state_dict: {missing[:5]}")
-        for name, p in self.params.items():
-            if name in sd:
-                host[p.offset:p.offset + p.numel] = self._to_arena(p, sd[name])
-        self.param_arena.copy_(host)
-        self.refresh_shadow()
-        return missing
-
-    def state_dict(self):
-        host = self.param_arena.cpu()
-        return OrderedDict((n, self._from_arena(p, host[p.offset:p.offset + p.numel])) for n, p in self.params.items())
-
-    def named_parameters(self):
-        for name, p in self.params.items():
-            yield name, self.param_arena[p.offset:p.offset + p.numel]
-
-    def parameters(self):
-        for _, v in self.named_parameters():
-            yield v
-
-    def grad_of(self, name):
-        p = self.params[name]
-        return self._from_arena(p, self.grad_arena[p.offset:p.offset + p.numel].cpu())
-
-    def refresh_shadow(self):
-        hip.check(self.lib.icamd_f32_to_bf16(self.param_arena.data_ptr(), self.shadow.data_ptr(), self.n_params,
-                                             hip.stream_ptr()), "f32_to_bf16")
-        self.refresh_transposed()
 
     def _ls_mode_cbs(self):
         """timm drop_path scales the kept samples by 1 / keep_prob in training; identity in eval."""
@@ -272,27 +176,9 @@ class ConvNeXt(PicklableModel):
                                                  hip.stream_ptr()), "layer scale fold")
 
     def refresh_transposed(self):
-        s = hip.stream_ptr()
         if self.fused_ls:
             self._fold_layerscale()      # before the transposes: fc2's slot of the shadow becomes the folded filter
-        if self._tr_ntjobs:
-            hip.check(self.lib.icamd_filter_transpose_tiled(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                            self._tr_descs.data_ptr(), self._tr_tjobs.data_ptr(),
-                                                            self._tr_ntjobs, s), "filter_transpose_tiled")
-        if self._tr_njobs:
-            hip.check(self.lib.icamd_filter_transpose(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                      self._tr_descs.data_ptr(), self._tr_jobs.data_ptr(), self._tr_njobs, s),
-                      "filter_transpose")
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def to(self, *a, **k):
-        return self
+        super().refresh_transposed()
 
     # ------------------------------------------------------------------ workspace
     def _workspace(self, N, H, W):
@@ -375,25 +261,9 @@ class ConvNeXt(PicklableModel):
         return ws["g"]
 
     # ------------------------------------------------------------------ helpers
-    def _pf(self, p):
-        return self.param_arena.data_ptr() + 4 * p.offset
-
-    def _gf(self, p):
-        return self.grad_arena.data_ptr() + 4 * p.offset
-
-    def _w(self, c):
-        return self.shadow.data_ptr() + 2 * c.w.offset
-
-    def _wt(self, c):
-        return self.shadow_t.data_ptr() + 2 * c.wt_offset
-
     def pack(self, x_nchw, mix=None):
         N, C, H, W = x_nchw.shape
-        ws = self._workspace(N, H, W)
-        mode, lam, box = (0, 1.0, (0, 0, 0, 0)) if mix is None else mix
-        hip.check(self.lib.icamd_pack_input(x_nchw.data_ptr(), ws["x8"].data_ptr(), N, C, H, W, mode, float(lam), int(box[0]),
-                                            int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
-        return ws
+        return self._pack_input(self._workspace(N, H, W), x_nchw, mix)
 
     def _conv(self, c, x_ptr, y, N, H, W, s):
         hip.check(self.lib.icamd_conv2d_fwd(ctypes.byref(c.desc(N, H, W)), x_ptr, self._w(c), y.data_ptr(), self._pf(c.b), None,
@@ -414,32 +284,9 @@ class ConvNeXt(PicklableModel):
         self._ln(ws["s"], self.stem_nw, self.stem_nb, ws["x0"], ws["st_stem"], N * h * w, self.dims[0], s)
         x = ws["x0"]
         bi = 0
-        # stochastic depth (timm drop_path: per sample, scaled by 1/keep_prob): every block's mask for this step is drawn in
-        # ONE host call and uploaded ONCE from pinned memory without blocking, so the host keeps running ahead of the device
-        drop_rows = None
+        drop_rows = None      # stochastic depth: every block's mask for this step
         if self.training and self.injected_keep is None:
-            rates = [blk["rate"] for st in self.stages for blk in st["blocks"]]
-            if any(r > 0.0 for r in rates):
-                kp = 1.0 - torch.tensor(rates, dtype=torch.float32).view(-1, 1)
-                # a ring of 4 pinned staging rows: the upload of step i is enqueued behind step i's stem kernels, so waiting for it
-                # before the NEXT draw (one buffer, rounds 2-3) tied the host to within one step of the device (12 ms of the host's
-                # step spent in Event.synchronize, round-4 profile); with four rows the wait is for the upload issued 4 steps ago
-                ring = ws.get("keep_host")
-                if ring is None or ring.shape[1:] != (len(rates), N):
-                    ring = ws["keep_host"] = torch.empty(4, len(rates), N, dtype=torch.float32).pin_memory()
-                    ws["keep_dev"] = torch.empty(len(rates), N, dtype=torch.float32, device=self.device)
-                    ws["keep_copied"] = [None] * 4
-                    ws["keep_slot"] = 0
-                slot = ws["keep_slot"]
-                ws["keep_slot"] = (slot + 1) % 4
-                host = ring[slot]
-                if ws["keep_copied"][slot] is not None:
-                    ws["keep_copied"][slot].synchronize()   # the upload that last used this row has left it
-                torch.div((torch.rand(len(rates), N) < kp).float(), kp, out=host)
-                ws["keep_dev"].copy_(host, non_blocking=True)
-                ws["keep_copied"][slot] = torch.cuda.Event()
-                ws["keep_copied"][slot].record()
-                drop_rows = ws["keep_dev"]
+            drop_rows = self._draw_keep(ws, [blk["rate"] for st in self.stages for blk in st["blocks"]], N)
         if self.fused_ls and self._ls_cbs != self._ls_mode_cbs():
             self.refresh_transposed()     # train() <-> eval(), or a test's injected masks: fold with this mode's constants
         for si, (st, sw) in enumerate(zip(self.stages, ws["stages"])):
@@ -488,10 +335,6 @@ class ConvNeXt(PicklableModel):
         self._ln(ws["pool"], self.head_nw, self.head_nb, ws["pn"], ws["st_head"], N, dl, s)
         self._conv(self.head, ws["pn"].data_ptr(), ws["logits"], N, 1, 1, s)
         return ws["logits"]
-
-    def __call__(self, x_nchw):
-        ws = self.pack(x_nchw.to(self.device, dtype=torch.float32).contiguous())
-        return self.forward_packed(ws)[:, : self.num_classes]
 
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False, dfeat=None):

@@ -5,7 +5,7 @@ the gfx950 kernels: static layer lists with hand-written forward and backward.
 The reference builds its network with timm.create_model (/root/reference/train.py:194) and runs it through
 autograd (engine.py:48,51,64,72); there is no model code in the reference tree.  Here a model is a flat list
 of layer records over four flat arenas (fp32 parameters, fp32 gradients, bf16 "shadow" filters the conv
-kernels read, fp32 BatchNorm buffers) and every layer's forward/backward is one or more C-ABI calls
+kernels read, fp32 BatchNorm buffers; the arena protocol is arena.py's) and every layer's forward/backward is one or more C-ABI calls
 (include/icamd.h).  No autograd graph, no torch ops on the step path.
 
 Architecture = timm/torchvision ResNet v1.5 (stride on the 3x3 of a bottleneck), BatchNorm eps 1e-5,
@@ -25,7 +25,7 @@ from types import SimpleNamespace
 import torch
 
 from . import hip
-from .checkpoint import PicklableModel
+from .arena import ArenaModel, Layout, align
 from .streams import side_lane
 
 BN_EPS = 1e-5
@@ -174,19 +174,6 @@ def se_shapes(name, c, rd):
             (name + ".fc2.weight", (c, rd, 1, 1)), (name + ".fc2.bias", (c,))]
 
 
-def _align(n, a):
-    return (n + a - 1) // a * a
-
-
-class _Param:
-    """One logical parameter: a slice of the flat arenas plus its torch-layout shape."""
-    __slots__ = ("name", "offset", "numel", "torch_shape", "kind", "padded_shape")
-
-    def __init__(self, name, offset, numel, torch_shape, kind, padded_shape):
-        self.name, self.offset, self.numel = name, offset, numel
-        self.torch_shape, self.kind, self.padded_shape = torch_shape, kind, padded_shape
-
-
 class _Conv:
     """Convolution record. weight param in arena layout [Cout_p][KH][KW][Cin_p / groups] (groups > 1: ResNeXt's 3x3, which runs on
     the icamd_gconv3x3_* entries with this same filter for forward, data gradient and weight gradient)."""
@@ -199,7 +186,7 @@ class _Conv:
         self.cout_p = cout_p or cout
         self.k_p = k_p or k        # kernel extent of the arena layout (the stem stores 7x7 filters as 8x8x4, see _build_graph)
         self.has_bias = bias
-        self.w = None      # _Param
+        self.w = None      # arena.Param
         self.b = None
         self.wt_offset = None  # offset into the transposed shadow arena (None: no data gradient needed)
         self.descs = {}    # (N, IH, IW) -> ConvDesc
@@ -218,7 +205,7 @@ class _Conv:
 class _BN:
     def __init__(self, name, c):
         self.name, self.c = name, c
-        self.weight = self.bias = None  # _Param
+        self.weight = self.bias = None  # arena.Param
         self.buf_offset = None          # running_mean at buf_offset, running_var at buf_offset + c
         self.stat_offset = None         # mean, invstd, scale, shift in the per-model stat arena (4*c floats)
 
@@ -230,19 +217,14 @@ class _SE:
 
     def __init__(self, name, c, rd):
         self.name, self.c, self.rd = name, c, rd
-        self.w1 = self.b1 = self.w2 = self.b2 = None  # _Param
+        self.w1 = self.b1 = self.w2 = self.b2 = None  # arena.Param
 
 
-class ResNet(PicklableModel):
+class ResNet(ArenaModel):
     """HIP ResNet. `model(x)` runs the forward and returns bf16 logits [B, num_classes] (a view)."""
 
     def __init__(self, arch="resnet50", num_classes=1000, device="cuda", zero_init_last=True, seed=None):
-        hip.require_gpu()
-        self.lib = hip.load()
-        self.arch = arch
-        self.num_classes = num_classes
-        self.device = torch.device(device)
-        self.training = True
+        super().__init__(arch, num_classes, device)
         self._fold_dirty = True
         # eval forwards use BatchNorm-folded filters (ICAMD_EVAL_FOLD=0 keeps the separate BatchNorm pass)
         self.fold_eval = os.environ.get("ICAMD_EVAL_FOLD", "1") != "0"
@@ -251,15 +233,9 @@ class ResNet(PicklableModel):
         self.se = has_se(arch)
         self.deep = is_d(arch)
         self.expansion = 4 if block == "bottleneck" else 1
-        self.ncls_p = _align(num_classes, 64)
         self._build_graph()
-        self._allocate()
-        self.num_batches_tracked = 0
-        self._ws = {}
+        self._build_arenas()
         self.wgrad_side_stream = True   # bench.py turns this off for its per-kernel timing pass
-        # called as gradients complete with (param_offset_lo, param_offset_hi or None, events): `events` are side-stream events a
-        # consumer on another stream must wait for besides the main stream
-        self.grad_ready_hook = None
         self.init_weights(zero_init_last=zero_init_last, seed=seed)
 
     # ------------------------------------------------------------------ structure
@@ -322,8 +298,7 @@ class ResNet(PicklableModel):
                 pairs.append((blk["down_conv"], blk["down_bn"]))
         return pairs
 
-    def _allocate(self):
-        dev = self.device
+    def _build_arenas(self):
         # parameter order = timm/torchvision module order (conv, bn, ..., se, downsample, fc)
         order = [m for pair in self.stem_pairs for m in pair]
         for blk in self.blocks:
@@ -333,25 +308,17 @@ class ResNet(PicklableModel):
             if "down_conv" in blk:
                 order += [blk["down_conv"], blk["down_bn"]]
         order.append(self.fc)
-        self.params = OrderedDict()
-        off = 0
-
-        def add(name, torch_shape, kind, padded_shape):
-            nonlocal off
-            numel = 1
-            for s in padded_shape:
-                numel *= s
-            p = _Param(name, off, numel, tuple(torch_shape), kind, tuple(padded_shape))
-            self.params[name] = p
-            off = _align(off + numel, 64)  # 256 B alignment of every fp32 slice
-            return p
-
+        layout = Layout()
+        add = layout.add
         boff = 0
         soff = 0
         for m in order:
-            if isinstance(m, _Conv):
-                wname = m.name + ".weight"
-                m.w = add(wname, (m.cout, m.cin // m.groups, m.k, m.k), "conv", (m.cout_p, m.k_p, m.k_p, m.cin_p // m.groups))
+            if m is self.fc:      # nn.Linear: a 2-D weight in the state_dict, the 1x1 filter [ncls_p][1][1][feat] in the arena
+                m.w = add("fc.weight", (m.cout, m.cin), "lin", (m.cout_p, 1, 1, m.cin_p))
+                m.b = add("fc.bias", (m.cout,), "vec", (m.cout_p,))
+            elif isinstance(m, _Conv):
+                m.w = add(m.name + ".weight", (m.cout, m.cin // m.groups, m.k, m.k), "conv",
+                          (m.cout_p, m.k_p, m.k_p, m.cin_p // m.groups))
                 if m.has_bias:
                     m.b = add(m.name + ".bias", (m.cout,), "vec", (m.cout_p,))
             elif isinstance(m, _SE):
@@ -364,41 +331,15 @@ class ResNet(PicklableModel):
                 m.weight = add(m.name + ".weight", (m.c,), "vec", (m.c,))
                 m.bias = add(m.name + ".bias", (m.c,), "vec", (m.c,))
                 m.buf_offset = boff
-                boff = _align(boff + 2 * m.c, 64)
+                boff = align(boff + 2 * m.c, 64)
                 m.stat_offset = soff
-                soff = _align(soff + 4 * m.c, 64)
-        self.n_params = off
-        self.param_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.grad_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev)
-        self.buffer_arena = torch.zeros(max(boff, 64), dtype=torch.float32, device=dev)
-        self.stat_arena = torch.zeros(max(soff, 64), dtype=torch.float32, device=dev)
+                soff = align(soff + 4 * m.c, 64)
         # transposed filters for the data-gradient kernels (every conv except the stem's first and the grouped ones, whose data
         # gradient reads the forward layout; so does the thin route of the deep stem's other two, but those keep their 2 x 18 KB:
         # ICAMD_STEM_THIN=0 and images too wide for the thin kernels' LDS tile run on icamd_conv2d_dgrad)
-        toff = 0
-        descs, jobs, tjobs = [], [], []
-        for m in self.convs:
-            if m is self.stem_conv or m.groups > 1:
-                continue
-            m.wt_offset = toff
-            T = m.k * m.k
-            descs.append([m.w.offset, toff, m.cout_p, T, m.cin_p, 0, 0, 0])
-            if m.cout_p % 64 == 0 and m.cin_p % 64 == 0:
-                for t in range(T):
-                    for co0 in range(0, m.cout_p, 64):
-                        for ci0 in range(0, m.cin_p, 64):
-                            tjobs.append([len(descs) - 1, t, co0, ci0])
-            else:
-                for s in range(0, m.w.numel, 4096):
-                    jobs.append([len(descs) - 1, s])
-            toff = _align(toff + m.w.numel, 128)
-        self.shadow_t = torch.zeros(toff, dtype=torch.bfloat16, device=dev)
-        self._tr_descs = torch.tensor(descs, dtype=torch.int64, device=dev)
-        self._tr_jobs = torch.tensor(jobs if jobs else [[0, 0]], dtype=torch.int32, device=dev)
-        self._tr_njobs = len(jobs)
-        self._tr_tjobs = torch.tensor(tjobs if tjobs else [[0, 0, 0, 0]], dtype=torch.int32, device=dev)
-        self._tr_ntjobs = len(tjobs)
+        self._allocate(layout, [(m, m.cout_p, m.k * m.k, m.cin_p) for m in self.convs if m is not self.stem_conv and m.groups == 1],
+                       buffer_elems=boff)
+        self.stat_arena = torch.zeros(max(soff, 64), dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ parameters / state_dict
     def _ctor_kwargs(self):
@@ -414,13 +355,13 @@ class ResNet(PicklableModel):
             g.manual_seed(torch.initial_seed() % (2 ** 63))
         sd = OrderedDict()
         for name, p in self.params.items():
-            if p.kind == "conv" and not name.startswith("fc."):
+            if p.kind == "conv":
                 cout, cin, k, _ = p.torch_shape
                 std = math.sqrt(2.0 / (cout * k * k))
                 sd[name] = torch.randn(p.torch_shape, generator=g) * std
             elif name == "fc.weight":
                 bound = 1.0 / math.sqrt(p.torch_shape[1])
-                sd[name] = (torch.rand(p.torch_shape[0], p.torch_shape[1], generator=g) * 2 - 1) * bound
+                sd[name] = (torch.rand(p.torch_shape, generator=g) * 2 - 1) * bound
             elif name == "fc.bias":
                 bound = 1.0 / math.sqrt(self.feat_dim)
                 sd[name] = (torch.rand(p.torch_shape, generator=g) * 2 - 1) * bound
@@ -440,110 +381,39 @@ class ResNet(PicklableModel):
             sd[b.name + ".num_batches_tracked"] = torch.tensor(0)
         self.load_state_dict(sd)
 
-    def _to_arena_layout(self, p, t):
-        t = t.detach().to(torch.float32).cpu()
-        if p.kind == "conv":
-            if t.dim() == 2:
-                t = t[:, :, None, None]
-            cout, cin, kh, kw = t.shape
-            full = torch.zeros(p.padded_shape)
-            full[:cout, :kh, :kw, :cin] = t.permute(0, 2, 3, 1)
-            return full.flatten()
-        full = torch.zeros(p.padded_shape)
-        full[: t.numel()] = t.flatten()
-        return full
+    def _buffer_keys(self):
+        return [f"{b.name}.{key}" for b in self.bns for key in ("running_mean", "running_var")]
 
-    def _from_arena_layout(self, p, flat):
-        t = flat.reshape(p.padded_shape)
-        if p.kind == "conv":
-            cout, cin, kh, kw = (tuple(p.torch_shape) + (1, 1))[:4]
-            t = t[:cout, :kh, :kw, :cin].permute(0, 3, 1, 2).contiguous()
-            if p.name == "fc.weight":
-                t = t.reshape(cout, cin)
-            return t
-        return t[: p.torch_shape[0]].clone()
-
-    def load_state_dict(self, sd, strict=True):
-        host = self.param_arena.cpu()
-        missing = []
-        for name, p in self.params.items():
-            if name not in sd:
-                missing.append(name)
-                continue
-            host[p.offset:p.offset + p.numel] = self._to_arena_layout(p, sd[name])
+    def _load_buffers(self, sd):
         bufs = self.buffer_arena.cpu()
         for b in self.bns:
             for j, key in enumerate(("running_mean", "running_var")):
                 k = f"{b.name}.{key}"
                 if k in sd:
                     bufs[b.buf_offset + j * b.c: b.buf_offset + (j + 1) * b.c] = sd[k].detach().float().cpu()
-                else:
-                    missing.append(k)
+        self.buffer_arena.copy_(bufs)
         k = f"{self.bns[0].name}.num_batches_tracked"
         if k in sd:
             self.num_batches_tracked = int(sd[k])
-        if strict and missing:
-            raise KeyError(f"missing keys in state_dict: {missing[:5]}{'...' if len(missing) > 5 else ''}")
-        self.param_arena.copy_(host)
-        self.buffer_arena.copy_(bufs)
-        self.refresh_shadow()
         self._fold_dirty = True
-        return missing
 
     def state_dict(self):
-        host = self.param_arena.cpu()
+        """Parameters in module order, each BatchNorm's buffers right after its bias (torch's key order)."""
         bufs = self.buffer_arena.cpu()
+        bn_of_bias = {b.name + ".bias": b for b in self.bns}
         sd = OrderedDict()
-        by_module = OrderedDict()
-        for name, p in self.params.items():
-            by_module.setdefault(name.rsplit(".", 1)[0], []).append(p)
-        bn_by_name = {b.name: b for b in self.bns}
-        for mod, plist in by_module.items():
-            for p in plist:
-                sd[p.name] = self._from_arena_layout(p, host[p.offset:p.offset + p.numel])
-            if mod in bn_by_name:
-                b = bn_by_name[mod]
-                sd[mod + ".running_mean"] = bufs[b.buf_offset:b.buf_offset + b.c].clone()
-                sd[mod + ".running_var"] = bufs[b.buf_offset + b.c:b.buf_offset + 2 * b.c].clone()
-                sd[mod + ".num_batches_tracked"] = torch.tensor(self.num_batches_tracked)
+        for name, t in super().state_dict().items():
+            sd[name] = t
+            b = bn_of_bias.get(name)
+            if b is not None:
+                sd[b.name + ".running_mean"] = bufs[b.buf_offset:b.buf_offset + b.c].clone()
+                sd[b.name + ".running_var"] = bufs[b.buf_offset + b.c:b.buf_offset + 2 * b.c].clone()
+                sd[b.name + ".num_batches_tracked"] = torch.tensor(self.num_batches_tracked)
         return sd
 
-    def named_parameters(self):
-        """(name, fp32 arena view) pairs; the views alias the flat parameter arena."""
-        for name, p in self.params.items():
-            yield name, self.param_arena[p.offset:p.offset + p.numel]
-
-    def parameters(self):
-        for _, v in self.named_parameters():
-            yield v
-
-    def grad_of(self, name):
-        """Gradient of a parameter in torch layout (host copy), for tests and checkpoint tools."""
-        p = self.params[name]
-        return self._from_arena_layout(p, self.grad_arena[p.offset:p.offset + p.numel].cpu())
-
-    def refresh_shadow(self):
-        """Re-derive the bf16 filters (and their transposes) from the fp32 master parameters."""
-        s = hip.stream_ptr()
-        hip.check(self.lib.icamd_f32_to_bf16(self.param_arena.data_ptr(), self.shadow.data_ptr(), self.n_params, s),
-                  "f32_to_bf16")
-        self.refresh_transposed()
-
-    def refresh_transposed(self):
-        s = hip.stream_ptr()
-        if self._tr_ntjobs:
-            hip.check(self.lib.icamd_filter_transpose_tiled(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                            self._tr_descs.data_ptr(), self._tr_tjobs.data_ptr(),
-                                                            self._tr_ntjobs, s), "filter_transpose_tiled")
-        if self._tr_njobs:
-            hip.check(self.lib.icamd_filter_transpose(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                      self._tr_descs.data_ptr(), self._tr_jobs.data_ptr(), self._tr_njobs,
-                                                      s), "filter_transpose")
-
     def train(self, mode=True):
-        self.training = bool(mode)
         self._fold_dirty = True     # parameters / running statistics may move before the next eval forward
-        return self
+        return super().train(mode)
 
     # ------------------------------------------------------------------ inference form (SURVEY 8f-1)
     def fold_batchnorm(self):
@@ -612,12 +482,6 @@ class ResNet(PicklableModel):
         hip.check(lib.icamd_conv2d_fwd(ctypes.byref(dfc), ws["pooled"].data_ptr(), self._w(self.fc),
                                        ws["logits"].data_ptr(), self._pf(self.fc.b), None, None, s), "fc")
         return ws["logits"]
-
-    def eval(self):
-        return self.train(False)
-
-    def to(self, *a, **k):
-        return self
 
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, N, H, W):
@@ -760,18 +624,6 @@ class ResNet(PicklableModel):
         raise KeyError(ptr)
 
     # ------------------------------------------------------------------ primitive wrappers
-    def _w(self, conv):
-        return self.shadow.data_ptr() + 2 * conv.w.offset
-
-    def _wt(self, conv):
-        return self.shadow_t.data_ptr() + 2 * conv.wt_offset
-
-    def _pf(self, p):  # fp32 param pointer
-        return self.param_arena.data_ptr() + 4 * p.offset
-
-    def _gf(self, p):  # fp32 grad pointer
-        return self.grad_arena.data_ptr() + 4 * p.offset
-
     def _stats(self, bn):
         """(mean, invstd, scale, shift) pointers of a BatchNorm's saved batch statistics."""
         st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
@@ -902,15 +754,8 @@ class ResNet(PicklableModel):
     def pack(self, x_nchw, mix=None):
         """fp32 NCHW device tensor -> packed NHWC bf16 (channels zero-padded to 8), with optional mixup/cutmix."""
         N, C, H, W = x_nchw.shape
-        ws = self._workspace(N, H, W)
-        mode, lam, box = (0, 1.0, (0, 0, 0, 0)) if mix is None else mix
-        if self.deep:      # the deep stem's first convolution reads the plain 8-channel packed image
-            hip.check(self.lib.icamd_pack_input(x_nchw.data_ptr(), ws["x8"].data_ptr(), N, C, H, W, mode, float(lam),
-                                                int(box[0]), int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
-            return ws
-        hip.check(self.lib.icamd_pack_input_rgb4(x_nchw.data_ptr(), ws["x8"].data_ptr(), N, C, H, W, mode, float(lam),
-                                                 int(box[0]), int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
-        return ws
+        # the deep stem's first convolution reads the plain 8-channel packed image, the 7x7 stem the rgb4 layout
+        return self._pack_input(self._workspace(N, H, W), x_nchw, mix, rgb4=not self.deep)
 
     def forward_packed(self, ws, logits_only=False):   # logits_only: accepted for interface parity (BatchNorm needs every conv output)
         lib = self.lib
@@ -1015,11 +860,6 @@ class ResNet(PicklableModel):
         hip.check(lib.icamd_conv2d_fwd(ctypes.byref(dfc), ws["pooled"].data_ptr(), self._w(self.fc),
                                        ws["logits"].data_ptr(), self._pf(self.fc.b), None, None, s), "fc")
         return ws["logits"]
-
-    def __call__(self, x_nchw):
-        ws = self.pack(x_nchw.to(self.device, dtype=torch.float32).contiguous())
-        logits = self.forward_packed(ws)
-        return logits[:, : self.num_classes]
 
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False):

@@ -13,9 +13,9 @@ rules.
 
 Tokens stay in their natural [B][H][W][C] order through the whole network: the window kernels do the roll, the partition and their
 inverses as address arithmetic, so every Linear is the 1x1 case of the convolution kernels on a [rows, 1, 1, C] "image" exactly as in
-vit.py (bias, GELU and the residual add fused in the epilogue).  Same flat-arena design as vit.py / convnext.py.  Stochastic depth
-is timm's (rates rising linearly to `drop_path_rate`, one per-sample mask per residual branch, drawn on the host as convnext.py
-does and applied with icamd_layerscale_fwd / _bwd and a vector of ones); with rate 0 the residual rides in the GEMM epilogue.
+vit.py (bias, GELU and the residual add fused in the epilogue).  The flat arenas are arena.py's.  Stochastic depth
+is timm's (rates rising linearly to `drop_path_rate`, one per-sample mask per residual branch, drawn on the host by
+ArenaModel._draw_keep and applied with icamd_layerscale_fwd / _bwd and a vector of ones); with rate 0 the residual rides in the GEMM epilogue.
 """
 import ctypes
 from collections import OrderedDict
@@ -23,8 +23,7 @@ from collections import OrderedDict
 import torch
 
 from . import hip
-from .checkpoint import PicklableModel
-from .vit import _P, _align
+from .arena import ArenaModel, Layout, Lin, align
 
 LN_EPS = 1e-5
 HEAD_DIM = 32
@@ -131,69 +130,34 @@ def param_shapes(arch, num_classes=1000, img_size=224):
     return OrderedDict((n, tuple(s)) for n, s, _ in _param_list(arch, num_classes, img_size))
 
 
-class _Lin:
-    """Linear layer = 1x1 convolution record (weight [out_p][in] in the arena; `b` is None for the bias-free reduction)."""
-
-    def __init__(self, name, cin, cout, cout_p=None):
-        self.name, self.cin, self.cout = name, cin, cout
-        self.cout_p = cout_p or cout
-        self.w = self.b = None
-        self.wt_offset = None
-        self.descs = {}
-
-    def desc(self, rows):
-        d = self.descs.get(rows)
-        if d is None:
-            d = hip.conv_desc(rows, 1, 1, self.cin, self.cout_p, 1, 1, 1, 0)
-            self.descs[rows] = d
-        return d
-
-
-class SwinTransformer(PicklableModel):
+class SwinTransformer(ArenaModel):
     def __init__(self, arch="swin_tiny_patch4_window7_224", num_classes=1000, device="cuda", img_size=None, drop_path_rate=0.1,
                  seed=None):
         self.plan = stage_plan(arch, img_size)          # before anything touches the GPU: a bad size is a ValueError everywhere
-        hip.require_gpu()
-        self.lib = hip.load()
-        self.arch, self.num_classes = arch, num_classes
-        self.device = torch.device(device)
-        self.training = True
+        super().__init__(arch, num_classes, device)
         self.embed, self.depths, self.heads, self.window = CONFIGS[arch]
         self.img_size = 224 if img_size is None else img_size
         self.drop_path_rate = drop_path_rate
-        self.ncls_p = _align(num_classes, 64)
-        self.num_batches_tracked = 0
-        self.grad_ready_hook = None
         self.injected_keep = None     # tests: list of per-branch keep tensors (float [B], two per block) used instead of drawing
-        self._ws = {}
         self._build()
         self.init_weights(seed)
 
     # ------------------------------------------------------------------ structure / arenas
     def _build(self):
         dev = self.device
-        self.params = OrderedDict()
-        off = 0
+        layout = Layout()
         for name, shape, kind in _param_list(self.arch, self.num_classes, self.img_size):
             if kind == "conv":
-                padded = (shape[0], PATCH, PATCH, 8)
-            elif name == "head.fc.weight":
-                padded = (self.ncls_p, shape[1])
-            elif name == "head.fc.bias":
-                padded = (self.ncls_p,)
+                layout.add(name, shape, kind, (shape[0], PATCH, PATCH, 8))
+            elif name.startswith("head.fc."):
+                layout.add(name, shape, kind, (self.ncls_p,) + tuple(shape[1:]))
             else:
-                padded = tuple(shape)
-            numel = 1
-            for s in padded:
-                numel *= s
-            self.params[name] = _P(name, off, numel, tuple(shape), kind, padded)
-            off = _align(off + numel, 64)
-        self.n_params = off
-        P = self.params
+                layout.add(name, shape, kind)
+        P = layout.params
         self.lins = []
 
         def lin(name, cin, cout, cout_p=None, bias=True):
-            l = _Lin(name, cin, cout, cout_p)
+            l = Lin(name, cin, cout, cout_p)
             l.w = P[name + ".weight"]
             l.b = P[name + ".bias"] if bias else None
             self.lins.append(l)
@@ -226,35 +190,17 @@ class SwinTransformer(PicklableModel):
                 blk["fc1"] = lin(f"{n}.mlp.fc1", dim, 4 * dim)
                 blk["fc2"] = lin(f"{n}.mlp.fc2", 4 * dim, dim)
                 st["blocks"].append(blk)
-                boff = _align(boff + self.heads[i] * ws ** 4, 64)
+                boff = align(boff + self.heads[i] * ws ** 4, 64)
                 bi += 1
             self.stages.append(st)
         self.last_dim = self.embed << (len(self.depths) - 1)
         self.p_nw, self.p_nb = P["norm.weight"], P["norm.bias"]
         self.head = lin("head.fc", self.last_dim, self.num_classes, self.ncls_p)
-        self.param_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.grad_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev)
-        self.buffer_arena = torch.zeros(64, dtype=torch.float32, device=dev)   # no buffers; kept for the EMA/DDP protocol
+        self._allocate(layout, [(l, l.cout_p, 1, l.cin) for l in self.lins])
         # the gathered relative-position bias of every block, fp32 [heads][ws^2][ws^2]: refreshed with the transposed shadow,
         # i.e. after every load and every optimizer step -- the only places the tables move
         self.bias_arena = torch.zeros(max(boff, 64), dtype=torch.float32, device=dev)
         self.ones = torch.ones(max(st["dim"] for st in self.stages), dtype=torch.float32, device=dev)
-        toff, descs, tjobs, jobs = 0, [], [], []
-        for l in self.lins:
-            l.wt_offset = toff
-            descs.append([l.w.offset, toff, l.cout_p, 1, l.cin, 0, 0, 0])
-            if l.cout_p % 64 == 0 and l.cin % 64 == 0:
-                tjobs += [[len(descs) - 1, 0, a, b] for a in range(0, l.cout_p, 64) for b in range(0, l.cin, 64)]
-            else:
-                jobs += [[len(descs) - 1, s] for s in range(0, l.w.numel, 4096)]
-            toff = _align(toff + l.w.numel, 128)
-        self.shadow_t = torch.zeros(toff, dtype=torch.bfloat16, device=dev)
-        self._tr_descs = torch.tensor(descs, dtype=torch.int64, device=dev)
-        self._tr_tjobs = torch.tensor(tjobs if tjobs else [[0, 0, 0, 0]], dtype=torch.int32, device=dev)
-        self._tr_ntjobs = len(tjobs)
-        self._tr_jobs = torch.tensor(jobs if jobs else [[0, 0]], dtype=torch.int32, device=dev)
-        self._tr_njobs = len(jobs)
 
     def _ctor_kwargs(self):
         return {"arch": self.arch, "num_classes": self.num_classes, "img_size": self.img_size,
@@ -278,89 +224,15 @@ class SwinTransformer(PicklableModel):
                 sd[name] = torch.zeros(p.torch_shape)
         self.load_state_dict(sd)
 
-    def _to_arena(self, p, t):
-        t = t.detach().to(torch.float32).cpu()
-        if tuple(t.shape) != p.torch_shape:
-            raise ValueError(f"size mismatch for {p.name}: {tuple(t.shape)} vs {p.torch_shape}")
-        full = torch.zeros(p.padded_shape)
-        if p.kind == "conv":
-            full[: t.shape[0], :, :, : t.shape[1]] = t.permute(0, 2, 3, 1)
-        elif p.kind == "lin":
-            full[: t.shape[0], :] = t
-        else:
-            full.view(-1)[: t.numel()] = t.flatten()
-        return full.flatten()
-
-    def _from_arena(self, p, flat):
-        t = flat.reshape(p.padded_shape)
-        if p.kind == "conv":
-            return t[: p.torch_shape[0], :, :, : p.torch_shape[1]].permute(0, 3, 1, 2).contiguous()
-        if p.kind == "lin":
-            return t[: p.torch_shape[0], :].clone()
-        n = 1
-        for s in p.torch_shape:
-            n *= s
-        return t.flatten()[:n].reshape(p.torch_shape).clone()
-
-    def load_state_dict(self, sd, strict=True):
-        host = self.param_arena.cpu()
-        missing = [n for n in self.params if n not in sd]
-        if strict and missing:
-            raise KeyError(f"missing keys in state_dict: {missing[:5]}")
-        for name, p in self.params.items():
-            if name in sd:
-                host[p.offset:p.offset + p.numel] = self._to_arena(p, sd[name])
-        self.param_arena.copy_(host)
-        self.refresh_shadow()
-        return missing
-
-    def state_dict(self):
-        host = self.param_arena.cpu()
-        return OrderedDict((n, self._from_arena(p, host[p.offset:p.offset + p.numel])) for n, p in self.params.items())
-
-    def named_parameters(self):
-        for name, p in self.params.items():
-            yield name, self.param_arena[p.offset:p.offset + p.numel]
-
-    def parameters(self):
-        for _, v in self.named_parameters():
-            yield v
-
-    def grad_of(self, name):
-        p = self.params[name]
-        return self._from_arena(p, self.grad_arena[p.offset:p.offset + p.numel].cpu())
-
-    def refresh_shadow(self):
-        hip.check(self.lib.icamd_f32_to_bf16(self.param_arena.data_ptr(), self.shadow.data_ptr(), self.n_params,
-                                             hip.stream_ptr()), "f32_to_bf16")
-        self.refresh_transposed()
-
     def refresh_transposed(self):
         """What follows every change of the parameters (load, optimizer step): the transposed bf16 filters of the data gradients
         and the relative-position bias of every block, gathered from its table."""
+        super().refresh_transposed()
         s = hip.stream_ptr()
-        if self._tr_ntjobs:
-            hip.check(self.lib.icamd_filter_transpose_tiled(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                            self._tr_descs.data_ptr(), self._tr_tjobs.data_ptr(),
-                                                            self._tr_ntjobs, s), "filter_transpose_tiled")
-        if self._tr_njobs:
-            hip.check(self.lib.icamd_filter_transpose(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                      self._tr_descs.data_ptr(), self._tr_jobs.data_ptr(), self._tr_njobs, s),
-                      "filter_transpose")
         for st in self.stages:
             for blk in st["blocks"]:
                 hip.check(self.lib.icamd_relpos_bias_gather(self._pf(blk["table"]), self._bias(blk), st["heads"], st["ws"], s),
                           blk["name"] + " bias gather")
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def to(self, *a, **k):
-        return self
 
     # ------------------------------------------------------------------ workspace
     def _workspace(self, B):
@@ -453,18 +325,6 @@ class SwinTransformer(PicklableModel):
         return d
 
     # ------------------------------------------------------------------ helpers
-    def _pf(self, p):
-        return self.param_arena.data_ptr() + 4 * p.offset
-
-    def _gf(self, p):
-        return self.grad_arena.data_ptr() + 4 * p.offset
-
-    def _w(self, l):
-        return self.shadow.data_ptr() + 2 * l.w.offset
-
-    def _wt(self, l):
-        return self.shadow_t.data_ptr() + 2 * l.wt_offset
-
     def _bias(self, blk):
         return self.bias_arena.data_ptr() + 4 * blk["bias_off"]
 
@@ -472,11 +332,7 @@ class SwinTransformer(PicklableModel):
         B, C, H, W = x_nchw.shape
         if H != self.img_size or W != self.img_size:
             raise ValueError(f"this model's window plan is built for {self.img_size}x{self.img_size} inputs, not {H}x{W}")
-        ws = self._workspace(B)
-        mode, lam, box = (0, 1.0, (0, 0, 0, 0)) if mix is None else mix
-        hip.check(self.lib.icamd_pack_input(x_nchw.data_ptr(), ws["x8"].data_ptr(), B, C, H, W, mode, float(lam), int(box[0]),
-                                            int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
-        return ws
+        return self._pack_input(self._workspace(B), x_nchw, mix)
 
     def _linear(self, l, x_ptr, y_ptr, rows, addend_ptr, s):
         hip.check(self.lib.icamd_conv2d_fwd(ctypes.byref(l.desc(rows)), x_ptr, self._w(l), y_ptr,
@@ -485,30 +341,6 @@ class SwinTransformer(PicklableModel):
     def _ln(self, x_ptr, wp, bp, y_ptr, st, rows, C, s):
         hip.check(self.lib.icamd_layernorm_fwd(x_ptr, self._pf(wp), self._pf(bp), y_ptr, st.data_ptr(), st.data_ptr() + 4 * rows,
                                                rows, C, LN_EPS, s), wp.name)
-
-    def _draw_keep(self, ws, B):
-        """One per-sample mask per residual branch for this step (timm drop_path: keep / keep_prob), drawn in one host call and
-        uploaded once from a ring of pinned rows (convnext.py)."""
-        rates = [blk["rate"] for st in self.stages for blk in st["blocks"] for _ in (0, 1)]
-        if not any(r > 0.0 for r in rates):
-            return None
-        kp = 1.0 - torch.tensor(rates, dtype=torch.float32).view(-1, 1)
-        ring = ws.get("keep_host")
-        if ring is None:
-            ring = ws["keep_host"] = torch.empty(4, len(rates), B, dtype=torch.float32).pin_memory()
-            ws["keep_dev"] = torch.empty(len(rates), B, dtype=torch.float32, device=self.device)
-            ws["keep_copied"] = [None] * 4
-            ws["keep_slot"] = 0
-        slot = ws["keep_slot"]
-        ws["keep_slot"] = (slot + 1) % 4
-        host = ring[slot]
-        if ws["keep_copied"][slot] is not None:
-            ws["keep_copied"][slot].synchronize()   # the upload that last used this row has left it
-        torch.div((torch.rand(len(rates), B) < kp).float(), kp, out=host)
-        ws["keep_dev"].copy_(host, non_blocking=True)
-        ws["keep_copied"][slot] = torch.cuda.Event()
-        ws["keep_copied"][slot].record()
-        return ws["keep_dev"]
 
     # ------------------------------------------------------------------ forward
     def forward_packed(self, ws, logits_only=False):
@@ -525,7 +357,8 @@ class SwinTransformer(PicklableModel):
         x = ws["x0"]
         drop_rows = None
         if self.training and self.injected_keep is None:
-            drop_rows = self._draw_keep(ws, B)
+            # one per-sample mask per residual branch: two per block
+            drop_rows = self._draw_keep(ws, [blk["rate"] for st in self.stages for blk in st["blocks"] for _ in (0, 1)], B)
         bi = 0
         for i, (st, sw) in enumerate(zip(self.stages, ws["stages"])):
             dim, res, wsz, H, M = st["dim"], st["res"], st["ws"], st["heads"], sw["M"]
@@ -584,10 +417,6 @@ class SwinTransformer(PicklableModel):
         if t is None:
             t = ws["branch_tmp"] = torch.empty(ws["max_mc"], dtype=torch.bfloat16, device=self.device)
         return t
-
-    def __call__(self, x_nchw):
-        ws = self.pack(x_nchw.to(self.device, dtype=torch.float32).contiguous())
-        return self.forward_packed(ws)[:, : self.num_classes]
 
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False):

@@ -9,7 +9,7 @@ pooling, linear head.  Parameter names follow timm (`cls_token`, `pos_embed`, `p
 
 Every Linear is the 1x1 case of the implicit-GEMM convolution kernels on a [B*T, 1, 1, C] "image" (bias and the
 residual add fused in the epilogue); LayerNorm / GELU / attention are the token kernels of include/icamd.h.
-Same flat-arena design as nets.ResNet (fp32 parameters and gradients, bf16 shadow weights and their transposes).
+The flat arenas (fp32 parameters and gradients, bf16 shadow weights and their transposes) are arena.py's.
 """
 import ctypes
 import math
@@ -18,7 +18,7 @@ from collections import OrderedDict
 import torch
 
 from . import hip
-from .checkpoint import PicklableModel
+from .arena import ArenaModel, Layout, Lin
 from .streams import side_lane
 
 LN_EPS = 1e-6
@@ -37,43 +37,9 @@ CONFIGS = {
 NATIVE_SIZE = {"vit_base_patch16_384": 384, "vit_small_patch16_384": 384}
 
 
-def _align(n, a):
-    return (n + a - 1) // a * a
-
-
-class _P:
-    __slots__ = ("name", "offset", "numel", "torch_shape", "kind", "padded_shape")
-
-    def __init__(self, name, offset, numel, torch_shape, kind, padded_shape):
-        self.name, self.offset, self.numel = name, offset, numel
-        self.torch_shape, self.kind, self.padded_shape = torch_shape, kind, padded_shape
-
-
-class _Lin:
-    """Linear layer = 1x1 convolution record (weight [out_p][in] in the arena)."""
-
-    def __init__(self, name, cin, cout, cout_p=None):
-        self.name, self.cin, self.cout = name, cin, cout
-        self.cout_p = cout_p or cout
-        self.w = self.b = None
-        self.wt_offset = None
-        self.descs = {}
-
-    def desc(self, rows):
-        d = self.descs.get(rows)
-        if d is None:
-            d = hip.conv_desc(rows, 1, 1, self.cin, self.cout_p, 1, 1, 1, 0)
-            self.descs[rows] = d
-        return d
-
-
-class VisionTransformer(PicklableModel):
+class VisionTransformer(ArenaModel):
     def __init__(self, arch="vit_base_patch16_224", num_classes=1000, device="cuda", img_size=None, seed=None):
-        hip.require_gpu()
-        self.lib = hip.load()
-        self.arch, self.num_classes = arch, num_classes
-        self.device = torch.device(device)
-        self.training = True
+        super().__init__(arch, num_classes, device)
         self.patch, self.dim, self.depth, self.heads, mlp_ratio = CONFIGS[arch]
         if self.dim // self.heads != 64:
             raise ValueError("the attention kernel is built for a head dimension of 64")
@@ -85,34 +51,18 @@ class VisionTransformer(PicklableModel):
         self.img_size = img_size
         self.grid = img_size // self.patch
         self.T = self.grid * self.grid + 1
-        self.ncls_p = _align(num_classes, 64)
-        self.num_batches_tracked = 0
-        self.grad_ready_hook = None
-        self._ws = {}
         self._build()
         self.init_weights(seed)
 
     # ------------------------------------------------------------------ structure / arenas
     def _build(self):
-        dev = self.device
         D = self.dim
-        self.params = OrderedDict()
-        off = 0
-
-        def add(name, torch_shape, kind, padded_shape):
-            nonlocal off
-            numel = 1
-            for s in padded_shape:
-                numel *= s
-            p = _P(name, off, numel, tuple(torch_shape), kind, tuple(padded_shape))
-            self.params[name] = p
-            off = _align(off + numel, 64)
-            return p
-
+        layout = Layout()
+        add = layout.add
         self.lins = []
 
         def lin(name, cin, cout, cout_p=None):
-            l = _Lin(name, cin, cout, cout_p)
+            l = Lin(name, cin, cout, cout_p)
             l.w = add(name + ".weight", (cout, cin), "lin", (l.cout_p, cin))
             l.b = add(name + ".bias", (cout,), "vec", (l.cout_p,))
             self.lins.append(l)
@@ -138,23 +88,7 @@ class VisionTransformer(PicklableModel):
         self.p_nw = add("norm.weight", (D,), "vec", (D,))
         self.p_nb = add("norm.bias", (D,), "vec", (D,))
         self.head = lin("head", D, self.num_classes, self.ncls_p)
-        self.n_params = off
-        self.param_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.grad_arena = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.shadow = torch.zeros(off, dtype=torch.bfloat16, device=dev)
-        self.buffer_arena = torch.zeros(64, dtype=torch.float32, device=dev)   # no buffers; kept for the EMA/DDP protocol
-        toff, descs, tjobs = 0, [], []
-        for l in self.lins:
-            l.wt_offset = toff
-            descs.append([l.w.offset, toff, l.cout_p, 1, l.cin, 0, 0, 0])
-            for co0 in range(0, l.cout_p, 64):
-                for ci0 in range(0, l.cin, 64):
-                    tjobs.append([len(descs) - 1, 0, co0, ci0])
-            toff = _align(toff + l.w.numel, 128)
-        self.shadow_t = torch.zeros(toff, dtype=torch.bfloat16, device=dev)
-        self._tr_descs = torch.tensor(descs, dtype=torch.int64, device=dev)
-        self._tr_tjobs = torch.tensor(tjobs, dtype=torch.int32, device=dev)
-        self._tr_ntjobs = len(tjobs)
+        self._allocate(layout, [(l, l.cout_p, 1, l.cin) for l in self.lins])
 
     def _ctor_kwargs(self):
         return {"arch": self.arch, "num_classes": self.num_classes, "img_size": self.img_size}
@@ -188,77 +122,6 @@ class VisionTransformer(PicklableModel):
             else:
                 sd[name] = torch.zeros(p.torch_shape)
         self.load_state_dict(sd)
-
-    def _to_arena(self, p, t):
-        t = t.detach().to(torch.float32).cpu()
-        full = torch.zeros(p.padded_shape)
-        if p.kind == "conv":
-            cout, cin = t.shape[0], t.shape[1]
-            full[:cout, :, :, :cin] = t.permute(0, 2, 3, 1)
-        elif p.kind == "lin":
-            full[: t.shape[0], :] = t
-        else:
-            full.view(-1)[: t.numel()] = t.flatten()
-        return full.flatten()
-
-    def _from_arena(self, p, flat):
-        t = flat.reshape(p.padded_shape)
-        if p.kind == "conv":
-            return t[: p.torch_shape[0], :, :, : p.torch_shape[1]].permute(0, 3, 1, 2).contiguous()
-        if p.kind == "lin":
-            return t[: p.torch_shape[0], :].clone()
-        n = 1
-        for s in p.torch_shape:
-            n *= s
-        return t.flatten()[:n].reshape(p.torch_shape).clone()
-
-    def load_state_dict(self, sd, strict=True):
-        host = self.param_arena.cpu()
-        missing = [n for n in self.params if n not in sd]
-        if strict and missing:
-            raise KeyError(f"missing keys in state_dict: {missing[:5]}")
-        for name, p in self.params.items():
-            if name in sd:
-                host[p.offset:p.offset + p.numel] = self._to_arena(p, sd[name])
-        self.param_arena.copy_(host)
-        self.refresh_shadow()
-        return missing
-
-    def state_dict(self):
-        host = self.param_arena.cpu()
-        return OrderedDict((n, self._from_arena(p, host[p.offset:p.offset + p.numel])) for n, p in self.params.items())
-
-    def named_parameters(self):
-        for name, p in self.params.items():
-            yield name, self.param_arena[p.offset:p.offset + p.numel]
-
-    def parameters(self):
-        for _, v in self.named_parameters():
-            yield v
-
-    def grad_of(self, name):
-        p = self.params[name]
-        return self._from_arena(p, self.grad_arena[p.offset:p.offset + p.numel].cpu())
-
-    def refresh_shadow(self):
-        hip.check(self.lib.icamd_f32_to_bf16(self.param_arena.data_ptr(), self.shadow.data_ptr(), self.n_params,
-                                             hip.stream_ptr()), "f32_to_bf16")
-        self.refresh_transposed()
-
-    def refresh_transposed(self):
-        hip.check(self.lib.icamd_filter_transpose_tiled(self.shadow.data_ptr(), self.shadow_t.data_ptr(),
-                                                        self._tr_descs.data_ptr(), self._tr_tjobs.data_ptr(), self._tr_ntjobs,
-                                                        hip.stream_ptr()), "filter_transpose_tiled")
-
-    def train(self, mode=True):
-        self.training = bool(mode)
-        return self
-
-    def eval(self):
-        return self.train(False)
-
-    def to(self, *a, **k):
-        return self
 
     # ------------------------------------------------------------------ workspace
     def _workspace(self, B):
@@ -322,26 +185,10 @@ class VisionTransformer(PicklableModel):
         return d
 
     # ------------------------------------------------------------------ helpers
-    def _pf(self, p):
-        return self.param_arena.data_ptr() + 4 * p.offset
-
-    def _gf(self, p):
-        return self.grad_arena.data_ptr() + 4 * p.offset
-
-    def _w(self, l):
-        return self.shadow.data_ptr() + 2 * l.w.offset
-
-    def _wt(self, l):
-        return self.shadow_t.data_ptr() + 2 * l.wt_offset
-
     def pack(self, x_nchw, mix=None):
         B, C, H, W = x_nchw.shape
         assert H == self.img_size and W == self.img_size, "ViT position embedding is built for a fixed input size"
-        ws = self._workspace(B)
-        mode, lam, box = (0, 1.0, (0, 0, 0, 0)) if mix is None else mix
-        hip.check(self.lib.icamd_pack_input(x_nchw.data_ptr(), ws["x8"].data_ptr(), B, C, H, W, mode, float(lam), int(box[0]),
-                                            int(box[1]), int(box[2]), int(box[3]), hip.stream_ptr()), "pack")
-        return ws
+        return self._pack_input(self._workspace(B), x_nchw, mix)
 
     def _linear(self, l, x, y, rows, addend, s):
         hip.check(self.lib.icamd_conv2d_fwd(ctypes.byref(l.desc(rows)), x.data_ptr(), self._w(l), y.data_ptr(), self._pf(l.b),
@@ -384,10 +231,6 @@ class VisionTransformer(PicklableModel):
                                           LN_EPS, s), "norm")
         self._linear(self.head, ws["pooled"], ws["logits"], B, None, s)
         return ws["logits"]
-
-    def __call__(self, x_nchw):
-        ws = self.pack(x_nchw.to(self.device, dtype=torch.float32).contiguous())
-        return self.forward_packed(ws)[:, : self.num_classes]
 
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False):

@@ -115,6 +115,7 @@ def test_switched_route_against_default(r50, monkeypatch, switch):
     32 x 128 x 128 signed values per channel; the second-worst tensors are bn1.weight at 1.24e-2 and layer1.0.bn1.weight at
     2.03e-2.  Twice either worst figure would pass 0.1, so the cap is what is asserted for them."""
     import imageclassification_amd.nets as nets
+    from imageclassification_amd.arena import from_arena
     from oracle import ops_ref as R
     net, ws, default = r50
     value, worst_measured, mean_measured = MEASURED[switch]
@@ -126,7 +127,7 @@ def test_switched_route_against_default(r50, monkeypatch, switch):
     errs = []
     for name, p in net.params.items():
         sl = slice(p.offset, p.offset + p.numel)
-        errs.append((float(R.rel_l2(net._from_arena_layout(p, got[sl]), net._from_arena_layout(p, want[sl]))), name))
+        errs.append((float(R.rel_l2(from_arena(p, got[sl]), from_arena(p, want[sl]))), name))
     worst, mean = max(errs), sum(e for e, _ in errs) / len(errs)
     print(f"{switch}={value} against the default route, {len(errs)} tensors: worst {worst[1]} {worst[0]:.3e}, mean {mean:.3e}, "
           f"bit-equal tensors {sum(e == 0.0 for e, _ in errs)}; five worst {sorted(errs, reverse=True)[:5]}")
