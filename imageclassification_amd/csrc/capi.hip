@@ -34,7 +34,7 @@ int icamd_bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* me
                                int C, int* nblk_out, hipStream_t s);
 // Swin: window attention, relative-position bias, patch merging (window_attention.hip)
 bool icamd_window_attention_ok(int Hs, int Ws, int ws, int D);
-int icamd_window_attention_bwd_chunks(long long nwin, int H);
+int icamd_window_attention_bwd_chunks(long long nwin, int H, int ws);
 int icamd_window_attention_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
                                       int ws, int shift, float scale, hipStream_t s);
 int icamd_window_attention_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout, const float* lse,
@@ -1342,7 +1342,7 @@ int icamd_window_attention_fwd(const void* qkv, const float* bias, void* out, fl
 size_t icamd_window_attention_bwd_workspace_bytes(int B, int Hs, int Ws, int H, int ws) {
   if (B <= 0 || H <= 0 || !icamd_window_attention_ok(Hs, Ws, ws, 32)) return 0;
   const long long nwin = (long long)B * (Hs / ws) * (Ws / ws);
-  return align_up((size_t)icamd_window_attention_bwd_chunks(nwin, H) * H * ws * ws * ws * ws * sizeof(float), 256);
+  return align_up((size_t)icamd_window_attention_bwd_chunks(nwin, H, ws) * H * ws * ws * ws * ws * sizeof(float), 256);
 }
 
 int icamd_window_attention_bwd(const void* qkv, const float* bias, const void* out, const void* dout, const float* lse,
@@ -1365,14 +1365,14 @@ int icamd_window_attention_bwd(const void* qkv, const float* bias, const void* o
 int icamd_relpos_bias_gather(const float* table, float* bias, int H, int ws, void* stream) {
   ProfScope _prof(PC_MISC, stream);
   if (table == nullptr || bias == nullptr || H <= 0) return ICAMD_ERR_BAD_ARG;
-  if (ws < 2 || ws > 8) return ICAMD_ERR_UNSUPPORTED;
+  if ((ws < 2 || ws > 8) && ws != 12) return ICAMD_ERR_UNSUPPORTED;
   return icamd_relpos_bias_gather_launch(table, bias, H, ws, (hipStream_t)stream);
 }
 
 int icamd_relpos_bias_scatter(const float* dbias, float* dtable, int H, int ws, int accumulate, void* stream) {
   ProfScope _prof(PC_MISC, stream);
   if (dbias == nullptr || dtable == nullptr || H <= 0) return ICAMD_ERR_BAD_ARG;
-  if (ws < 2 || ws > 8) return ICAMD_ERR_UNSUPPORTED;
+  if ((ws < 2 || ws > 8) && ws != 12) return ICAMD_ERR_UNSUPPORTED;
   return icamd_relpos_bias_scatter_launch(dbias, dtable, H, ws, accumulate, (hipStream_t)stream);
 }
 

@@ -11,6 +11,8 @@
 // grid (win_token below; imageclassification_amd/swin.py window_geometry is the host-side statement of the same rule and the tests
 // compare the two).  No permuted copy of an activation and no mask tensor exists.
 //
+// Windows of side 2..8; 12 x 12 windows are window_attention_w12.hip's, reached through the launch functions below.
+//
 // Execution: ONE WAVE owns one (window, head) pair at a time -- T = ws^2 <= 64 tokens is a single 64 x 64 score tile, i.e. 4 x 4
 // MFMA tiles of v_mfma_f32_16x16x32_bf16, and with D = 32 one k-step covers q k^T.  A workgroup is four such waves with the SAME
 // head: blockIdx.y is the head, blockIdx.x a chunk of windows, and bias[h] ([T][T] fp32, at most 16 KB) is staged into LDS once per
@@ -589,12 +591,22 @@ int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 }  // namespace
 
+// 12 x 12 windows (T = 144: nine MFMA blocks per side) run on the kernels of window_attention_w12.hip
+constexpr int WS12 = 12;
+int icamd_window_attention_w12_bwd_chunks(long long nwin, int H);
+int icamd_window_attention_w12_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
+                                          int shift, float scale, hipStream_t s);
+int icamd_window_attention_w12_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout,
+                                          const float* lse, bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs,
+                                          int Ws, int H, int shift, float scale, hipStream_t s);
+
 bool icamd_window_attention_ok(int Hs, int Ws, int ws, int D) {
-  return D == WD && ws >= 2 && ws <= 8 && Hs > 0 && Ws > 0 && Hs % ws == 0 && Ws % ws == 0;
+  return D == WD && ((ws >= 2 && ws <= 8) || ws == WS12) && Hs > 0 && Ws > 0 && Hs % ws == 0 && Ws % ws == 0;
 }
 
 // workgroups per head of the backward (= dbias partials per head): a function of the problem shape only
-int icamd_window_attention_bwd_chunks(long long nwin, int H) {
+int icamd_window_attention_bwd_chunks(long long nwin, int H, int ws) {
+  if (ws == WS12) return icamd_window_attention_w12_bwd_chunks(nwin, H);
   const long long by_windows = (nwin + WWAVES - 1) / WWAVES;
   const long long cap = 1024 / H > 1 ? 1024 / H : 1;
   return (int)(by_windows < cap ? by_windows : cap);
@@ -602,6 +614,7 @@ int icamd_window_attention_bwd_chunks(long long nwin, int H) {
 
 int icamd_window_attention_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
                                       int ws, int shift, float scale, hipStream_t s) {
+  if (ws == WS12) return icamd_window_attention_w12_fwd_launch(qkv, bias, out, lse, B, Hs, Ws, H, shift, scale, s);
   const WinGeom G = make_geom(Hs, Ws, H, ws, shift);
   const long long nwin = (long long)B * G.nW;
   const long long by_windows = (nwin + WWAVES - 1) / WWAVES;
@@ -614,9 +627,11 @@ int icamd_window_attention_fwd_launch(const bf16_t* qkv, const float* bias, bf16
 int icamd_window_attention_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout, const float* lse,
                                       bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs, int Ws, int H, int ws,
                                       int shift, float scale, hipStream_t s) {
+  if (ws == WS12)
+    return icamd_window_attention_w12_bwd_launch(qkv, bias, out, dout, lse, dqkv, dbias, accumulate, part, B, Hs, Ws, H, shift, scale, s);
   const WinGeom G = make_geom(Hs, Ws, H, ws, shift);
   const long long nwin = (long long)B * G.nW;
-  const int P = icamd_window_attention_bwd_chunks(nwin, H);
+  const int P = icamd_window_attention_bwd_chunks(nwin, H, ws);
   hipLaunchKernelGGL(winattn_bwd_kernel, dim3((unsigned)P, (unsigned)H), dim3(WTHREADS), 0, s, qkv, bias, out, dout, lse, dqkv, part, G,
                      (int)nwin, scale);
   const int n = H * G.T * G.T;

@@ -148,7 +148,7 @@ _SIGNATURES = {
     # (csrc/attention_long.hip); ICAMD_ATTN_LONG=2 forces the tiled route for every T, 0 disables it (see include/icamd.h)
     "icamd_attention_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
     "icamd_attention_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P]),
-    # Swin (csrc/window_attention.hip): shifted-window attention over the natural token order (D = 32, 2 <= window <= 8), the
+    # Swin (csrc/window_attention.hip): shifted-window attention over the natural token order (D = 32, 2 <= window <= 8 or window 12), the
     # relative-position table <-> bias gather / scatter, patch merging fused with its LayerNorm (4C <= 2048)
     "icamd_window_attention_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "icamd_window_attention_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, _P]),

@@ -1,10 +1,11 @@
-"""Swin Transformer (timm `swin_*_patch4_window7_224`) on the gfx950 kernels: hand-written forward and backward.
+"""Swin Transformer (timm `swin_*_patch4_window7_224` and `swin_base_patch4_window12_384`) on the gfx950 kernels: hand-written
+forward and backward.
 
 The reference builds every model with timm.create_model(args.model) (/root/reference/train.py:194).  Architecture restated from
 the published source (timm is absent; parity is against tests/_swin_ref.py, "timm-unpinned" like ViT and ResNet here):
 4x4/4 patch-embedding conv + bias and a LayerNorm, four stages of pre-LayerNorm blocks (eps 1e-5) whose attention runs inside
-7x7 windows with 32-wide heads, a learned relative-position bias and, in every second block, a cyclic shift by 3 with its region
-mask; stage i > 0 opens with patch merging (2x2 gather -> LayerNorm(4C) -> bias-free Linear 4C -> 2C, current timm's placement);
+7x7 (or 12x12: CONFIGS_W12) windows with 32-wide heads, a learned relative-position bias and, in every second block, a cyclic
+shift by half the window with its region mask; stage i > 0 opens with patch merging (2x2 gather -> LayerNorm(4C) -> bias-free Linear 4C -> 2C, current timm's placement);
 final LayerNorm, mean over tokens, linear head.  Parameter names follow timm: `patch_embed.{proj,norm}.*`,
 `layers.I.downsample.{norm,reduction}.*`, `layers.I.blocks.J.{norm1,attn.relative_position_bias_table,attn.qkv,attn.proj,norm2,
 mlp.fc1,mlp.fc2}.*`, `norm.*`, `head.fc.*`.  The relative-position index and the attention mask are not state: the kernels compute
@@ -35,7 +36,23 @@ CONFIGS = {
     "swin_base_patch4_window7_224": (128, (2, 2, 18, 2), (4, 8, 16, 32), 7),
     "swin_test": (32, (2, 2), (1, 2), 7),   # small configuration for parity tests (56^2 input: 14^2 then 7^2 tokens)
 }
+# the window-12 models, fine-tuned at 384 x 384 in the paper (a table of their own: CONFIGS is what the window-7 tests enumerate)
+CONFIGS_W12 = {
+    "swin_base_patch4_window12_384": (128, (2, 2, 18, 2), (4, 8, 16, 32), 12),
+    "swin_test_w12": (32, (2, 2), (1, 2), 12),   # parity tests (96^2 input: 24^2 then 12^2 tokens; 192^2: 48^2 then 24^2)
+}
+# names that carry their input size are built at that size when none is given (every other name: 224)
+NATIVE_SIZE = {"swin_base_patch4_window12_384": 384}
 PATCH = 4
+
+
+def config(arch):
+    """(embed dim, depths, heads, window) of a name of either table; KeyError for any other"""
+    return CONFIGS[arch] if arch in CONFIGS else CONFIGS_W12[arch]
+
+
+def native_size(arch):
+    return NATIVE_SIZE.get(arch, 224)
 
 
 # ---------------------------------------------------------------------------------------------------- host-side geometry (no GPU)
@@ -70,11 +87,12 @@ def relative_position_index(ws):
     return ((dr + ws - 1) * (2 * ws - 1) + dc + ws - 1).long()
 
 
-def stage_plan(arch, img_size=224):
-    """[(tokens per side, window, shift of the odd blocks)] per stage; raises ValueError for an input size the windows do not tile."""
-    embed, depths, heads, window = CONFIGS[arch]
+def stage_plan(arch, img_size=None):
+    """[(tokens per side, window, shift of the odd blocks)] per stage; raises ValueError for an input size the windows do not tile.
+    img_size None: the name's own size."""
+    embed, depths, heads, window = config(arch)
     if img_size is None:
-        img_size = 224
+        img_size = native_size(arch)
     if img_size < PATCH or img_size % PATCH:
         raise ValueError(f"img_size {img_size} is not a positive multiple of the patch size {PATCH}")
     res = img_size // PATCH
@@ -91,15 +109,16 @@ def stage_plan(arch, img_size=224):
             plan.append((res, window, window // 2))
         else:
             raise ValueError(f"{arch} at {img_size}x{img_size}: every stage's resolution must be a multiple of the window, or <= the "
-                             f"window; stage {i} has {res} tokens per side and the window is {window} (224 and 448 work, 384 does not)")
+                             f"window; stage {i} has {res} tokens per side and the window is {window} " +
+                             ("(224 and 448 work, 384 does not)" if window == 7 else "(192 and 384 work, 224 does not)"))
         if plan[-1][1] < 2:
             raise ValueError(f"{arch} at {img_size}x{img_size}: stage {i} has a single token")
     return plan
 
 
-def _param_list(arch, num_classes, img_size=224):
+def _param_list(arch, num_classes, img_size=None):
     """(name, torch shape, kind) of every parameter, in timm's order."""
-    embed, depths, heads, _ = CONFIGS[arch]
+    embed, depths, heads, _ = config(arch)
     plan = stage_plan(arch, img_size)
     out = [("patch_embed.proj.weight", (embed, 3, PATCH, PATCH), "conv"), ("patch_embed.proj.bias", (embed,), "vec"),
            ("patch_embed.norm.weight", (embed,), "vec"), ("patch_embed.norm.bias", (embed,), "vec")]
@@ -125,7 +144,7 @@ def _param_list(arch, num_classes, img_size=224):
     return out
 
 
-def param_shapes(arch, num_classes=1000, img_size=224):
+def param_shapes(arch, num_classes=1000, img_size=None):
     """OrderedDict name -> shape of every parameter (what state_dict() holds), without a GPU."""
     return OrderedDict((n, tuple(s)) for n, s, _ in _param_list(arch, num_classes, img_size))
 
@@ -135,8 +154,8 @@ class SwinTransformer(ArenaModel):
                  seed=None):
         self.plan = stage_plan(arch, img_size)          # before anything touches the GPU: a bad size is a ValueError everywhere
         super().__init__(arch, num_classes, device)
-        self.embed, self.depths, self.heads, self.window = CONFIGS[arch]
-        self.img_size = 224 if img_size is None else img_size
+        self.embed, self.depths, self.heads, self.window = config(arch)
+        self.img_size = native_size(arch) if img_size is None else img_size
         self.drop_path_rate = drop_path_rate
         self.injected_keep = None     # tests: list of per-branch keep tensors (float [B], two per block) used instead of drawing
         self._build()

@@ -337,7 +337,8 @@ int icamd_attention_fwd(const void* qkv, void* out, float* lse, int B, int T, in
 int icamd_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                         int B, int T, int H, int D, float scale, void* stream);
 
-/* ---- Swin Transformer (timm swin_*_patch4_window7_224 under the same reference calls; csrc/window_attention.hip) --------
+/* ---- Swin Transformer (timm swin_*_patch4_window7_224 and swin_base_patch4_window12_384 under the same reference calls;
+ * csrc/window_attention.hip, 12 x 12 windows csrc/window_attention_w12.hip) ----------------------------------------------
  * Shifted-window attention over ws x ws windows of a [B][Hs][Ws] token grid, H heads of D = 32:
  *   qkv  bf16 [B][Hs][Ws][3*H*D] in the NATURAL token order (q | k | v, each [head][D]: timm's reshape(B_, N, 3, heads, -1));
  *   bias fp32 [H][ws^2][ws^2] (the gathered relative-position bias);  out bf16 [B][Hs][Ws][H*D], natural order;
@@ -346,8 +347,8 @@ int icamd_attention_bwd(const void* qkv, const void* out, const void* dout, cons
  * the roll back are address arithmetic in the kernel; for shift > 0 two tokens of a window get -100 added to their score when
  * their region ids on the rolled grid differ (per axis the slices [0, L-ws), [L-ws, L-shift), [L-shift, L); id = 3 * row slice
  * + column slice: timm's img_mask) -- computed from the coordinates, no mask tensor is read.
- * _supported: 1 for D == 32, 2 <= ws <= 8, Hs % ws == 0, Ws % ws == 0; the calls also need 0 <= shift < ws.  Anything else
- * returns ICAMD_ERR_UNSUPPORTED and writes nothing.
+ * _supported: D == 32 and (2 <= ws <= 8 or ws == 12), Hs % ws == 0, Ws % ws == 0; the calls also need 0 <= shift < ws.
+ * Anything else (ws 9..11, 13, 16, ...) returns ICAMD_ERR_UNSUPPORTED and writes nothing.
  * bwd: dqkv bf16 in the layout of qkv; dbias fp32 [H][ws^2][ws^2] (+)= the sum over all images and windows of dS (the gradient
  * of the scores after the scale, taken in fp32 before dS is rounded for its products).  workspace: _bwd_workspace_bytes, no
  * initialisation needed (per-workgroup partials, folded in a fixed order by a second launch).  No atomics: bitwise repeatable. */
@@ -360,7 +361,8 @@ int icamd_window_attention_bwd(const void* qkv, const float* bias, const void* o
                                int Ws, int H, int D, int ws, int shift, float scale, void* stream);
 /* table fp32 [(2 ws - 1)^2][H] (timm relative_position_bias_table) <-> bias fp32 [H][ws^2][ws^2]:
  * bias[h][i][j] = table[(dr + ws - 1) * (2 ws - 1) + (dc + ws - 1)][h], (dr, dc) = coordinates of i minus coordinates of j.
- * scatter: dtable (+)= the transpose of the gather applied to dbias, pairs summed in increasing (i, j) order.  2 <= ws <= 8. */
+ * scatter: dtable (+)= the transpose of the gather applied to dbias, pairs summed in increasing (i, j) order.  2 <= ws <= 8 or ws == 12
+ * (table [529][H] <-> bias [H][144][144]). */
 int icamd_relpos_bias_gather(const float* table, float* bias, int H, int ws, void* stream);
 int icamd_relpos_bias_scatter(const float* dbias, float* dtable, int H, int ws, int accumulate, void* stream);
 /* Patch merging + LayerNorm: x bf16 [N][H][W][C] (H, W even) -> y bf16 [N*H/2*W/2][4C] = LayerNorm over 4C of the gathered row,

@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Times Swin-T on the gfx950 kernels, batch 256 at 224 x 224:
+"""Times a Swin model on the gfx950 kernels (default: Swin-T, batch 256 at 224 x 224; --arch swin_base_patch4_window12_384 --hw 384
+--batch 64 for the window-12 model):
 
   * the whole training step through engine.train_one_epoch on synthetic data with bench.py's recipe (AdamW, label smoothing 0.1,
     1000 classes, --steps after --warmup);
-  * the window attention kernels (csrc/window_attention.hip) alone at Swin-T's four stage shapes (56 / 28 / 14 / 7 tokens per side,
-    3 / 6 / 12 / 24 heads; odd blocks' shift 3, none at 7), forward and backward, and patch merging + LayerNorm at its three shapes,
+  * the window attention kernels (csrc/window_attention.hip, csrc/window_attention_w12.hip) alone at the model's stage shapes
+    (Swin-T: 56 / 28 / 14 / 7 tokens per side, 3 / 6 / 12 / 24 heads; odd blocks' shift 3, none at 7), forward and backward, and patch
+    merging + LayerNorm at its shapes,
     beside two yardsticks taken in the same session:
       - a byte roof: algorithmic bytes (every operand read once, every result written once) divided by the streaming bandwidth
         tools/bench_bn.py reports for icamd_bn_apply (read y, write a) -- it is run first, as a child process;
@@ -14,6 +16,7 @@
 Method: device events around `reps` back-to-back launches after `warmup` launches, `rounds` rounds, the median round reported.
 
     python tools/bench_swin.py [--steps 20] [--warmup 5] [--batch 256] > profiles/swin.txt
+    python tools/bench_swin.py --arch swin_base_patch4_window12_384 --hw 384 --batch 64 > profiles/swin_w12.txt
 """
 import argparse
 import contextlib
@@ -31,10 +34,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from imageclassification_amd import hip  # noqa: E402
-from imageclassification_amd.swin import relative_position_index, window_geometry  # noqa: E402
+from imageclassification_amd.swin import config, relative_position_index, stage_plan, window_geometry  # noqa: E402
 
 D = 32
-STAGES = [(56, 3, 96), (28, 6, 192), (14, 12, 384), (7, 24, 768)]   # tokens per side, heads, channels
+
+
+def stages_of(arch, hw):
+    """[(tokens per side, heads, channels, window, shift of the odd blocks)] per stage; Swin-T at 224: (56, 3, 96, 7, 3) ..."""
+    embed, _, heads, _ = config(arch)
+    return [(res, heads[i], embed << i, ws, shift) for i, (res, ws, shift) in enumerate(stage_plan(arch, hw))]
 
 
 def timed(fn, warmup, reps):
@@ -97,7 +105,7 @@ def step_time(args):
     from imageclassification_amd.utils import NativeScalerWithGradNormCount, cosine_scheduler
     dev = torch.device("cuda")
     C, B = 1000, args.batch
-    net = SwinTransformer("swin_tiny_patch4_window7_224", C, seed=88)       # drop_path_rate: the class default (0.1)
+    net = SwinTransformer(args.arch, C, img_size=args.hw, seed=88)          # drop_path_rate: the class default (0.1)
     opt = create_optimizer("adamw", 1e-3, 5e-4, net)
     crit = LabelSmoothingCrossEntropy(0.1)
     total = args.warmup + args.steps
@@ -106,7 +114,7 @@ def step_time(args):
         lr = cosine_scheduler(1e-3, 1e-6, 1, total, warmup_epochs=0)
         wd = cosine_scheduler(5e-4, 5e-6, 1, total)
     g = torch.Generator(device=dev).manual_seed(88)
-    pool = [(torch.randn(B, 3, 224, 224, generator=g, device=dev), torch.randint(0, C, (B,), generator=g, device=dev)) for _ in range(2)]
+    pool = [(torch.randn(B, 3, args.hw, args.hw, generator=g, device=dev), torch.randint(0, C, (B,), generator=g, device=dev)) for _ in range(2)]
 
     def run(n, start):
         loader = [pool[i % 2] for i in range(n)]
@@ -121,7 +129,7 @@ def step_time(args):
     stats = run(args.steps, args.warmup)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(f"swin_tiny_patch4_window7_224 training step, batch {B}, drop_path 0.1: {1e3 * dt / args.steps:.2f} ms/step, "
+    print(f"{args.arch} training step, batch {B}, drop_path 0.1: {1e3 * dt / args.steps:.2f} ms/step, "
           f"{B * args.steps / dt:.0f} img/s over {args.steps} steps after {args.warmup} (loss {stats['loss']:.4f})")
     del net, opt, pool
     torch.cuda.empty_cache()
@@ -132,6 +140,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--arch", default="swin_tiny_patch4_window7_224")
+    ap.add_argument("--hw", type=int, default=224, help="input height = width")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--kwarmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
@@ -143,7 +153,8 @@ def main():
     dev = "cuda"
     s = hip.stream_ptr()
     B = args.batch
-    print(f"# Swin-T, batch {B}; {torch.cuda.get_device_name(0)}")
+    stages = stages_of(args.arch, args.hw)
+    print(f"# {args.arch} at {args.hw} x {args.hw}, batch {B}; {torch.cuda.get_device_name(0)}")
     if not args.no_step:
         step_time(args)
     print(f"# kernels: {args.reps} launches per measurement after {args.kwarmup}, median of {args.rounds} rounds; byte roof = "
@@ -155,10 +166,9 @@ def main():
 
     print("# window attention              op          us  alg_GB/s   roof_us  roof%   torch_us torch/ours")
     slower = []
-    for res, H, _ in STAGES:
-        ws = 7
+    for res, H, _, ws, odd_shift in stages:
         T = ws * ws
-        for shift in ((0, 3) if res > ws else (0,)):
+        for shift in ((0, odd_shift) if odd_shift else (0,)):
             g = torch.Generator(device=dev).manual_seed(1)
             qkv = torch.randn(B, res, res, 3 * H * D, generator=g, device=dev).to(torch.bfloat16)
             dout = torch.randn(B, res, res, H * D, generator=g, device=dev).to(torch.bfloat16)
@@ -223,7 +233,7 @@ def main():
         print("# faster than torch's route at every shape above (torch's backward = its forward + backward minus its forward)")
 
     print("# patch merging + LayerNorm     op          us  alg_GB/s   roof_us  roof%")
-    for res, _, C in STAGES[:3]:
+    for res, _, C, _, _ in stages[:-1]:
         g = torch.Generator(device=dev).manual_seed(2)
         x = torch.randn(B, res, res, C, generator=g, device=dev).to(torch.bfloat16)
         rows = B * (res // 2) ** 2

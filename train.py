@@ -26,7 +26,8 @@ from imageclassification_amd.mixup import CrossEntropyLoss, LabelSmoothingCrossE
 from imageclassification_amd.nets import ARCHS, ResNet
 from imageclassification_amd.vit import CONFIGS as VIT_CONFIGS, NATIVE_SIZE as VIT_NATIVE_SIZE, VisionTransformer
 from imageclassification_amd.convnext import CONFIGS as CNX_CONFIGS, ConvNeXt
-from imageclassification_amd.swin import CONFIGS as SWIN_CONFIGS, SwinTransformer
+from imageclassification_amd.swin import (CONFIGS as SWIN_CONFIGS, CONFIGS_W12 as SWIN_CONFIGS_W12, NATIVE_SIZE as SWIN_NATIVE_SIZE,
+                                          SwinTransformer)
 from imageclassification_amd.optim_factory import create_optimizer
 from imageclassification_amd.utils import NativeScalerWithGradNormCount as NativeScaler
 
@@ -91,11 +92,15 @@ def create_model(name, num_classes, input_size=None, drop_path=0.0):
         return VisionTransformer(name, num_classes, img_size=input_size)   # None: the name's own size (224 unless it says 384)
     if name in CNX_CONFIGS:
         return ConvNeXt(name, num_classes, drop_path_rate=drop_path)   # reference train.py:189-192
-    if name in SWIN_CONFIGS:
+    if name in SWIN_CONFIGS or name in SWIN_CONFIGS_W12:
+        native = SWIN_NATIVE_SIZE.get(name)   # swin_base_patch4_window12_384 carries its size, like vit_*_384 above
+        if native is not None and input_size not in (None, native):
+            raise ValueError(f"model '{name}' is built for {native}x{native} inputs, not --input_size {input_size}: pass "
+                             f"--input_size {native}")
         # the reference passes --drop_path to convnext* / efficientvit* only (train.py:189-192): Swin keeps its own default (timm: 0.1)
-        # a size the 7x7 windows do not tile (384) is the constructor's ValueError, raised before any device work
+        # a size the windows do not tile (384 for 7x7, 224 for 12x12) is the constructor's ValueError, raised before any device work
         return SwinTransformer(name, num_classes, img_size=input_size)
-    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS)})")
+    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS) + sorted(SWIN_CONFIGS_W12)})")
 
 
 def main(args):
