@@ -7,7 +7,8 @@ Linear -> gamma -> drop_path -> residual; stem 4x4/4 conv + channels-first LN :7
 names are used here: `stem.{0,1}`, `stages.S.downsample.{0,1}`, `stages.S.blocks.B.{conv_dw,norm,mlp.fc1,mlp.fc2,gamma}`,
 `head.{norm,fc}`.  Stochastic depth follows timm: linearly increasing rates up to `drop_path_rate`
 (train.py:189-192 passes --drop_path, default 0.05), per-sample masks drawn on the host from torch's RNG.  The flat arenas are
-arena.py's.
+arena.py's; the GEMM and LayerNorm steps of both passes (blocks.Forward, blocks.Backward: weight gradients on the side lane, the
+waits before a buffer is overwritten) are blocks.py's.  The block itself is written here.
 
 NHWC activations make every "channels-first LayerNorm" an ordinary row LayerNorm over pixels, and every Linear a 1x1
 convolution on the same tensor (bias fused); the depthwise stencil and the layer-scale tail are dedicated kernels.
@@ -20,6 +21,7 @@ import torch
 
 from . import hip
 from .arena import ArenaModel, Layout, align
+from .blocks import Backward, Forward, loss_workspace
 from .streams import side_lane
 
 LN_EPS = 1e-6
@@ -231,10 +233,7 @@ class ConvNeXt(ArenaModel):
         ws["pool"] = act(N, dl)
         ws["pn"] = act(N, dl)
         ws["st_head"] = f32(2 * N)
-        ws["logits"] = torch.zeros(N, self.ncls_p, dtype=torch.bfloat16, device=dev)
-        ws["dlogits"] = torch.zeros(N, self.ncls_p, dtype=torch.bfloat16, device=dev)
-        ws["loss_rows"] = f32(N)
-        ws["pred"] = torch.empty(N, dtype=torch.int32, device=dev)
+        loss_workspace(ws, N, self.ncls_p, dev)
         wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(self.head.desc(N, 1, 1))))
         ws["wg_ws"] = torch.empty(wg, dtype=torch.uint8, device=dev)
         ws["wg_bytes"] = wg
@@ -260,28 +259,21 @@ class ConvNeXt(ArenaModel):
             ws["g"] = [torch.empty(ws["max_act"], dtype=torch.bfloat16, device=self.device) for _ in range(5)]
         return ws["g"]
 
-    # ------------------------------------------------------------------ helpers
     def pack(self, x_nchw, mix=None):
         N, C, H, W = x_nchw.shape
         return self._pack_input(self._workspace(N, H, W), x_nchw, mix)
-
-    def _conv(self, c, x_ptr, y, N, H, W, s):
-        hip.check(self.lib.icamd_conv2d_fwd(ctypes.byref(c.desc(N, H, W)), x_ptr, self._w(c), y.data_ptr(), self._pf(c.b), None,
-                                            None, s), c.name)
-
-    def _ln(self, x, wp, bp, y, st, rows, C, s):
-        hip.check(self.lib.icamd_layernorm_fwd(x.data_ptr(), self._pf(wp), self._pf(bp), y.data_ptr(), st.data_ptr(),
-                                               st.data_ptr() + 4 * rows, rows, C, LN_EPS, s), wp.name)
 
     # ------------------------------------------------------------------ forward
     def forward_packed(self, ws, logits_only=False):
         """logits_only: a forward whose activations no backward will read (the reference's second, accuracy-only forward under
         mixup): tensors kept only for the backward pass (the pre-GELU Mlp activations) are not written."""
-        lib, s = self.lib, hip.stream_ptr()
+        f = Forward(self, ws, LN_EPS, logits_only)
+        lib, s = self.lib, f.s
         N, H, W = ws["N"], ws["H"], ws["W"]
-        self._conv(self.stem, ws["x8"].data_ptr(), ws["s"], N, H, W, s)
+        f.linear(self.stem, self.stem.desc(N, H, W), ws["x8"].data_ptr(), ws["s"].data_ptr())
         h, w = H // 4, W // 4
-        self._ln(ws["s"], self.stem_nw, self.stem_nb, ws["x0"], ws["st_stem"], N * h * w, self.dims[0], s)
+        f.layernorm(ws["s"].data_ptr(), self.stem_nw, self.stem_nb, ws["x0"].data_ptr(), ws["st_stem"].data_ptr(), N * h * w,
+                    self.dims[0])
         x = ws["x0"]
         bi = 0
         drop_rows = None      # stochastic depth: every block's mask for this step
@@ -293,8 +285,9 @@ class ConvNeXt(ArenaModel):
             dim = st["dim"]
             if si > 0:
                 sw["in"] = x
-                self._ln(x, st["ds_nw"], st["ds_nb"], sw["ln"], sw["st"], N * h * w, self.dims[si - 1], s)
-                self._conv(st["ds"], sw["ln"].data_ptr(), sw["x"], N, h, w, s)
+                f.layernorm(x.data_ptr(), st["ds_nw"], st["ds_nb"], sw["ln"].data_ptr(), sw["st"].data_ptr(), N * h * w,
+                            self.dims[si - 1])
+                f.linear(st["ds"], st["ds"].desc(N, h, w), sw["ln"].data_ptr(), sw["x"].data_ptr())
                 h, w = h // 2, w // 2
                 x = sw["x"]
             rows = N * h * w
@@ -302,10 +295,9 @@ class ConvNeXt(ArenaModel):
                 b["in"] = x
                 hip.check(lib.icamd_dwconv7_fwd(x.data_ptr(), self.shadow.data_ptr() + 2 * blk["dw_w"].offset,
                                                 self._pf(blk["dw_b"]), b["d"].data_ptr(), N, h, w, dim, s), blk["name"] + " dw")
-                self._ln(b["d"], blk["nw"], blk["nb"], b["h"], b["st"], rows, dim, s)
-                c1 = blk["fc1"]                                                   # z1 = pwconv1(h), a = gelu(z1): one kernel
-                hip.check(lib.icamd_conv2d_fwd_gelu(ctypes.byref(c1.desc(N, h, w)), b["h"].data_ptr(), self._w(c1),
-                                                    (None if logits_only else b["z1"].data_ptr()), b["a"].data_ptr(), self._pf(c1.b), s), c1.name + " + gelu")
+                f.layernorm(b["d"].data_ptr(), blk["nw"], blk["nb"], b["h"].data_ptr(), b["st"].data_ptr(), rows, dim)
+                # z1 = pwconv1(h), a = gelu(z1): one kernel
+                f.linear_gelu(blk["fc1"], blk["fc1"].desc(N, h, w), b["h"].data_ptr(), b["z1"].data_ptr(), b["a"].data_ptr())
                 keep = None
                 if self.training and blk["rate"] > 0.0:
                     if self.injected_keep is not None:
@@ -324,7 +316,7 @@ class ConvNeXt(ArenaModel):
                         hip.check(lib.icamd_rows_fix(keep.data_ptr(), N, b["out"].data_ptr(), x.data_ptr(), h * w * dim * 2,
                                                      None if logits_only else b["a"].data_ptr(), h * w * dim * 8, s), "drop path")
                 else:
-                    self._conv(blk["fc2"], b["a"].data_ptr(), b["z2"], N, h, w, s)
+                    f.linear(blk["fc2"], blk["fc2"].desc(N, h, w), b["a"].data_ptr(), b["z2"].data_ptr())
                     hip.check(lib.icamd_layerscale_fwd(b["z2"].data_ptr(), x.data_ptr(), self._pf(blk["gamma"]),
                                                        None if keep is None else keep.data_ptr(), b["out"].data_ptr(), rows, dim,
                                                        h * w, s), "layer scale")
@@ -332,8 +324,8 @@ class ConvNeXt(ArenaModel):
                 bi += 1
         dl = self.dims[-1]
         hip.check(lib.icamd_avgpool_fwd(x.data_ptr(), ws["pool"].data_ptr(), N, h * w, dl, s), "avgpool")
-        self._ln(ws["pool"], self.head_nw, self.head_nb, ws["pn"], ws["st_head"], N, dl, s)
-        self._conv(self.head, ws["pn"].data_ptr(), ws["logits"], N, 1, 1, s)
+        f.layernorm(ws["pool"].data_ptr(), self.head_nw, self.head_nb, ws["pn"].data_ptr(), ws["st_head"].data_ptr(), N, dl)
+        f.linear(self.head, self.head.desc(N, 1, 1), ws["pn"].data_ptr(), ws["logits"].data_ptr())
         return ws["logits"]
 
     # ------------------------------------------------------------------ backward
@@ -341,45 +333,21 @@ class ConvNeXt(ArenaModel):
         """Backward from ws['dlogits'].  `dfeat` (bf16 NHWC tensor shaped like the last stage's output): start from that
         gradient instead and skip the classification head -- the entry the reference-vector parity test uses, since the
         reference tree's ConvNeXt is the headless backbone."""
-        lib, s = self.lib, hip.stream_ptr()
+        lane = side_lane(self, "ICAMD_WGRAD_STREAM", True)
+        bw = Backward(self, ws, lane, accumulate)
+        lib, s, acc, W = self.lib, bw.s, bw.acc, bw.writes
         N = ws["N"]
-        acc = int(bool(accumulate))
         hook = self.grad_ready_hook
-        wsp, wsb = ws["wg_ws"].data_ptr(), ws["wg_bytes"]
+        wsp, wsb = bw.wg
         dwp, dwb = ws["dwg_ws"].data_ptr(), ws["dwg_bytes"]
-        lnp, lnb = ws["ln_ws"].data_ptr(), ws["ln_bytes"]
         csp, csb = ws["cs_ws"].data_ptr(), ws["cs_bytes"]
         G = [g.data_ptr() for g in self._scratch(ws)]
-
-        lane = side_lane(self, "ICAMD_WGRAD_STREAM", True)
-        lane.begin(getattr(self, "wgrad_side_stream", True))
-
-        def W(ptr):
-            """`ptr` is about to be overwritten on the main stream: wait for side-lane launches still reading it."""
-            lane.before_write(ptr)
-            return ptr
-
-        def gemm_bwd(c, x_ptr, dy_ptr, n, h, w, dx_ptr, gelu_z=None):
-            d = c.desc(n, h, w)
-            lane.launch(lambda st_: hip.check(lib.icamd_conv2d_wgrad_bias(ctypes.byref(d), x_ptr, dy_ptr, self._gf(c.w),
-                                                                          self._gf(c.b), acc, wsp, wsb, st_),
-                                              c.name + " wgrad+bias"), reads=(dy_ptr,))
-            if dx_ptr is not None and gelu_z is None:
-                hip.check(lib.icamd_conv2d_dgrad(ctypes.byref(d), dy_ptr, self._wt(c), W(dx_ptr), None, None, s), c.name + " dgrad")
-            elif dx_ptr is not None:   # dx = (dy W) * gelu'(z) in the data-gradient kernel's store pass
-                hip.check(lib.icamd_conv2d_dgrad_gelu(ctypes.byref(d), dy_ptr, self._wt(c), gelu_z, W(dx_ptr), s),
-                          c.name + " dgrad + gelu bwd")
-
-        def ln_bwd(dy_ptr, x, st, wp, bp, dx_ptr, rows, C):
-            hip.check(lib.icamd_layernorm_bwd(dy_ptr, x.data_ptr(), st.data_ptr(), st.data_ptr() + 4 * rows, self._pf(wp), None,
-                                              W(dx_ptr), self._gf(wp), self._gf(bp), rows, C, acc, lnp, lnb, s), wp.name + " bwd")
-
         dl = self.dims[-1]
         h, w = ws["final_hw"]
         dout = G[0]
         if dfeat is None:
-            gemm_bwd(self.head, ws["pn"].data_ptr(), ws["dlogits"].data_ptr(), N, 1, 1, G[1])
-            ln_bwd(G[1], ws["pool"], ws["st_head"], self.head_nw, self.head_nb, G[2], N, dl)
+            bw.gemm(self.head, self.head.desc(N, 1, 1), ws["pn"].data_ptr(), ws["dlogits"].data_ptr(), G[1])
+            bw.layernorm(G[1], ws["pool"].data_ptr(), ws["st_head"].data_ptr(), self.head_nw, self.head_nb, None, G[2], N, dl)
             hip.check(lib.icamd_avgpool_bwd(G[2], W(dout), N, h * w, dl, s), "avgpool bwd")
         else:
             assert dfeat.dtype == torch.bfloat16 and dfeat.numel() == N * h * w * dl
@@ -421,9 +389,10 @@ class ConvNeXt(ArenaModel):
                 else:
                     hip.check(lib.icamd_layerscale_bwd(dout, b["z2"].data_ptr(), self._pf(blk["gamma"]), keep, W(G[1]),
                                                        self._gf(blk["gamma"]), rows, dim, h * w, acc, csp, csb, s), "layer scale bwd")
-                    gemm_bwd(blk["fc2"], b["a"].data_ptr(), G[1], N, h, w, G[4], gelu_z=b["z1"].data_ptr())   # G4 = d z1
-                gemm_bwd(blk["fc1"], b["h"].data_ptr(), G[4], N, h, w, G[1])                 # G1 = d h
-                ln_bwd(G[1], b["d"], b["st"], blk["nw"], blk["nb"], G[2], rows, dim)         # G2 = d (dwconv out)
+                    bw.gemm(blk["fc2"], blk["fc2"].desc(N, h, w), b["a"].data_ptr(), G[1], G[4], gelu_z=b["z1"].data_ptr())   # G4 = d z1
+                bw.gemm(blk["fc1"], blk["fc1"].desc(N, h, w), b["h"].data_ptr(), G[4], G[1])                         # G1 = d h
+                # G2 = d (dwconv out)
+                bw.layernorm(G[1], b["d"].data_ptr(), b["st"].data_ptr(), blk["nw"], blk["nb"], None, G[2], rows, dim)
                 bin_ptr, g2, hh, ww_, dd = b["in"].data_ptr(), G[2], h, w, dim
                 dwg = self._gf(blk["dw_w"])
                 if lib.icamd_dwconv7_wgrad_bias_supported(N, hh, ww_, dd):   # filter and bias gradient out of one pass over dy
@@ -443,14 +412,16 @@ class ConvNeXt(ArenaModel):
                     hook(blk["dw_w"].offset, None, lane.events())
             if si > 0:
                 prev = self.dims[si - 1]
-                gemm_bwd(st["ds"], sw["ln"].data_ptr(), dout, N, 2 * h, 2 * w, G[1])
+                bw.gemm(st["ds"], st["ds"].desc(N, 2 * h, 2 * w), sw["ln"].data_ptr(), dout, G[1])
                 h, w = 2 * h, 2 * w
-                ln_bwd(G[1], sw["in"], sw["st"], st["ds_nw"], st["ds_nb"], other, N * h * w, prev)
+                bw.layernorm(G[1], sw["in"].data_ptr(), sw["st"].data_ptr(), st["ds_nw"], st["ds_nb"], None, other, N * h * w,
+                             prev)
                 dout, other = other, dout
                 if hook:
                     hook(st["ds_nw"].offset, None, lane.events())
-        ln_bwd(dout, ws["s"], ws["st_stem"], self.stem_nw, self.stem_nb, G[1], N * h * w, self.dims[0])
-        gemm_bwd(self.stem, ws["x8"].data_ptr(), G[1], N, ws["H"], ws["W"], None)
+        bw.layernorm(dout, ws["s"].data_ptr(), ws["st_stem"].data_ptr(), self.stem_nw, self.stem_nb, None, G[1], N * h * w,
+                     self.dims[0])
+        bw.gemm(self.stem, self.stem.desc(N, ws["H"], ws["W"]), ws["x8"].data_ptr(), G[1], None)
         lane.join()
         if hook:
             hook(0, None)

@@ -14,20 +14,26 @@ rules.
 
 Tokens stay in their natural [B][H][W][C] order through the whole network: the window kernels do the roll, the partition and their
 inverses as address arithmetic, so every Linear is the 1x1 case of the convolution kernels on a [rows, 1, 1, C] "image" exactly as in
-vit.py (bias, GELU and the residual add fused in the epilogue).  The flat arenas are arena.py's.  Stochastic depth
+vit.py (bias, GELU and the residual add fused in the epilogue).  The flat arenas are arena.py's; the block and the GEMM / LayerNorm
+steps are blocks.py's, shared with vit.py: this file supplies the window attention launches (with the relative-position scatter),
+patch merging, the bias arena and the loop over stages.  There is no side stream: the lane handed to blocks.Backward is never
+enabled.  Stochastic depth
 is timm's (rates rising linearly to `drop_path_rate`, one per-sample mask per residual branch, drawn on the host by
-ArenaModel._draw_keep and applied with icamd_layerscale_fwd / _bwd and a vector of ones); with rate 0 the residual rides in the GEMM epilogue.
+ArenaModel._draw_keep and applied by the block's keep1 / keep2 path with icamd_layerscale_fwd / _bwd and a vector of ones); with rate 0
+the residual rides in the GEMM epilogue.
 """
 import ctypes
 from collections import OrderedDict
 
 import torch
 
-from . import hip
+from . import hip, streams
 from .arena import ArenaModel, Layout, Lin, align
+from .blocks import Backward, Forward, block_params, block_workspace, lin_builder, loss_workspace, patch_embed_desc
 
 LN_EPS = 1e-5
 HEAD_DIM = 32
+SCALE = HEAD_DIM ** -0.5      # of the attention scores
 
 CONFIGS = {
     # name: (embed dim, depths, heads, window)
@@ -174,15 +180,10 @@ class SwinTransformer(ArenaModel):
                 layout.add(name, shape, kind)
         P = layout.params
         self.lins = []
-
-        def lin(name, cin, cout, cout_p=None, bias=True):
-            l = Lin(name, cin, cout, cout_p)
-            l.w = P[name + ".weight"]
-            l.b = P[name + ".bias"] if bias else None
-            self.lins.append(l)
-            return l
-
-        self.pe_w, self.pe_b = P["patch_embed.proj.weight"], P["patch_embed.proj.bias"]
+        param = lambda name, *shape: P[name]        # everything is laid out already
+        lin = lin_builder(self.lins, param)
+        self.pe = Lin("patch_embed.proj", 8, self.embed)      # the patch-embedding convolution; its descriptor is _pe_desc's
+        self.pe.w, self.pe.b = P["patch_embed.proj.weight"], P["patch_embed.proj.bias"]
         self.pe_nw, self.pe_nb = P["patch_embed.norm.weight"], P["patch_embed.norm.bias"]
         self.stages = []
         nblocks = sum(self.depths)
@@ -200,14 +201,9 @@ class SwinTransformer(ArenaModel):
                 st["ds"] = lin(f"layers.{i}.downsample.reduction", 4 * prev, dim, bias=False)
             for j in range(depth):
                 n = f"layers.{i}.blocks.{j}"
-                blk = {"name": n, "rate": rates[bi], "shift": shift if j % 2 else 0, "bias_off": boff}
-                blk["n1w"], blk["n1b"] = P[f"{n}.norm1.weight"], P[f"{n}.norm1.bias"]
-                blk["table"] = P[f"{n}.attn.relative_position_bias_table"]
-                blk["qkv"] = lin(f"{n}.attn.qkv", dim, 3 * dim)
-                blk["proj"] = lin(f"{n}.attn.proj", dim, dim)
-                blk["n2w"], blk["n2b"] = P[f"{n}.norm2.weight"], P[f"{n}.norm2.bias"]
-                blk["fc1"] = lin(f"{n}.mlp.fc1", dim, 4 * dim)
-                blk["fc2"] = lin(f"{n}.mlp.fc2", 4 * dim, dim)
+                blk = block_params(n, dim, 4 * dim, param, lin)
+                blk.update(rate=rates[bi], shift=shift if j % 2 else 0, bias_off=boff,
+                           table=P[f"{n}.attn.relative_position_bias_table"])
                 st["blocks"].append(blk)
                 boff = align(boff + self.heads[i] * ws ** 4, 64)
                 bi += 1
@@ -288,10 +284,7 @@ class SwinTransformer(ArenaModel):
                 pm = max(pm, lib.icamd_patch_merge_ln_bwd_workspace_bytes(B, 2 * res, 2 * res, dim // 2))
             nwin = B * (res // wsz) ** 2
             for blk in st["blocks"]:
-                sw["blocks"].append({"h": act(M, dim), "qkv": act(M, 3 * dim), "ao": act(M, dim), "x1": act(M, dim),
-                                     "h2": act(M, dim), "z": act(M, 4 * dim), "a": act(M, 4 * dim), "x2": act(M, dim),
-                                     "lse": f32(nwin * H * wsz * wsz), "st1": f32(2 * M), "st2": f32(2 * M),
-                                     "keep1": None, "keep2": None})
+                sw["blocks"].append(block_workspace(dev, M, dim, 4 * dim, nwin * H * wsz * wsz))
                 for l in (blk["qkv"], blk["proj"], blk["fc1"], blk["fc2"]):
                     wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(l.desc(M))))
             wa = max(wa, lib.icamd_window_attention_bwd_workspace_bytes(B, res, res, H, wsz))
@@ -302,10 +295,7 @@ class SwinTransformer(ArenaModel):
         ws["normed"] = act(ML, self.last_dim)
         ws["st_f"] = f32(2 * ML)
         ws["pooled"] = act(B, self.last_dim)
-        ws["logits"] = torch.zeros(B, self.ncls_p, dtype=torch.bfloat16, device=dev)
-        ws["dlogits"] = torch.zeros(B, self.ncls_p, dtype=torch.bfloat16, device=dev)
-        ws["loss_rows"] = f32(B)
-        ws["pred"] = torch.empty(B, dtype=torch.int32, device=dev)
+        loss_workspace(ws, B, self.ncls_p, dev)
         wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(self.head.desc(B))))
         ws["wg_ws"] = torch.empty(wg, dtype=torch.uint8, device=dev)
         ws["wg_bytes"] = wg
@@ -326,24 +316,26 @@ class SwinTransformer(ArenaModel):
         return ws
 
     def _scratch(self, ws):
-        """backward scratch, made at the first backward: four [rows][C], one [rows][3C], two [rows][4C] at the largest stage"""
+        """backward scratch, made at the first backward: four [rows][C], one [rows][3C], two [rows][4C] at the largest stage;
+        returns the pointers of the four, of the [rows][3C] and of the first [rows][4C]"""
         if "g" not in ws:
             n = ws["max_mc"]
             e = lambda k: torch.empty(k * n, dtype=torch.bfloat16, device=self.device)
             ws["g"] = [e(1), e(1), e(1), e(1)]
             ws["g3"] = e(3)
             ws["g4"] = [e(4), e(4)]
-        return ws["g"], ws["g3"], ws["g4"]
+        return [g.data_ptr() for g in ws["g"]], ws["g3"].data_ptr(), ws["g4"][0].data_ptr()
 
     def _pe_desc(self, B):
-        key = ("pe", B)
-        d = self._ws.get(key)
-        if d is None:
-            d = hip.conv_desc(B, self.img_size, self.img_size, 8, self.embed, PATCH, PATCH, PATCH, 0)
-            self._ws[key] = d
-        return d
+        return patch_embed_desc(self, B, self.embed, PATCH)
 
-    # ------------------------------------------------------------------ helpers
+    def _branch_tmp(self, ws):
+        """forward scratch of a dropped fc2 branch, made at the first step that drops one"""
+        t = ws.get("branch_tmp")
+        if t is None:
+            t = ws["branch_tmp"] = torch.empty(ws["max_mc"], dtype=torch.bfloat16, device=self.device)
+        return t
+
     def _bias(self, blk):
         return self.bias_arena.data_ptr() + 4 * blk["bias_off"]
 
@@ -353,26 +345,16 @@ class SwinTransformer(ArenaModel):
             raise ValueError(f"this model's window plan is built for {self.img_size}x{self.img_size} inputs, not {H}x{W}")
         return self._pack_input(self._workspace(B), x_nchw, mix)
 
-    def _linear(self, l, x_ptr, y_ptr, rows, addend_ptr, s):
-        hip.check(self.lib.icamd_conv2d_fwd(ctypes.byref(l.desc(rows)), x_ptr, self._w(l), y_ptr,
-                                            None if l.b is None else self._pf(l.b), addend_ptr, None, s), l.name)
-
-    def _ln(self, x_ptr, wp, bp, y_ptr, st, rows, C, s):
-        hip.check(self.lib.icamd_layernorm_fwd(x_ptr, self._pf(wp), self._pf(bp), y_ptr, st.data_ptr(), st.data_ptr() + 4 * rows,
-                                               rows, C, LN_EPS, s), wp.name)
-
     # ------------------------------------------------------------------ forward
     def forward_packed(self, ws, logits_only=False):
         """logits_only: a forward whose activations no backward will read (the reference's second, accuracy-only forward under
         mixup): the pre-GELU Mlp activations are not written."""
-        lib, s = self.lib, hip.stream_ptr()
+        f = Forward(self, ws, LN_EPS, logits_only)
+        lib, s = self.lib, f.s
         B = ws["B"]
-        scale = HEAD_DIM ** -0.5
-        hip.check(lib.icamd_conv2d_fwd(ctypes.byref(self._pe_desc(B)), ws["x8"].data_ptr(),
-                                       self.shadow.data_ptr() + 2 * self.pe_w.offset, ws["s"].data_ptr(), self._pf(self.pe_b),
-                                       None, None, s), "patch_embed")
+        f.linear(self.pe, self._pe_desc(B), ws["x8"].data_ptr(), ws["s"].data_ptr())
         M0 = ws["stages"][0]["M"]
-        self._ln(ws["s"].data_ptr(), self.pe_nw, self.pe_nb, ws["x0"].data_ptr(), ws["st_stem"], M0, self.embed, s)
+        f.layernorm(ws["s"].data_ptr(), self.pe_nw, self.pe_nb, ws["x0"].data_ptr(), ws["st_stem"].data_ptr(), M0, self.embed)
         x = ws["x0"]
         drop_rows = None
         if self.training and self.injected_keep is None:
@@ -386,9 +368,14 @@ class SwinTransformer(ArenaModel):
                 hip.check(lib.icamd_patch_merge_ln_fwd(x.data_ptr(), self._pf(st["ds_nw"]), self._pf(st["ds_nb"]),
                                                        sw["ln"].data_ptr(), sw["st"].data_ptr(), sw["st"].data_ptr() + 4 * M, B,
                                                        2 * res, 2 * res, dim // 2, LN_EPS, s), "patch merging")
-                self._linear(st["ds"], sw["ln"].data_ptr(), sw["x"].data_ptr(), M, None, s)
+                f.linear(st["ds"], st["ds"].desc(M), sw["ln"].data_ptr(), sw["x"].data_ptr())
                 x = sw["x"]
-            tok = res * res
+
+            def attn_fwd(blk, b):
+                hip.check(lib.icamd_window_attention_fwd(b["qkv"].data_ptr(), self._bias(blk), b["ao"].data_ptr(),
+                                                         b["lse"].data_ptr(), B, res, res, H, HEAD_DIM, wsz, blk["shift"], SCALE,
+                                                         s), blk["name"] + " window attention")
+
             for blk, b in zip(st["blocks"], sw["blocks"]):
                 keep1 = keep2 = None
                 if self.training and blk["rate"] > 0.0:
@@ -397,127 +384,53 @@ class SwinTransformer(ArenaModel):
                         keep2 = self.injected_keep[2 * bi + 1].to(self.device, dtype=torch.float32)
                     else:
                         keep1, keep2 = drop_rows[2 * bi], drop_rows[2 * bi + 1]
-                b["keep1"], b["keep2"], b["x"] = keep1, keep2, x
-                self._ln(x.data_ptr(), blk["n1w"], blk["n1b"], b["h"].data_ptr(), b["st1"], M, dim, s)
-                self._linear(blk["qkv"], b["h"].data_ptr(), b["qkv"].data_ptr(), M, None, s)
-                hip.check(lib.icamd_window_attention_fwd(b["qkv"].data_ptr(), self._bias(blk), b["ao"].data_ptr(),
-                                                         b["lse"].data_ptr(), B, res, res, H, HEAD_DIM, wsz, blk["shift"], scale,
-                                                         s), blk["name"] + " window attention")
-                if keep1 is None:
-                    self._linear(blk["proj"], b["ao"].data_ptr(), b["x1"].data_ptr(), M, x.data_ptr(), s)   # x1 = x + proj(attn)
-                else:     # x1 = x + keep * proj(attn); the branch passes through h2's buffer (LayerNorm 2 overwrites it next)
-                    self._linear(blk["proj"], b["ao"].data_ptr(), b["h2"].data_ptr(), M, None, s)
-                    hip.check(lib.icamd_layerscale_fwd(b["h2"].data_ptr(), x.data_ptr(), self.ones.data_ptr(), keep1.data_ptr(),
-                                                       b["x1"].data_ptr(), M, dim, tok, s), "drop path")
-                self._ln(b["x1"].data_ptr(), blk["n2w"], blk["n2b"], b["h2"].data_ptr(), b["st2"], M, dim, s)
-                l1 = blk["fc1"]                                                   # z = fc1(h2), a = gelu(z): one kernel
-                hip.check(lib.icamd_conv2d_fwd_gelu(ctypes.byref(l1.desc(M)), b["h2"].data_ptr(), self._w(l1),
-                                                    None if logits_only else b["z"].data_ptr(), b["a"].data_ptr(), self._pf(l1.b),
-                                                    s), l1.name + " + gelu")
-                if keep2 is None:
-                    self._linear(blk["fc2"], b["a"].data_ptr(), b["x2"].data_ptr(), M, b["x1"].data_ptr(), s)   # x2 = x1 + mlp
-                else:     # x2 = x1 + keep * mlp; every buffer of the block is still needed by the backward: a scratch of its own
-                    t = self._branch_tmp(ws)
-                    self._linear(blk["fc2"], b["a"].data_ptr(), t.data_ptr(), M, None, s)
-                    hip.check(lib.icamd_layerscale_fwd(t.data_ptr(), b["x1"].data_ptr(), self.ones.data_ptr(), keep2.data_ptr(),
-                                                       b["x2"].data_ptr(), M, dim, tok, s), "drop path")
-                x = b["x2"]
+                x = f.block(blk, b, x, M, dim, attn_fwd, keep1, keep2, res * res)
                 bi += 1
         ws["x_last"] = x
         sl = ws["stages"][-1]
         ML, DL = sl["M"], self.last_dim
-        self._ln(x.data_ptr(), self.p_nw, self.p_nb, ws["normed"].data_ptr(), ws["st_f"], ML, DL, s)
+        f.layernorm(x.data_ptr(), self.p_nw, self.p_nb, ws["normed"].data_ptr(), ws["st_f"].data_ptr(), ML, DL)
         hip.check(lib.icamd_avgpool_fwd(ws["normed"].data_ptr(), ws["pooled"].data_ptr(), B, ML // B, DL, s), "avgpool")
-        self._linear(self.head, ws["pooled"].data_ptr(), ws["logits"].data_ptr(), B, None, s)
+        f.linear(self.head, self.head.desc(B), ws["pooled"].data_ptr(), ws["logits"].data_ptr())
         return ws["logits"]
-
-    def _branch_tmp(self, ws):
-        t = ws.get("branch_tmp")
-        if t is None:
-            t = ws["branch_tmp"] = torch.empty(ws["max_mc"], dtype=torch.bfloat16, device=self.device)
-        return t
 
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False):
-        lib, s = self.lib, hip.stream_ptr()
+        (g0, g1, g2, g3), gq, gz = self._scratch(ws)
+        # Swin has no second stream: its lane is never enabled, so every weight gradient stays on the main stream
+        bw = Backward(self, ws, streams.SideLane(self.device, enabled=False), accumulate)
+        lib, s, acc = self.lib, bw.s, bw.acc
         B = ws["B"]
-        acc = int(bool(accumulate))
         hook = self.grad_ready_hook
-        wsp, wsb = ws["wg_ws"].data_ptr(), ws["wg_bytes"]
-        lnp, lnb = ws["ln_ws"].data_ptr(), ws["ln_bytes"]
-        scale = HEAD_DIM ** -0.5
-        (g0, g1, g2, g3), gq, (gz, _) = self._scratch(ws)
-
-        def lin_bwd(l, x_ptr, dy_ptr, rows, dx_ptr, gelu_z=None):
-            """weight, bias gradients (+ data gradient into dx when given) of y = x W^T + b"""
-            d = l.desc(rows)
-            if l.b is None:
-                hip.check(lib.icamd_conv2d_wgrad(ctypes.byref(d), x_ptr, dy_ptr, self._gf(l.w), acc, wsp, wsb, s), l.name + " wgrad")
-            else:
-                hip.check(lib.icamd_conv2d_wgrad_bias(ctypes.byref(d), x_ptr, dy_ptr, self._gf(l.w), self._gf(l.b), acc, wsp, wsb,
-                                                      s), l.name + " wgrad+bias")
-            if dx_ptr is None:
-                return
-            if gelu_z is None:
-                hip.check(lib.icamd_conv2d_dgrad(ctypes.byref(d), dy_ptr, self._wt(l), dx_ptr, None, None, s), l.name + " dgrad")
-            else:   # dx = (dy W) * gelu'(z): the GELU backward rides in the data-gradient kernel's store pass
-                hip.check(lib.icamd_conv2d_dgrad_gelu(ctypes.byref(d), dy_ptr, self._wt(l), gelu_z, dx_ptr, s),
-                          l.name + " dgrad + gelu bwd")
-
-        def ln_bwd(dy_ptr, x_ptr, st, wp, bp, addend_ptr, dx_ptr, rows, C):
-            hip.check(lib.icamd_layernorm_bwd(dy_ptr, x_ptr, st.data_ptr(), st.data_ptr() + 4 * rows, self._pf(wp), addend_ptr,
-                                              dx_ptr, self._gf(wp), self._gf(bp), rows, C, acc, lnp, lnb, s), wp.name + " bwd")
-
-        def drop_bwd(dout_ptr, keep, dz_ptr, rows, C, tok):
-            """gradient of the dropped branch: dz = dout * keep (the entry's dgamma goes to a scratch vector)"""
-            hip.check(lib.icamd_layerscale_bwd(dout_ptr, dout_ptr, self.ones.data_ptr(), keep.data_ptr(), dz_ptr,
-                                               ws["ls_dg"].data_ptr(), rows, C, tok, 0, ws["ls_ws"].data_ptr(), ws["ls_bytes"], s),
-                      "drop path bwd")
-
         sl = ws["stages"][-1]
         ML, DL = sl["M"], self.last_dim
-        dpooled = g1.data_ptr()
-        lin_bwd(self.head, ws["pooled"].data_ptr(), ws["dlogits"].data_ptr(), B, dpooled)
-        hip.check(lib.icamd_avgpool_bwd(dpooled, g2.data_ptr(), B, ML // B, DL, s), "avgpool bwd")
-        ln_bwd(g2.data_ptr(), ws["x_last"].data_ptr(), ws["st_f"], self.p_nw, self.p_nb, None, g0.data_ptr(), ML, DL)
+        bw.gemm(self.head, self.head.desc(B), ws["pooled"].data_ptr(), ws["dlogits"].data_ptr(), g1)       # d pooled
+        hip.check(lib.icamd_avgpool_bwd(g1, g2, B, ML // B, DL, s), "avgpool bwd")
+        bw.layernorm(g2, ws["x_last"].data_ptr(), ws["st_f"].data_ptr(), self.p_nw, self.p_nb, None, g0, ML, DL)
         if hook:
             hook(self.p_nw.offset, self.n_params, ())
         dx, free = g0, [g1, g2, g3]
         for i in range(len(self.stages) - 1, -1, -1):
             st, sw = self.stages[i], ws["stages"][i]
             dim, res, wsz, H, M = st["dim"], st["res"], st["ws"], st["heads"], sw["M"]
-            tok = res * res
-            for blk, b in zip(reversed(st["blocks"]), reversed(sw["blocks"])):
-                t0, t1, t2 = free
-                # dx = gradient of x2 = x1 + keep2 * fc2(a)
-                d2 = dx.data_ptr()
-                if b["keep2"] is not None:
-                    drop_bwd(dx.data_ptr(), b["keep2"], t2.data_ptr(), M, dim, tok)
-                    d2 = t2.data_ptr()
-                lin_bwd(blk["fc2"], b["a"].data_ptr(), d2, M, gz.data_ptr(), gelu_z=b["z"].data_ptr())        # d z
-                lin_bwd(blk["fc1"], b["h2"].data_ptr(), gz.data_ptr(), M, t0.data_ptr())                       # d h2
-                ln_bwd(t0.data_ptr(), b["x1"].data_ptr(), b["st2"], blk["n2w"], blk["n2b"], dx.data_ptr(), t1.data_ptr(), M, dim)
-                dx1 = t1                                                                                       # = LN2'(dh2) + dx
-                d1 = dx1.data_ptr()
-                if b["keep1"] is not None:
-                    drop_bwd(dx1.data_ptr(), b["keep1"], t2.data_ptr(), M, dim, tok)
-                    d1 = t2.data_ptr()
-                lin_bwd(blk["proj"], b["ao"].data_ptr(), d1, M, t0.data_ptr())                                 # d attention out
-                hip.check(lib.icamd_window_attention_bwd(b["qkv"].data_ptr(), self._bias(blk), b["ao"].data_ptr(), t0.data_ptr(),
-                                                         b["lse"].data_ptr(), gq.data_ptr(), ws["dbias"].data_ptr(), 0,
+
+            def attn_bwd(blk, b, dao, dqkv):
+                hip.check(lib.icamd_window_attention_bwd(b["qkv"].data_ptr(), self._bias(blk), b["ao"].data_ptr(), dao,
+                                                         b["lse"].data_ptr(), dqkv, ws["dbias"].data_ptr(), 0,
                                                          ws["wa_ws"].data_ptr(), ws["wa_bytes"], B, res, res, H, HEAD_DIM, wsz,
-                                                         blk["shift"], scale, s), blk["name"] + " window attention bwd")
+                                                         blk["shift"], SCALE, s), blk["name"] + " window attention bwd")
                 hip.check(lib.icamd_relpos_bias_scatter(ws["dbias"].data_ptr(), self._gf(blk["table"]), H, wsz, acc, s),
                           blk["name"] + " bias table grad")
-                lin_bwd(blk["qkv"], b["h"].data_ptr(), gq.data_ptr(), M, t0.data_ptr())                        # d h
-                ln_bwd(t0.data_ptr(), b["x"].data_ptr(), b["st1"], blk["n1w"], blk["n1b"], dx1.data_ptr(), dx.data_ptr(), M, dim)
+
+            for blk, b in zip(reversed(st["blocks"]), reversed(sw["blocks"])):
+                bw.block(blk, b, M, dim, dx, (*free, gz, gq), attn_bwd, res * res)
                 if hook:
                     hook(blk["n1w"].offset, None, ())
             if i > 0:
                 t0, t1, t2 = free
-                lin_bwd(st["ds"], sw["ln"].data_ptr(), dx.data_ptr(), M, gq.data_ptr())                        # d LayerNorm(4 C_prev)
-                hip.check(lib.icamd_patch_merge_ln_bwd(gq.data_ptr(), sw["in"].data_ptr(), sw["st"].data_ptr(),
-                                                       sw["st"].data_ptr() + 4 * M, self._pf(st["ds_nw"]), t0.data_ptr(),
+                bw.gemm(st["ds"], st["ds"].desc(M), sw["ln"].data_ptr(), dx, gq)                            # d LayerNorm(4 C_prev)
+                hip.check(lib.icamd_patch_merge_ln_bwd(gq, sw["in"].data_ptr(), sw["st"].data_ptr(),
+                                                       sw["st"].data_ptr() + 4 * M, self._pf(st["ds_nw"]), t0,
                                                        self._gf(st["ds_nw"]), self._gf(st["ds_nb"]), B, 2 * res, 2 * res, dim // 2,
                                                        acc, ws["pm_ws"].data_ptr(), ws["pm_bytes"], s), "patch merging bwd")
                 dx, free = t0, [dx, t1, t2]
@@ -525,9 +438,7 @@ class SwinTransformer(ArenaModel):
                     hook(st["ds_nw"].offset, None, ())
         M0 = ws["stages"][0]["M"]
         t0 = free[0]
-        ln_bwd(dx.data_ptr(), ws["s"].data_ptr(), ws["st_stem"], self.pe_nw, self.pe_nb, None, t0.data_ptr(), M0, self.embed)
-        dpe = self._pe_desc(B)
-        hip.check(lib.icamd_conv2d_wgrad_bias(ctypes.byref(dpe), ws["x8"].data_ptr(), t0.data_ptr(), self._gf(self.pe_w),
-                                              self._gf(self.pe_b), acc, wsp, wsb, s), "patch_embed wgrad+bias")
+        bw.layernorm(dx, ws["s"].data_ptr(), ws["st_stem"].data_ptr(), self.pe_nw, self.pe_nb, None, t0, M0, self.embed)
+        bw.gemm(self.pe, self._pe_desc(B), ws["x8"].data_ptr(), t0, None)
         if hook:
             hook(0, None)

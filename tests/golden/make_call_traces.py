@@ -1,0 +1,306 @@
+"""Generates tests/golden/call_traces.json: one SHA-256 per case over every library call a ViT, Swin or ConvNeXt step makes.
+
+Run at the commit whose launches are to be pinned (no GPU needed):
+    python tests/golden/make_call_traces.py
+To see what moved when the test fails, write the records themselves at both commits and compare them (the fixture is untouched):
+    python tests/golden/make_call_traces.py --dump DIR
+
+The models run on the CPU under make_arena_layouts.install_stubs plus three more replacements (`install_recorders`): the library
+records (entry, arguments) and returns 0, torch.cuda.current_stream is a stand-in whose stream is 0, and streams.SideLane is a
+lane of the same interface that runs a launch with stream 1 when it is enabled (0 otherwise) and leaves a record for every
+before_write that meets a pending read and for every join.  grad_ready_hook records (lo, hi, events).  A case is: construct at
+seed 0, train(), pack, forward_packed, backward_packed, backward_packed(accumulate=True), eval(), forward_packed(logits_only=True),
+load_state_dict(state_dict()).
+
+Arguments are written by their type in hip._SIGNATURES: a descriptor as its key(), a float as its repr, the last pointer as the
+stream id, any other pointer as [number of its buffer in order of first use, byte offset, bytes of the buffer] -- looked up
+among all tensors reachable from the model (collected after every phase and kept alive, so that an address is never used twice),
+"input" for the image batch, None for NULL.  No attribute or dictionary name enters the record; a pointer into no buffer is an
+error.  Besides the trace the file keeps, per case, the number of stream queries (hip.stream_ptr, torch.cuda.current_stream) and,
+per model, what state_dict() holds at seed 0 (`state_record`).  tests/test_call_trace_cpu.py reruns every case and compares.
+"""
+import bisect
+import ctypes
+import hashlib
+import importlib
+import importlib.util
+import json
+import os
+import sys
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+_spec = importlib.util.spec_from_file_location("make_arena_layouts", os.path.join(HERE, "make_arena_layouts.py"))
+L = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(L)
+
+BATCH = 2
+DROP_PATH = 0.2
+VIT_ENV, CNX_ENV = "ICAMD_WGRAD_STREAM_VIT", "ICAMD_WGRAD_STREAM"
+# model id -> (module, class, constructor arguments, input size)
+MODELS = {
+    "vit_tiny_test": ("vit", "VisionTransformer", {"arch": "vit_tiny_test"}, 224),
+    "swin_test": ("swin", "SwinTransformer", {"arch": "swin_test", "img_size": 56}, 56),
+    "swin_test_w12": ("swin", "SwinTransformer", {"arch": "swin_test_w12", "img_size": 96}, 96),
+    "convnext_test": ("convnext", "ConvNeXt", {"arch": "convnext_test"}, 64),
+}
+# case id -> (model id, further constructor arguments, masks per block (None: none injected), environment (None: unset))
+CASES = {
+    "vit_tiny_test/lane_off": ("vit_tiny_test", {}, None, {VIT_ENV: None}),
+    "vit_tiny_test/lane_on": ("vit_tiny_test", {}, None, {VIT_ENV: "1"}),
+    "swin_test/no_drop": ("swin_test", {"drop_path_rate": 0.0}, None, {}),
+    "swin_test/drop": ("swin_test", {"drop_path_rate": DROP_PATH}, 2, {}),
+    "swin_test_w12/no_drop": ("swin_test_w12", {"drop_path_rate": 0.0}, None, {}),
+    "swin_test_w12/drop": ("swin_test_w12", {"drop_path_rate": DROP_PATH}, 2, {}),
+    "convnext_test/lane_on": ("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: None}),
+    "convnext_test/lane_off": ("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: "0"}),
+}
+
+TRACE = []          # the records of the case that is running
+QUERIES = [0]       # its stream queries
+
+
+class RecordingLib:
+    """Stands in for libicamd.so: every entry of hip._SIGNATURES records its call and returns 0; any other name is an error."""
+
+    def __getattr__(self, name):
+        from imageclassification_amd import hip
+        argtypes = hip._SIGNATURES[name][1]
+
+        def desc_key(a):      # byref(ConvDesc) -> the descriptor's fields, taken now
+            d = getattr(a, "_obj", None)
+            return d.key() if isinstance(d, hip.ConvDesc) else a
+
+        def entry(*args):
+            assert len(args) == len(argtypes), (name, len(args), len(argtypes))
+            TRACE.append((name, argtypes, tuple(desc_key(a) for a in args)))
+            return 0
+        return entry
+
+
+class _Stream:
+    cuda_stream = 0
+
+
+class RecordingLane:
+    """streams.SideLane without streams or events: same interface, same bookkeeping, and a record of every wait it would make."""
+
+    def __init__(self, device, enabled=True):
+        self.enabled = bool(enabled)
+        self.side = 1 if self.enabled else None
+        self._pending = set()
+        self._launched = self._joined = 0
+
+    def begin(self, enabled=True):
+        self.enabled = self.side is not None and bool(enabled)
+        self._pending.clear()
+        self._launched = 0
+        self._joined = 0
+
+    @property
+    def stream_ptr(self):
+        return 1 if self.enabled else 0
+
+    def launch(self, fn, reads=()):
+        fn(self.stream_ptr)
+        if self.enabled:
+            self._launched += 1
+            self._pending.update(reads)
+
+    def before_write(self, *ptrs):
+        for p in ptrs:
+            if p in self._pending:
+                self._pending.discard(p)
+                TRACE.append(("lane.before_write", (ctypes.c_void_p, None), (p, None)))
+
+    def events(self):
+        return (self._launched,) if self._launched > self._joined else ()
+
+    def join(self):
+        TRACE.append(("lane.join", (ctypes.c_int,), (self._launched - self._joined,)))
+        self._joined = self._launched
+        self._pending.clear()
+
+
+def _query(value):
+    def f(*a, **k):
+        QUERIES[0] += 1
+        return value
+    return f
+
+
+def install_recorders(setattr_fn=setattr):
+    """install_stubs plus the recording library, stream stand-in and lane; a test passes monkeypatch.setattr."""
+    from imageclassification_amd import hip, streams
+    L.install_stubs(setattr_fn)
+    lib = RecordingLib()
+    setattr_fn(hip, "load", lambda: lib)
+    setattr_fn(hip, "stream_ptr", _query(0))
+    setattr_fn(torch.cuda, "current_stream", _query(_Stream()))
+    setattr_fn(streams, "SideLane", RecordingLane)
+
+
+def build_model(model_id, **more):
+    module, cls, kwargs, _ = MODELS[model_id]
+    mod = importlib.import_module("imageclassification_amd." + module)
+    return getattr(mod, cls)(num_classes=L.NUM_CLASSES, device="cpu", seed=0, **kwargs, **more)
+
+
+def state_record(model):
+    """What pins the weights a seed gives: a SHA-256 over the names and shapes of state_dict(), and per parameter its sum (in
+    float64) and its first, middle and last element.  The values themselves are not hashed: the draws are the generator's, the same
+    everywhere, but trunc_normal_ evaluates erfinv, which differs in the last bits from one CPU to another; a draw that moved changes
+    every figure here by far more (STATE_TOL)."""
+    sd = model.state_dict()
+    h = hashlib.sha256(json.dumps([[n, list(t.shape)] for n, t in sd.items()]).encode()).hexdigest()
+    flat = [t.double().flatten() for t in sd.values()]
+    return {"names_and_shapes_sha256": h,
+            "values": [[float(f.sum()), float(f[0]), float(f[f.numel() // 2]), float(f[-1])] for f in flat]}
+
+
+def state_tol(numel):
+    """(tolerance of a parameter's sum, of one element): the weights are below 0.25 in magnitude except the LayerNorm ones, which are
+    exact, so one float32 ulp is at most 1.5e-8 and a few ulps of evaluation difference stay below 1e-7 per element -- summed over
+    the parameter in the worst case.  A parameter drawn from other random numbers moves its sum by about 0.02 * sqrt(numel)."""
+    return 1e-7 * numel, 1e-7
+
+
+def _masks(model, per_block):
+    """Per residual branch one [BATCH] mask of {0, 1 / keep_prob}, the zero alternating between the two samples; ones for a
+    block whose rate is 0 (never read)."""
+    out = []
+    for st in model.stages:
+        for blk in st["blocks"]:
+            for _ in range(per_block):
+                c = 1.0 / (1.0 - blk["rate"])
+                m = [c, 0.0] if len(out) % 2 else [0.0, c]
+                out.append(torch.tensor(m if blk["rate"] > 0.0 else [1.0, 1.0], dtype=torch.float32))
+    return out
+
+
+def _collect(obj, held, seen):
+    """Every tensor reachable from `obj` through dicts, sequences and attributes: storage address -> (bytes, the tensor)."""
+    if id(obj) in seen or obj is None or isinstance(obj, (int, float, str, bytes, bool, type)):
+        return
+    seen.add(id(obj))
+    if isinstance(obj, torch.Tensor):
+        st = obj.untyped_storage()
+        if st.nbytes():
+            held.setdefault(st.data_ptr(), (st.nbytes(), obj))
+    elif isinstance(obj, dict):
+        for v in obj.values():
+            _collect(v, held, seen)
+    elif isinstance(obj, (list, tuple, set)):
+        for v in obj:
+            _collect(v, held, seen)
+    elif hasattr(obj, "__dict__") and not callable(obj):
+        _collect(vars(obj), held, seen)
+
+
+def canonical(trace, held, x):
+    """The trace with every argument in its canonical form (module docstring); LookupError for a pointer into no buffer."""
+    bases = sorted(held)
+    order = {}
+
+    def pointer(p, where):
+        if not p:
+            return None
+        i = bisect.bisect_right(bases, p) - 1
+        if i < 0 or p >= bases[i] + held[bases[i]][0]:
+            raise LookupError(f"{where}: pointer {p:#x} is in no tensor of the model")
+        base = bases[i]
+        if base == x.untyped_storage().data_ptr():
+            return "input" if p == base else ["input", p - base]
+        return [order.setdefault(base, len(order)), p - base, held[base][0]]
+
+    out = []
+    for name, argtypes, args in trace:
+        row = [name]
+        for k, (t, a) in enumerate(zip(argtypes, args)):
+            if isinstance(a, tuple):
+                row.append(list(a))
+            elif t is ctypes.c_void_p:
+                row.append(f"stream {a}" if k == len(args) - 1 else pointer(a, f"{name} argument {k}"))
+            elif t is ctypes.c_float or isinstance(a, float):
+                row.append(repr(float(a)))
+            else:
+                row.append(None if a is None else int(a))
+        out.append(row)
+    return out
+
+
+def run_case(case_id, setenv=None, dump=None):
+    """-> {"sha256", "calls", "stream_queries"} of one case, under install_recorders; dump: a file for the records, one per line.  setenv(name, value or None) changes the
+    environment (a test passes a function that undoes itself); by default os.environ, restored at the end."""
+    model_id, more, per_block, env = CASES[case_id]
+    saved = {k: os.environ.get(k) for k in env}
+
+    def default_setenv(k, v):
+        os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+
+    for k, v in env.items():
+        (setenv or default_setenv)(k, v)
+    try:
+        del TRACE[:]
+        QUERIES[0] = 0
+        held = {}
+        model = build_model(model_id, **more)
+
+        def phase(result=None):
+            _collect(vars(model), held, set())
+            return result
+
+        model.grad_ready_hook = lambda lo, hi, events=(): TRACE.append(
+            ("hook", (ctypes.c_int, ctypes.c_int, None), (lo, hi, tuple(events))))
+        if per_block:
+            model.injected_keep = _masks(model, per_block)
+        size = MODELS[model_id][3]
+        x = torch.randn(BATCH, 3, size, size, generator=torch.Generator().manual_seed(1))
+        held[x.untyped_storage().data_ptr()] = (x.untyped_storage().nbytes(), x)
+        phase(model.train())
+        ws = phase(model.pack(x))
+        phase(model.forward_packed(ws))
+        phase(model.backward_packed(ws))
+        phase(model.backward_packed(ws, accumulate=True))
+        phase(model.eval())
+        phase(model.forward_packed(ws, logits_only=True))
+        phase(model.load_state_dict(model.state_dict()))
+        rows = canonical(TRACE, held, x)
+    finally:
+        if setenv is None:
+            for k, v in saved.items():
+                default_setenv(k, v)
+    blob = json.dumps(rows, separators=(",", ":"))
+    if dump:
+        with open(dump, "w") as f:
+            f.writelines(json.dumps(r) + "\n" for r in rows)
+    return {"sha256": hashlib.sha256(blob.encode()).hexdigest(), "calls": len(rows), "stream_queries": QUERIES[0]}
+
+
+def main():
+    install_recorders()
+    if sys.argv[1:2] == ["--dump"]:
+        os.makedirs(sys.argv[2], exist_ok=True)
+        for case_id in CASES:
+            print(case_id, run_case(case_id, dump=os.path.join(sys.argv[2], case_id.replace("/", "__") + ".jsonl")))
+        return
+    out = {"generator": "tests/golden/make_call_traces.py", "num_classes": L.NUM_CLASSES, "batch": BATCH, "cases": {},
+           "state_dict_seed0": {}}
+    for case_id in CASES:
+        out["cases"][case_id] = run_case(case_id)
+        print(case_id, out["cases"][case_id])
+    for model_id in MODELS:
+        out["state_dict_seed0"][model_id] = state_record(build_model(model_id))
+        print(model_id, out["state_dict_seed0"][model_id]["names_and_shapes_sha256"])
+    with open(os.path.join(HERE, "call_traces.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
