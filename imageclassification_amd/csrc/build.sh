@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -I../../include"
-UNITS="conv_igemm conv3x3_halo conv_grouped conv1x1_resident conv_fused_bwd conv_fused_fwd conv_stem conv_stem_deep conv_wgrad norm_pool se_ops loss_optim token_ops attention attention_long window_attention window_attention_w12 dwconv gemm_nt image_ops collective capi"
+UNITS="conv_igemm conv3x3_halo conv_grouped conv1x1_resident conv_fused_bwd conv_fused_fwd conv_stem conv_stem_deep conv_wgrad norm_pool se_ops loss_optim token_ops attention attention_long window_attention window_attention_w12 dwconv gemm_nt image_ops collective capi capi_conv_special capi_norm capi_tokens capi_step"
 asm_of() { echo "build/$1-hip-amdgcn-amd-amdhsa-gfx950.s"; }
 OBJS=""
 ASMS=""
@@ -14,7 +14,7 @@ REUSED=""
 for f in $UNITS; do
   # An object is reused only together with the device assembly it was built with: the ISA lint below reads that file, and an
   # object whose .s is missing (a build directory of an older tree, a deleted file) would otherwise be linked unlinted.
-  if [ ! -f build/$f.o ] || [ ! -f "$(asm_of $f)" ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ icamd_internal.h -nt build/$f.o ] || [ attention_common.h -nt build/$f.o ] || [ ../../include/icamd.h -nt build/$f.o ]; then
+  if [ ! -f build/$f.o ] || [ ! -f "$(asm_of $f)" ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ icamd_internal.h -nt build/$f.o ] || [ capi_common.h -nt build/$f.o ] || [ attention_common.h -nt build/$f.o ] || [ ../../include/icamd.h -nt build/$f.o ]; then
     mkdir -p build
     rm -f build/$f.o "$(asm_of $f)"   # a failed compile must not leave a stale object (or its assembly) for the link step
     # -save-temps=obj leaves build/$f-hip-amdgcn-amd-amdhsa-gfx950.s next to the object: the device assembly tools/isa_lint.py reads
@@ -50,6 +50,7 @@ if ! python3 ../../tools/isa_lint.py $ASMS > build/isa_lint.log; then
   exit 1
 fi
 cat build/isa_lint.log
-$HIPCC --offload-arch=gfx950 -shared -fPIC $OBJS -ldl -o libicamd.so
+# -z defs: a launcher prototype of icamd_internal.h that no unit defines as declared fails here, not when the library is loaded
+$HIPCC --offload-arch=gfx950 -shared -fPIC -Wl,-z,defs $OBJS -ldl -o libicamd.so
 echo "compiled for gfx950:${COMPILED:- (none)}; reused up-to-date objects:${REUSED:- (none)}"
 echo "built $(pwd)/libicamd.so"

@@ -1,0 +1,289 @@
+// C-ABI entry points of BatchNorm (finalize / apply / backward), the squeeze-and-excitation tail and max / average pooling.
+#include "capi_common.h"
+
+extern "C" {
+
+size_t icamd_bn_workspace_bytes(int C) { return C > 0 ? bn_chunk_bytes(C) : 0; }
+
+int icamd_bn_train_finalize(const float* partials, int nrows, int C, double count, const float* gamma,
+                            const float* beta, float* running_mean, float* running_var, float momentum, float eps,
+                            float* mean, float* invstd, float* scale, float* shift, void* workspace, void* stream) {
+  ProfScope _prof(PC_BN_FINALIZE, stream);
+  _prof.work(8.0 * nrows * C);
+  if (partials == nullptr || nrows <= 0 || C <= 0 || count <= 0 || gamma == nullptr || beta == nullptr ||
+      mean == nullptr || invstd == nullptr || scale == nullptr || shift == nullptr || workspace == nullptr || C > 4096)
+    return ICAMD_ERR_BAD_ARG;
+  return icamd_bn_finalize_launch(partials, nrows, C, count, gamma, beta, running_mean, running_var, momentum, eps, mean,
+                                  invstd, scale, shift, (double*)((char*)workspace + 256), (hipStream_t)stream);
+}
+
+int icamd_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
+                         const float* running_var, float eps, float* scale, float* shift, void* stream) {
+  ProfScope _prof(PC_BN_FINALIZE, stream);
+  _prof.work(24.0 * C);
+  if (C <= 0 || gamma == nullptr || beta == nullptr || running_mean == nullptr || running_var == nullptr ||
+      scale == nullptr || shift == nullptr)
+    return ICAMD_ERR_BAD_ARG;
+  return icamd_bn_eval_coeffs_launch(C, gamma, beta, running_mean, running_var, eps, scale, shift, (hipStream_t)stream);
+}
+
+int icamd_bn_apply(const void* y, const float* scale, const float* shift, const void* residual, void* out,
+                   uint8_t* maskbits, long long numel, int C, int relu, void* stream) {
+  ProfScope _prof(PC_BN_APPLY, stream);
+  _prof.work((double)numel * (4 + (residual ? 2 : 0)) + (maskbits ? numel / 8.0 : 0));
+  if (y == nullptr || scale == nullptr || shift == nullptr || out == nullptr || numel <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  return icamd_bn_apply_launch((const bf16_t*)y, scale, shift, (const bf16_t*)residual, (bf16_t*)out, maskbits, numel, C,
+                               relu, (hipStream_t)stream);
+}
+
+int icamd_bn_apply_res_bn(const void* y, const float* scale, const float* shift, const void* res_y, const float* res_scale,
+                          const float* res_shift, void* out, uint8_t* maskbits, long long numel, int C, int relu,
+                          void* stream) {
+  ProfScope _prof(PC_BN_APPLY, stream);
+  _prof.work((double)numel * 6 + (maskbits ? numel / 8.0 : 0));
+  if (y == nullptr || scale == nullptr || shift == nullptr || res_y == nullptr || res_scale == nullptr ||
+      res_shift == nullptr || out == nullptr || numel <= 0 || C <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  return icamd_bn_apply_launch((const bf16_t*)y, scale, shift, (const bf16_t*)res_y, (bf16_t*)out, maskbits, numel, C, relu,
+                               (hipStream_t)stream, res_scale, res_shift);
+}
+
+// ---- squeeze-and-excitation tail (se_ops.hip) ----
+size_t icamd_se_squeeze_workspace_bytes(int N, int HW, int C) {
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return 0;
+  return icamd_se_squeeze_bytes(N, HW, C);
+}
+
+int icamd_se_squeeze(const void* y, float* ysum, int N, int HW, int C, void* workspace, size_t workspace_bytes, void* stream) {
+  if (y == nullptr || ysum == nullptr || workspace == nullptr || N <= 0 || HW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace_bytes < icamd_se_squeeze_bytes(N, HW, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work(2.0 * N * HW * C + 4.0 * N * C);
+  return icamd_se_squeeze_launch((const bf16_t*)y, ysum, N, HW, C, (float*)workspace, (hipStream_t)stream);
+}
+
+int icamd_se_excite_fwd(const float* ysum, const float* scale, const float* shift, float inv_hw, const float* w1, const float* b1,
+                        const float* w2, const float* b2, float* s, float* h, float* e, int N, int C, int rd, void* stream) {
+  if (ysum == nullptr || scale == nullptr || shift == nullptr || w1 == nullptr || b1 == nullptr || w2 == nullptr || b2 == nullptr ||
+      s == nullptr || h == nullptr || e == nullptr || N <= 0 || C <= 0 || rd <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, 1, C, rd)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_MISC, stream);
+  _prof.work(4.0 * N * (3.0 * C + rd) + 4.0 * (2.0 * C * rd + C + rd), 4.0 * N * C * rd);
+  return icamd_se_excite_fwd_launch(ysum, scale, shift, inv_hw, w1, b1, w2, b2, s, h, e, N, C, rd, (hipStream_t)stream);
+}
+
+int icamd_se_bn_apply(const void* y, const float* scale, const float* shift, const float* e, const void* residual,
+                      const float* res_scale, const float* res_shift, void* out, uint8_t* maskbits, int N, int HW, int C, int relu,
+                      void* stream) {
+  if (y == nullptr || scale == nullptr || shift == nullptr || e == nullptr || out == nullptr || N <= 0 || HW <= 0 || C <= 0 ||
+      (res_scale == nullptr) != (res_shift == nullptr) || (res_scale != nullptr && residual == nullptr))
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_BN_APPLY, stream);
+  const double numel = (double)N * HW * C;
+  _prof.work(numel * (4 + (residual ? 2 : 0)) + (maskbits ? numel / 8.0 : 0) + 4.0 * N * C);
+  return icamd_se_bn_apply_launch((const bf16_t*)y, scale, shift, e, (const bf16_t*)residual, res_scale, res_shift, (bf16_t*)out,
+                                  maskbits, N, HW, C, relu, (hipStream_t)stream);
+}
+
+size_t icamd_se_bn_bwd_workspace_bytes(int N, int HW, int C) {
+  if (!icamd_se_shape_ok(N, HW, C, 1)) return 0;
+  return icamd_se_bn_bwd_bytes(N, HW, C);
+}
+
+int icamd_se_bn_bwd(const void* dout, const uint8_t* maskbits, const void* y, const float* mean, const float* invstd,
+                    const float* gamma, const float* beta, const float* ysum, const float* s, const float* h, const float* e,
+                    const float* w1, const float* w2, float* dgamma, float* dbeta, float* dw1, float* db1, float* dw2, float* db2,
+                    void* dy, int N, int HW, int C, int rd, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+  if (dout == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || gamma == nullptr || beta == nullptr ||
+      ysum == nullptr || s == nullptr || h == nullptr || e == nullptr || w1 == nullptr || w2 == nullptr || dgamma == nullptr ||
+      dbeta == nullptr || dw1 == nullptr || db1 == nullptr || dw2 == nullptr || db2 == nullptr || dy == nullptr ||
+      workspace == nullptr || N <= 0 || HW <= 0 || C <= 0 || rd <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_se_shape_ok(N, HW, C, rd)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace_bytes < icamd_se_bn_bwd_bytes(N, HW, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_BN_BWD, stream);
+  const double numel = (double)N * HW * C;
+  _prof.work(numel * (2 * 4 + 2) + (maskbits ? numel / 4.0 : 0) + 4.0 * N * (8.0 * C + 2.0 * rd) + 16.0 * C * rd, 8.0 * N * C * rd);
+  return icamd_se_bn_bwd_launch((const bf16_t*)dout, maskbits, (const bf16_t*)y, mean, invstd, gamma, beta, ysum, s, h, e, w1, w2,
+                                dgamma, dbeta, dw1, db1, dw2, db2, (bf16_t*)dy, N, HW, C, rd, accumulate, workspace,
+                                (hipStream_t)stream);
+}
+
+// bwd workspace: partial rows [nblk][2][C] floats | chunks [64][2][C] doubles | c1,c2 [2][C] floats
+size_t icamd_bn_bwd_workspace_bytes(long long rows, int C) {
+  if (rows <= 0 || C <= 0) return 0;
+  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
+  const long long nblk = (rows + rpb - 1) / rpb;
+  return align_up((size_t)nblk * 2 * C * sizeof(float), 256) + bn_chunk_bytes(C) + align_up((size_t)2 * C * sizeof(float), 256);
+}
+
+int icamd_bn_bwd(const void* dout, const void* act, const void* y, const float* mean, const float* invstd,
+                 const float* scale, const float* shift, float* dgamma, float* dbeta, void* dy, void* gout,
+                 const uint8_t* maskbits, long long rows, int C, int relu, int accumulate, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)rows * C * (2 * (4 + (act ? 2 : 0)) + 2 + (gout ? 2 : 0)) + (maskbits ? rows * C / 4.0 : 0));
+  if (dout == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || scale == nullptr || shift == nullptr ||
+      dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 || C <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  const size_t need = icamd_bn_bwd_workspace_bytes(rows, C);
+  if (workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
+  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
+  const long long nblk = (rows + rpb - 1) / rpb;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  char* ws = (char*)workspace;
+  double* chunks = (double*)(ws + 256);     // arrival counters live in the first 256 B
+  ws += bn_chunk_bytes(C);
+  float* part = (float*)ws;
+  ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
+  float* c1c2 = (float*)ws;
+  return icamd_bn_bwd_launch((const bf16_t*)dout, (const bf16_t*)act, (const bf16_t*)y, mean, invstd, scale, shift, dgamma,
+                             dbeta, (bf16_t*)dy, (bf16_t*)gout, maskbits, rows, C, relu, accumulate, part, chunks, c1c2,
+                             (hipStream_t)stream);
+}
+
+int icamd_bn_bwd_maxpool3x3s2(const void* dout_pooled, const uint8_t* idx, const void* y, const float* mean,
+                              const float* invstd, const float* scale, const float* shift, float* dgamma, float* dbeta,
+                              void* dy, int N, int IH, int IW, int C, int accumulate, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)N * IH * IW * C * (2 * 2 + 2) + 2.0 * N * IH * IW * C / 4 * 3);
+  if (dout_pooled == nullptr || idx == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || scale == nullptr ||
+      shift == nullptr || dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || N <= 0 || IH <= 0 ||
+      IW <= 0 || C <= 0 || C % 8 != 0)
+    return ICAMD_ERR_BAD_ARG;
+  const long long rows = (long long)N * IH * IW;
+  const size_t need = icamd_bn_bwd_workspace_bytes(rows, C);
+  if (workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
+  const long long nblk = (rows + rpb - 1) / rpb;
+  char* ws = (char*)workspace;
+  double* chunks = (double*)(ws + 256);
+  ws += bn_chunk_bytes(C);
+  float* part = (float*)ws;
+  ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
+  float* c1c2 = (float*)ws;
+  return icamd_bn_bwd_launch((const bf16_t*)dout_pooled, nullptr, (const bf16_t*)y, mean, invstd, scale, shift, dgamma, dbeta,
+                             (bf16_t*)dy, nullptr, nullptr, rows, C, /*relu=*/1, accumulate, part, chunks, c1c2,
+                             (hipStream_t)stream, idx, IH, IW);
+}
+
+int icamd_bn_bwd_dual(const void* dout, const uint8_t* maskbits, const void* yA, const float* meanA, const float* invstdA,
+                      const float* scaleA, float* dgammaA, float* dbetaA, void* dyA, const void* yB, const float* meanB,
+                      const float* invstdB, const float* scaleB, float* dgammaB, float* dbetaB, void* dyB, long long rows, int C,
+                      int accumulate, void* workspaceA, void* workspaceB, size_t workspace_bytes, void* stream) {
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)rows * C * (2 * 6 + 4) + rows * C / 4.0);
+  if (dout == nullptr || maskbits == nullptr || yA == nullptr || yB == nullptr || meanA == nullptr || meanB == nullptr ||
+      invstdA == nullptr || invstdB == nullptr || scaleA == nullptr || scaleB == nullptr || dgammaA == nullptr ||
+      dgammaB == nullptr || dbetaA == nullptr || dbetaB == nullptr || dyA == nullptr || dyB == nullptr ||
+      workspaceA == nullptr || workspaceB == nullptr || workspaceA == workspaceB || rows <= 0 || C <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (workspace_bytes < icamd_bn_bwd_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
+  const long long nblk = (rows + rpb - 1) / rpb;
+  float* part[2]; double* chunks[2]; float* cc[2];
+  void* wsv[2] = {workspaceA, workspaceB};
+  for (int i = 0; i < 2; ++i) {
+    char* ws = (char*)wsv[i];
+    chunks[i] = (double*)(ws + 256);
+    ws += bn_chunk_bytes(C);
+    part[i] = (float*)ws;
+    ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
+    cc[i] = (float*)ws;
+  }
+  return icamd_bn_bwd_dual_launch((const bf16_t*)dout, maskbits, (const bf16_t*)yA, meanA, invstdA, scaleA, dgammaA, dbetaA,
+                                  (bf16_t*)dyA, (const bf16_t*)yB, meanB, invstdB, scaleB, dgammaB, dbetaB, (bf16_t*)dyB, rows,
+                                  C, accumulate, part[0], chunks[0], cc[0], part[1], chunks[1], cc[1], (hipStream_t)stream);
+}
+
+// workspace: chunks [64][2][C] doubles | c1,c2 [2][C] floats
+size_t icamd_bn_bwd_apply_workspace_bytes(int C) {
+  return C > 0 ? bn_chunk_bytes(C) + align_up((size_t)2 * C * sizeof(float), 256) : 0;
+}
+
+int icamd_bn_bwd_from_partials(const float* partials, int nrows, const void* g, const void* y, const float* mean,
+                               const float* invstd, const float* scale, float* dgamma, float* dbeta, void* dy,
+                               long long rows, int C, int accumulate, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)rows * C * 6 + 8.0 * nrows * C);
+  if (partials == nullptr || nrows <= 0 || g == nullptr || y == nullptr || mean == nullptr || invstd == nullptr ||
+      scale == nullptr || dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 ||
+      C <= 0 || C % 8 != 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (workspace_bytes < icamd_bn_bwd_apply_workspace_bytes(C)) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  char* ws = (char*)workspace;
+  double* chunks = (double*)(ws + 256);
+  ws += bn_chunk_bytes(C);
+  return icamd_bn_bwd_apply_launch(partials, nrows, (const bf16_t*)g, (const bf16_t*)y, mean, invstd, scale, dgamma, dbeta,
+                                   (bf16_t*)dy, rows, C, accumulate, chunks, (float*)ws, (hipStream_t)stream);
+}
+
+int icamd_bn_bwd_from_gy_partials(const float* partials, int nrows, const void* g, const void* y, const float* mean,
+                                  const float* invstd, const float* scale, float* dgamma, float* dbeta, void* dy,
+                                  long long rows, int C, int accumulate, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)rows * C * 6 + 8.0 * nrows * C);
+  if (partials == nullptr || nrows <= 0 || g == nullptr || y == nullptr || mean == nullptr || invstd == nullptr ||
+      scale == nullptr || dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 ||
+      C <= 0 || C % 8 != 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (workspace_bytes < icamd_bn_bwd_apply_workspace_bytes(C)) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  char* ws = (char*)workspace;
+  double* chunks = (double*)(ws + 256);
+  ws += bn_chunk_bytes(C);
+  return icamd_bn_bwd_apply_launch(partials, nrows, (const bf16_t*)g, (const bf16_t*)y, mean, invstd, scale, dgamma, dbeta,
+                                   (bf16_t*)dy, rows, C, accumulate, chunks, (float*)ws, (hipStream_t)stream, 1);
+}
+
+int icamd_maxpool3x3s2_fwd(const void* x, void* out, uint8_t* argmax, int N, int IH, int IW, int C, void* stream) {
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work((double)N * IH * IW * C * (2 + 0.75));
+  if (x == nullptr || out == nullptr || N <= 0 || IH <= 0 || IW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  const int OH = (IH + 2 - 3) / 2 + 1, OW = (IW + 2 - 3) / 2 + 1;
+  return icamd_maxpool_fwd_launch((const bf16_t*)x, (bf16_t*)out, argmax, N, IH, IW, C, OH, OW, (hipStream_t)stream);
+}
+
+int icamd_bn_relu_maxpool3x3s2_fwd(const void* y, const float* scale, const float* shift, void* out, uint8_t* argmax, int N,
+                                   int IH, int IW, int C, void* stream) {
+  ProfScope _prof(PC_BN_APPLY, stream);
+  _prof.work((double)N * IH * IW * C * (2 + 0.75));
+  if (y == nullptr || scale == nullptr || shift == nullptr || out == nullptr || N <= 0 || IH <= 0 || IW <= 0 || C <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  const int OH = (IH + 2 - 3) / 2 + 1, OW = (IW + 2 - 3) / 2 + 1;
+  return icamd_bn_relu_maxpool_fwd_launch((const bf16_t*)y, scale, shift, (bf16_t*)out, argmax, N, IH, IW, C, OH, OW,
+                                          (hipStream_t)stream);
+}
+
+int icamd_maxpool3x3s2_bwd(const void* dout, const uint8_t* argmax, void* dx, int N, int IH, int IW, int C, void* stream) {
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work((double)N * IH * IW * C * (2 + 0.75));
+  if (dout == nullptr || argmax == nullptr || dx == nullptr || N <= 0 || IH <= 0 || IW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  const int OH = (IH + 2 - 3) / 2 + 1, OW = (IW + 2 - 3) / 2 + 1;
+  return icamd_maxpool_bwd_launch((const bf16_t*)dout, argmax, (bf16_t*)dx, N, IH, IW, C, OH, OW, (hipStream_t)stream);
+}
+
+int icamd_avgpool_fwd(const void* x, void* out, int N, int HW, int C, void* stream) {
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work(2.0 * N * HW * C + 2.0 * N * C);
+  if (x == nullptr || out == nullptr || N <= 0 || HW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  return icamd_avgpool_fwd_launch((const bf16_t*)x, (bf16_t*)out, N, HW, C, (hipStream_t)stream);
+}
+
+int icamd_avgpool_bwd(const void* dout, void* dx, int N, int HW, int C, void* stream) {
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work(2.0 * N * HW * C + 2.0 * N * C);
+  if (dout == nullptr || dx == nullptr || N <= 0 || HW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  return icamd_avgpool_bwd_launch((const bf16_t*)dout, (bf16_t*)dx, N, HW, C, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,4 +1,6 @@
-// Internal launch-parameter blocks shared between the C-ABI layer (capi.hip) and the kernels.
+// Internal launch-parameter blocks and launcher prototypes shared between the C-ABI layer (the capi*.hip units) and the kernels.
+// Every launcher is declared here and nowhere else; the defining unit includes this header, and the library is linked with
+// -z defs, so a declaration that drifts from its definition fails the build.
 #pragma once
 #include "common.h"
 
@@ -260,3 +262,158 @@ int icamd_wgrad_halo_launch(WgradParams& p, hipStream_t stream);   // output-til
 // out[i] = (accumulate ? out[i] : 0) + sum over S slabs of slab[s][i], fixed order; n % 4 == 0
 int icamd_slab_reduce_launch(const float* slab, float* out, long long n, int S, int accumulate, hipStream_t stream,
                              int stem7_mask = 0);
+
+// BatchNorm, pooling, input packing, BatchNorm folding, partial-row sums (norm_pool.hip)
+int icamd_bn_finalize_launch(const float* part, int nrows, int C, double count, const float* gamma, const float* beta,
+                             float* running_mean, float* running_var, float momentum, float eps, float* mean,
+                             float* invstd, float* scale, float* shift, double* chunks, hipStream_t s);
+int icamd_bn_eval_coeffs_launch(int C, const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                                float* scale, float* shift, hipStream_t s);
+int icamd_bn_apply_launch(const bf16_t* y, const float* scale, const float* shift, const bf16_t* residual, bf16_t* out,
+                          unsigned char* maskbits, long long numel, int C, int relu, hipStream_t s,
+                          const float* res_scale = nullptr, const float* res_shift = nullptr);
+int icamd_bn_bwd_rows_per_block(long long rows, int C);
+int icamd_bn_bwd_launch(const bf16_t* dout, const bf16_t* act, const bf16_t* y, const float* mean, const float* invstd,
+                        const float* scale, const float* shift, float* dgamma, float* dbeta, bf16_t* dy, bf16_t* gout,
+                        const unsigned char* maskbits, long long rows, int C, int relu, int accumulate, float* part,
+                        double* chunks, float* c1c2, hipStream_t s, const unsigned char* pool_idx = nullptr,
+                        int pool_ih = 0, int pool_iw = 0);
+int icamd_bn_bwd_dual_launch(const bf16_t* dout, const unsigned char* maskbits, const bf16_t* yA, const float* meanA,
+                             const float* invstdA, const float* scaleA, float* dgammaA, float* dbetaA, bf16_t* dyA,
+                             const bf16_t* yB, const float* meanB, const float* invstdB, const float* scaleB, float* dgammaB,
+                             float* dbetaB, bf16_t* dyB, long long rows, int C, int accumulate, float* partA, double* chunksA,
+                             float* cA, float* partB, double* chunksB, float* cB, hipStream_t s);
+int icamd_bn_bwd_apply_launch(const float* part, int nrows, const bf16_t* g, const bf16_t* y, const float* mean,
+                              const float* invstd, const float* scale, float* dgamma, float* dbeta, bf16_t* dy,
+                              long long rows, int C, int accumulate, double* chunks, float* c1c2, hipStream_t s, int sums_are_gy = 0);
+int icamd_bn_bwd_finalize_launch(const float* part, int nrows, const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                                 long long rows, int C, int accumulate, double* chunks, float* c1c2, hipStream_t s, int sums_are_gy);
+int icamd_bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* mean, const float* invstd, float* part, long long rows,
+                               int C, int* nblk_out, hipStream_t s);
+int icamd_maxpool_fwd_launch(const bf16_t* x, bf16_t* out, unsigned char* idx, int N, int IH, int IW, int C, int OH, int OW,
+                             hipStream_t s);
+int icamd_bn_relu_maxpool_fwd_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out, unsigned char* idx,
+                                     int N, int IH, int IW, int C, int OH, int OW, hipStream_t s);
+int icamd_maxpool_bwd_launch(const bf16_t* dout, const unsigned char* idx, bf16_t* dx, int N, int IH, int IW, int C, int OH,
+                             int OW, hipStream_t s);
+int icamd_avgpool_fwd_launch(const bf16_t* x, bf16_t* out, int N, int HW, int C, hipStream_t s);
+int icamd_avgpool_bwd_launch(const bf16_t* dout, bf16_t* dx, int N, int HW, int C, hipStream_t s);
+int icamd_pack_input_launch(const float* x, bf16_t* out, int B, int Cin, int H, int W, int mode, float lam, int yl, int yh,
+                            int xl, int xh, hipStream_t s);
+int icamd_pack_input_rgb4_launch(const float* x, bf16_t* out, int B, int Cin, int H, int W, int mode, float lam, int yl,
+                                 int yh, int xl, int xh, hipStream_t s);
+int icamd_bn_fold_launch(const float* w, const float* gamma, const float* beta, const float* rm, const float* rv, float eps,
+                         int Cout, int K, bf16_t* w_folded, float* shift, hipStream_t s);
+int icamd_sum_partials_launch(const float* part, int nrows, int C, float* out1, float* out2, int accumulate, double* chunks,
+                              float* c1c2, hipStream_t s);
+
+// squeeze-and-excitation tail (se_ops.hip)
+bool icamd_se_shape_ok(int N, int HW, int C, int rd);
+size_t icamd_se_squeeze_bytes(int N, int HW, int C);
+int icamd_se_squeeze_launch(const bf16_t* y, float* ysum, int N, int HW, int C, float* part, hipStream_t s);
+int icamd_se_excite_fwd_launch(const float* ysum, const float* scale, const float* shift, float inv_hw, const float* w1,
+                               const float* b1, const float* w2, const float* b2, float* s_out, float* h_out, float* e_out,
+                               int N, int C, int rd, hipStream_t s);
+int icamd_se_bn_apply_launch(const bf16_t* y, const float* scale, const float* shift, const float* gate, const bf16_t* residual,
+                             const float* res_scale, const float* res_shift, bf16_t* out, unsigned char* maskbits, int N, int HW,
+                             int C, int relu, hipStream_t s);
+size_t icamd_se_bn_bwd_bytes(int N, int HW, int C);
+int icamd_se_bn_bwd_launch(const bf16_t* dout, const unsigned char* maskbits, const bf16_t* y, const float* mean,
+                           const float* invstd, const float* gamma, const float* beta, const float* ysum, const float* sv,
+                           const float* h, const float* e, const float* w1, const float* w2, float* dgamma, float* dbeta,
+                           float* dw1, float* db1, float* dw2, float* db2, bf16_t* dy, int N, int HW, int C, int rd,
+                           int accumulate, void* workspace, hipStream_t s);
+
+// loss, step metrics, optimizers, filter preparation, column sums (loss_optim.hip)
+int icamd_softmax_xent_launch(const bf16_t* logits, int ld, int B, int C, const long long* y1, const long long* y2,
+                              float lam, float smoothing, float gscale, float* loss_rows, int* pred, bf16_t* dlogits,
+                              hipStream_t s);
+int icamd_step_metrics_launch(const float* loss_rows, const int* pred, const long long* target, int B, int C,
+                              float* loss_out, int* finite_out, double* acc_f64, int* counts, float* loss_log,
+                              int log_slot, int log_stride, int respect_skip, hipStream_t s);
+int icamd_grad_norm_launch(const float* g, long long n, float inv_scale, float max_norm, double* partial, float* out,
+                           hipStream_t s);
+int icamd_adamw_ema_launch(float* p, float* g, float* m, float* v, float* ema, bf16_t* shadow, long long n, float lr,
+                           float wd, float beta1, float beta2, float eps, int step, float gscale, float ema_decay,
+                           const float* clip, const int* finite_flag, int* skipped, int zero_grad, hipStream_t s);
+int icamd_optim_ema_launch(int kind, float* p, float* g, float* m, float* v, float* ema, bf16_t* shadow, long long n,
+                           float lr, float wd, float beta1, float beta2, float eps, int step, float gscale,
+                           float ema_decay, const float* clip, const int* finite_flag, int* skipped, int zero_grad,
+                           hipStream_t s);
+int icamd_grad_guard_launch(float* g, long long n, const int* finite_flag, hipStream_t s);
+int icamd_lerp_launch(float* dst, const float* src, long long n, float w, const int* finite_flag, hipStream_t s);
+int icamd_f32_to_bf16_launch(const float* src, bf16_t* dst, long long n, hipStream_t s);
+int icamd_filter_transpose_launch(const bf16_t* src_base, bf16_t* dst_base, const long long* descs, const int* jobs,
+                                  int njobs, hipStream_t s);
+int icamd_filter_transpose_tiled_launch(const bf16_t* src_base, bf16_t* dst_base, const long long* descs, const int* jobs,
+                                        int njobs, hipStream_t s);
+int icamd_colsum_launch(const bf16_t* x, int rows, int ld, int cols, float* out, int accumulate, hipStream_t s);
+
+// LayerNorm, GELU, ViT tokens, row / batch reductions and copies (token_ops.hip)
+int icamd_layernorm_fwd_launch(const bf16_t* x, const float* gamma, const float* beta, bf16_t* y, float* mean, float* rstd,
+                               long long rows, int C, float eps, hipStream_t s);
+int icamd_layernorm_bwd_blocks(long long rows);
+int icamd_layernorm_bwd_launch(const bf16_t* dy, const bf16_t* x, const float* mean, const float* rstd, const float* gamma,
+                               const bf16_t* addend, bf16_t* dx, float* part, long long rows, int C, hipStream_t s);
+int icamd_vit_tokens_fwd_launch(const bf16_t* patches, const float* cls, const float* pos, bf16_t* tok, int B, int T, int C,
+                                hipStream_t s);
+int icamd_batch_sum_launch(const bf16_t* x, long long stride, int B, long long n, float* out, int accumulate, hipStream_t s);
+int icamd_strided_rows_copy_launch(const bf16_t* src, long long sstride, bf16_t* dst, long long dstride, long long rows,
+                                   long long C, hipStream_t s);
+int icamd_gelu_fwd_launch(const bf16_t* z, bf16_t* a, long long numel, hipStream_t s);
+int icamd_gelu_bwd_launch(const bf16_t* da, const bf16_t* z, bf16_t* dz, long long numel, hipStream_t s);
+int icamd_colsum_blocks(long long rows);
+int icamd_colsum_partial_launch(const bf16_t* x, float* part, long long rows, int ld, int cols, hipStream_t s);
+
+// ViT attention (attention.hip; sequences past its limit go on to attention_long.hip, see attention_common.h)
+int icamd_attention_fwd_launch(const bf16_t* qkv, bf16_t* out, float* lse, int B, int T, int H, float scale, hipStream_t s);
+int icamd_attention_bwd_launch(const bf16_t* qkv, const bf16_t* out, const bf16_t* dout, const float* lse, float* delta,
+                               bf16_t* dqkv, int B, int T, int H, float scale, hipStream_t s);
+
+// Swin: window attention, relative-position bias, patch merging (window_attention.hip)
+bool icamd_window_attention_ok(int Hs, int Ws, int ws, int D);
+int icamd_window_attention_bwd_chunks(long long nwin, int H, int ws);
+int icamd_window_attention_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
+                                      int ws, int shift, float scale, hipStream_t s);
+int icamd_window_attention_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout, const float* lse,
+                                      bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs, int Ws, int H, int ws,
+                                      int shift, float scale, hipStream_t s);
+int icamd_relpos_bias_gather_launch(const float* table, float* bias, int H, int ws, hipStream_t s);
+int icamd_relpos_bias_scatter_launch(const float* dbias, float* dtable, int H, int ws, int accumulate, hipStream_t s);
+bool icamd_patch_merge_ln_ok(int N, int H, int W, int C);
+int icamd_patch_merge_ln_bwd_blocks(long long rows);
+int icamd_patch_merge_ln_fwd_launch(const bf16_t* x, const float* gamma, const float* beta, bf16_t* y, float* mean, float* rstd,
+                                    int N, int H, int W, int C, float eps, hipStream_t s);
+int icamd_patch_merge_ln_bwd_launch(const bf16_t* dy, const bf16_t* x, const float* mean, const float* rstd, const float* gamma,
+                                    bf16_t* dx, float* dgamma, float* dbeta, int N, int H, int W, int C, int accumulate, float* part,
+                                    hipStream_t s);
+
+// 12 x 12 windows (window_attention_w12.hip), reached through the launchers above
+int icamd_window_attention_w12_bwd_chunks(long long nwin, int H);
+int icamd_window_attention_w12_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
+                                          int shift, float scale, hipStream_t s);
+int icamd_window_attention_w12_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout,
+                                          const float* lse, bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs,
+                                          int Ws, int H, int shift, float scale, hipStream_t s);
+
+// ConvNeXt: depthwise 7x7, layer scale / stochastic depth (dwconv.hip)
+int icamd_dwconv7_launch(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* addend, bf16_t* y, int N, int H,
+                         int W, int C, int flip, hipStream_t s);
+int icamd_dwconv7_wgrad_blocks(int N, int H, int W, int C);
+int icamd_dwconv7_wgrad_launch(const bf16_t* x, const bf16_t* dy, float* part, float* dw, float* dbias, int N, int H, int W, int C,
+                               int accumulate, hipStream_t s);
+bool icamd_dwconv7_wgrad_bias_supported_cxx(int N, int H, int W, int C);
+int icamd_layerscale_fwd_launch(const bf16_t* z, const bf16_t* inp, const float* gamma, const float* keep, bf16_t* out,
+                                long long rows, int C, long long rows_per_image, hipStream_t s);
+int icamd_layerscale_bwd_blocks(long long rows);
+int icamd_layerscale_fold_launch(const float* params, bf16_t* shadow, float* fold_bias, const long long* jobs, int njobs,
+                                 int total_rows, hipStream_t s);
+int icamd_rows_fix_launch(const float* keep, int n_images, void* dst1, const void* src1, long long bytes1, void* dst2,
+                          long long bytes2, hipStream_t s);
+int icamd_dropped_colsum_launch(const bf16_t* dy, const float* keep, int n_images, long long rows_per_image, int C, float* partial,
+                                hipStream_t s);
+int icamd_layerscale_param_grads_launch(const float* G, const float* w, const float* bias, const float* gamma,
+                                        const float* colsum_all, const float* dropped, int n_images, float cb, int C, int K,
+                                        float* dw, float* dbias, float* dgamma, int accumulate, hipStream_t s);
+int icamd_layerscale_bwd_launch(const bf16_t* dout, const bf16_t* z, const float* gamma, const float* keep, bf16_t* dz,
+                                float* part, long long rows, int C, long long rows_per_image, hipStream_t s);

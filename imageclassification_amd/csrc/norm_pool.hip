@@ -1039,7 +1039,7 @@ inline int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } retu
 
 }  // namespace
 
-// ---------------- host launchers (called from capi.hip) ----------------
+// ---------------- host launchers (called from the capi*.hip units) ----------------
 
 static void chunking(int nrows, int* rows_per_chunk, int* nchunks) {
   int rpc = 128;

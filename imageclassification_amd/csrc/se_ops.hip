@@ -405,7 +405,7 @@ unsigned int blocks_per_sample(int N, int HW, int cpr) {
 
 }  // namespace
 
-// ---------------- host launchers (called from capi.hip) ----------------
+// ---------------- host launchers (called from the capi*.hip units) ----------------
 
 bool icamd_se_shape_ok(int N, int HW, int C, int rd) {
   return N > 0 && N <= 65535 && HW > 0 && C > 0 && C % 8 == 0 && C <= 4096 && rd >= 1 && rd <= 256 &&

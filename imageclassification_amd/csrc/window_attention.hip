@@ -593,12 +593,6 @@ int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // 12 x 12 windows (T = 144: nine MFMA blocks per side) run on the kernels of window_attention_w12.hip
 constexpr int WS12 = 12;
-int icamd_window_attention_w12_bwd_chunks(long long nwin, int H);
-int icamd_window_attention_w12_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
-                                          int shift, float scale, hipStream_t s);
-int icamd_window_attention_w12_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout,
-                                          const float* lse, bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs,
-                                          int Ws, int H, int shift, float scale, hipStream_t s);
 
 bool icamd_window_attention_ok(int Hs, int Ws, int ws, int D) {
   return D == WD && ((ws >= 2 && ws <= 8) || ws == WS12) && Hs > 0 && Ws > 0 && Hs % ws == 0 && Ws % ws == 0;

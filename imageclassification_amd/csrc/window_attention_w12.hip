@@ -33,13 +33,6 @@
 #include "icamd_internal.h"
 #include "attention_common.h"   // pack_acc2, group_max, group_sum
 
-int icamd_window_attention_w12_bwd_chunks(long long nwin, int H);
-int icamd_window_attention_w12_fwd_launch(const bf16_t* qkv, const float* bias, bf16_t* out, float* lse, int B, int Hs, int Ws, int H,
-                                          int shift, float scale, hipStream_t s);
-int icamd_window_attention_w12_bwd_launch(const bf16_t* qkv, const float* bias, const bf16_t* out, const bf16_t* dout,
-                                          const float* lse, bf16_t* dqkv, float* dbias, int accumulate, float* part, int B, int Hs,
-                                          int Ws, int H, int shift, float scale, hipStream_t s);
-
 namespace {
 
 constexpr int WS = 12, T = WS * WS;    // window side, tokens per window

@@ -152,3 +152,40 @@ def test_routing_did_not_move(r50):
     print("prof calls:", calls)
     assert calls == PROF_CALLS
     assert torch.equal(net.grad_arena, default)
+
+
+def test_profiler_state_is_one_object_across_the_capi_units():
+    """The C-ABI layer is five translation units (csrc/capi*.hip) around one profiler state, defined in capi.hip.  One tiny call
+    into each unit while profiling is on: icamd_prof_collect (capi.hip) sees exactly one call in each of their five classes and none
+    anywhere else -- a unit with a state of its own would never see the switch, or would keep its record to itself."""
+    import ctypes
+    from imageclassification_amd import hip
+    lib = hip.load()
+    dev, s = "cuda", hip.stream_ptr()
+    bf = lambda *shape: torch.zeros(*shape, dtype=torch.bfloat16, device=dev)      # noqa: E731
+    f32 = lambda *shape: torch.ones(*shape, dtype=torch.float32, device=dev)       # noqa: E731
+    x, w, y = bf(1, 8, 8, 64), bf(64, 1, 1, 64), bf(1, 8, 8, 64)                   # capi.hip: 1x1 convolution, 64 -> 64 at 8 x 8
+    d = hip.conv_desc(1, 8, 8, 64, 64, 1, 1, 1, 0)
+    gamma, beta, rm, rv, scale, shift = (f32(64) for _ in range(6))                # capi_norm.hip: C = 64
+    z, a = bf(1024), bf(1024)                                                      # capi_tokens.hip
+    src, dst = f32(1024), bf(1024)                                                 # capi_step.hip
+    px, pout = bf(1, 2, 2, 8), bf(1, 1, 1, 8)                                      # capi_conv_special.hip: 2x2 average pool, C = 8
+    torch.cuda.synchronize()
+    hip.prof_collect()
+    lib.icamd_prof_enable(1)
+    try:
+        hip.check(lib.icamd_conv2d_fwd(ctypes.byref(d), x.data_ptr(), w.data_ptr(), y.data_ptr(), None, None, None, s), "conv2d_fwd")
+        hip.check(lib.icamd_bn_eval_coeffs(64, gamma.data_ptr(), beta.data_ptr(), rm.data_ptr(), rv.data_ptr(), 1e-5,
+                                           scale.data_ptr(), shift.data_ptr(), s), "bn_eval_coeffs")
+        hip.check(lib.icamd_gelu_fwd(z.data_ptr(), a.data_ptr(), 1024, s), "gelu_fwd")
+        hip.check(lib.icamd_f32_to_bf16(src.data_ptr(), dst.data_ptr(), 1024, s), "f32_to_bf16")
+        hip.check(lib.icamd_avgpool2x2_fwd(px.data_ptr(), pout.data_ptr(), 1, 2, 2, 8, s), "avgpool2x2_fwd")
+        torch.cuda.synchronize()
+    finally:
+        lib.icamd_prof_enable(0)
+    calls = {k: v[1] for k, v in hip.prof_collect().items()}
+    print("prof calls:", {k: v for k, v in calls.items() if v})
+    expected = {"conv_fwd": 1, "bn_finalize": 1, "elementwise": 1, "optimizer": 1, "pool": 1}
+    assert calls == {k: expected.get(k, 0) for k in hip.PROF_CLASSES}
+    assert bool((dst.float() == 1).all())                                          # the calls ran: f32 ones arrived as bf16 ones
+    assert all(v[1] == 0 for v in hip.prof_collect().values())                     # collected once, the log is empty
