@@ -241,24 +241,18 @@ class ResNet(ArenaModel):
     # ------------------------------------------------------------------ structure
     def _build_graph(self):
         self.convs, self.bns = [], []
-        # stem filters live as [64][8][8][4] (row 7, column 7, channel 3 zero): the layout icamd_stem7x7s2_fwd / _wgrad
-        # reduce over, on the [N][H][W+8][4] image icamd_pack_input_rgb4 writes
-        if self.deep:
-            # deep stem: three conv + BatchNorm pairs; the first convolution reads the 8-channel packed image (icamd_pack_input) on
-            # the general entries, the other two are the thin 3x3 problems.  stem_conv is the first of them (what reads the image);
-            # stem_bn is bn1, whose apply is fused with the max-pool as for the plain stem
-            self.stem_pairs = []
-            for (n, cin, cout, k, st, pad, g), (bn_name, bn_c) in stem_specs(self.arch):
-                conv = self._conv(n, cin, cout, k, st, pad, cin_p=8 if cin == 3 else None)
-                conv.thin = cin == 32
-                self.stem_pairs.append((conv, self._bn(bn_name, bn_c)))
-            self.stem_conv = self.stem_pairs[0][0]
-            self.stem_bn = self.stem_pairs[-1][1]
-        else:
-            self.stem_conv = self._conv("conv1", 3, 64, 7, 2, 3, cin_p=4, k_p=8)
-            self.stem_conv.stem7 = True
-            self.stem_bn = self._bn("bn1", 64)
-            self.stem_pairs = [(self.stem_conv, self.stem_bn)]
+        # The stem as conv + BatchNorm pairs: the 7x7 / stride 2 one, or the deep stem's three 3x3 ones.  The 7x7 filters live as
+        # [64][8][8][4] (row 7, column 7, channel 3 zero): the layout icamd_stem7x7s2_fwd / _wgrad reduce over, on the [N][H][W+8][4]
+        # image icamd_pack_input_rgb4 writes.  The deep stem's first convolution reads the 8-channel packed image (icamd_pack_input)
+        # on the general entries, the other two are the thin 3x3 problems.  stem_conv is what reads the image; stem_bn is bn1, whose
+        # apply is fused with the max-pool
+        self.stem_pairs = []
+        for (n, cin, cout, k, st, pad, g), (bn_name, bn_c) in stem_specs(self.arch):
+            conv = self._conv(n, cin, cout, k, st, pad, cin_p=(4 if k == 7 else 8) if cin == 3 else None, k_p=8 if k == 7 else None)
+            conv.stem7, conv.thin = k == 7, cin == 32
+            self.stem_pairs.append((conv, self._bn(bn_name, bn_c)))
+        self.stem_conv = self.stem_pairs[0][0]
+        self.stem_bn = self.stem_pairs[-1][1]
         self.blocks = []
         inplanes = 64
         for spec in block_specs(self.arch):
@@ -437,52 +431,6 @@ class ResNet(ArenaModel):
                                                      self.eval_shift.data_ptr() + 4 * bn.shift_offset, s), bn.name)
         self._fold_dirty = False
 
-    def _conv_act_eval(self, conv, bn, x, N, IH, IW, out, residual, relu, s):
-        d = conv.desc(N, IH, IW)
-        self._conv_fwd(conv, d, x, self.shadow_eval.data_ptr() + 2 * conv.w.offset, out.data_ptr(), s,
-                       shift=self.eval_shift.data_ptr() + 4 * bn.shift_offset, residual=residual, relu=int(relu))
-        return d
-
-    def _forward_eval_folded(self, ws):
-        lib = self.lib
-        s = hip.stream_ptr()
-        N, H, W = ws["N"], ws["H"], ws["Ws"]
-        if self._fold_dirty:
-            self.fold_batchnorm()
-        cur, ch, cw = ws["x8"], H, W
-        for (conv, bn), out in zip(self.stem_pairs, ws.get("stem_a", []) + [ws["a0"]]):
-            d0 = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, out, None, True, s)
-            cur, ch, cw = out, d0.OH, d0.OW
-        hip.check(lib.icamd_maxpool3x3s2_fwd(ws["a0"].data_ptr(), ws["p0"].data_ptr(), None, N, d0.OH, d0.OW, 64, s),
-                  "maxpool")
-        x = ws["p0"]
-        h, w = x.shape[1], x.shape[2]
-        for blk, b in zip(self.blocks, ws["blocks"]):
-            if "down_conv" in blk:
-                xs, sh_, sw_ = self._shortcut_input(blk, b, x, N, h, w, s)
-                self._conv_act_eval(blk["down_conv"], blk["down_bn"], xs.data_ptr(), N, sh_, sw_, b["ad"], None, False, s)
-                idn = b["ad"]
-            else:
-                idn = x
-            cur, ch, cw = x, h, w
-            n = len(blk["convs"])
-            for i, (conv, bn) in enumerate(zip(blk["convs"], blk["bns"])):
-                if i == n - 1 and "se" in blk:
-                    # the folded convolution alone (z = conv + shift, no activation), then the SE tail with identity coefficients
-                    d = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, b["y"][i], None, False, s)
-                    one = ws["se_ident"].data_ptr()
-                    self._se_tail(ws, blk, b, one, one + 4 * 4096, idn.data_ptr(), None, N, d.OH * d.OW, s)
-                else:
-                    d = self._conv_act_eval(conv, bn, cur.data_ptr(), N, ch, cw, b["a"][i],
-                                            idn.data_ptr() if i == n - 1 else None, True, s)
-                cur, ch, cw = b["a"][i], d.OH, d.OW
-            x, h, w = cur, ch, cw
-        hip.check(lib.icamd_avgpool_fwd(x.data_ptr(), ws["pooled"].data_ptr(), N, h * w, self.feat_dim, s), "avgpool")
-        dfc = self.fc.desc(N, 1, 1)
-        hip.check(lib.icamd_conv2d_fwd(ctypes.byref(dfc), ws["pooled"].data_ptr(), self._w(self.fc),
-                                       ws["logits"].data_ptr(), self._pf(self.fc.b), None, None, s), "fc")
-        return ws["logits"]
-
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, N, H, W):
         key = (N, H, W)
@@ -496,49 +444,38 @@ class ResNet(ArenaModel):
         def act(n, h, w, c):
             return torch.empty(n, h, w, c, dtype=torch.bfloat16, device=dev)
 
-        # the rgb4 stem layout (3 + 5 zero columns per row); an odd width gets one more zero column -- part of the
-        # convolution's own padding -- and the stem kernels run on the even width Ws
-        if self.deep:
-            # deep stem: the 8-channel packed image; stem_in[i] / stem_y[i] = input / raw output of the i-th stem convolution,
-            # stem_a[i] = its BatchNorm + ReLU output (the third one's goes through the fused max-pool and is never stored:
-            # y0 is stem_y[2]); the batch statistics sit in the stat arena (_stats(bn))
-            Ws = W
-            ws["Ws"] = Ws
-            ws["x8"] = act(N, H, W, 8)
-            ws["stem_y"], ws["stem_a"], ws["stem_in"], ws["stem_hw"] = [], [], [ws["x8"]], []
-            max_act, max_stats, max_wg, max_bnb = ws["x8"].numel(), 0, 0, 0
-            sh_, sw_ = H, W
-            for i, (conv, bn) in enumerate(self.stem_pairs):
-                d0 = conv.desc(N, sh_, sw_)
-                ws["stem_hw"].append((sh_, sw_))
-                ws["stem_y"].append(act(N, d0.OH, d0.OW, conv.cout_p))
-                if i + 1 < len(self.stem_pairs):
-                    ws["stem_a"].append(act(N, d0.OH, d0.OW, conv.cout_p))
-                    ws["stem_in"].append(ws["stem_a"][-1])
-                max_act = max(max_act, ws["stem_y"][-1].numel())
-                max_stats = max(max_stats, self._stats_rows(conv, d0) * 2 * conv.cout_p)
-                max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d0))
-                max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, conv.cout_p))
-                sh_, sw_ = d0.OH, d0.OW
-            ws["y0"] = ws["stem_y"][-1]
-        else:
-            Ws = W + (W & 1)
-            ws["Ws"] = Ws
-            ws["x8"] = act(N, H, Ws + 8, 4)
-            d0 = self.stem_conv.desc(N, H, Ws)
-            ws["y0"] = act(N, d0.OH, d0.OW, 64)
+        # The image: 8 channels packed, or for the 7x7 stem the rgb4 layout (3 + 5 zero columns per row); there an odd width gets one
+        # more zero column -- part of the convolution's own padding -- and the stem kernels run on the even width Ws.
+        # stem_in[i] / stem_y[i] = input / raw output of the i-th stem convolution, stem_a[i] = its BatchNorm + ReLU output (the last
+        # one's goes through the fused max-pool and is never stored: y0 is stem_y[-1]); the batch statistics sit in the stat arena
+        # (_stats(bn))
+        rgb4 = self.stem_conv.stem7
+        Ws = W + (W & 1) if rgb4 else W
+        ws["Ws"] = Ws
+        ws["x8"] = act(N, H, Ws + 8, 4) if rgb4 else act(N, H, W, 8)
+        ws["stem_y"], ws["stem_a"], ws["stem_in"], ws["stem_hw"] = [], [], [ws["x8"]], []
+        max_act, max_stats, max_wg, max_bnb = ws["x8"].numel(), 0, 0, 0
+        sh_, sw_ = H, Ws
+        for i, (conv, bn) in enumerate(self.stem_pairs):
+            d0 = conv.desc(N, sh_, sw_)
+            ws["stem_hw"].append((sh_, sw_))
+            ws["stem_y"].append(act(N, d0.OH, d0.OW, conv.cout_p))
+            if i + 1 < len(self.stem_pairs):
+                ws["stem_a"].append(act(N, d0.OH, d0.OW, conv.cout_p))
+                ws["stem_in"].append(ws["stem_a"][-1])
+            max_act = max(max_act, ws["stem_y"][-1].numel())
+            max_stats = max(max_stats, self._stats_rows(conv, d0) * 2 * conv.cout_p)
+            max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d0))
+            max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, conv.cout_p))
+            sh_, sw_ = d0.OH, d0.OW
+        ws["y0"] = ws["stem_y"][-1]
         ws["a0"] = act(N, d0.OH, d0.OW, 64)
         PH, PW = (d0.OH - 1) // 2 + 1, (d0.OW - 1) // 2 + 1
         ws["p0"] = act(N, PH, PW, 64)
         ws["p0_idx"] = torch.empty(N, PH, PW, 64, dtype=torch.uint8, device=dev)
-        if not self.deep:
-            max_act = max(ws["y0"].numel(), ws["x8"].numel())
-            max_stats = lib.icamd_conv2d_stats_rows(ctypes.byref(d0)) * 2 * 64
-            max_wg = self._wgrad_workspace_bytes(self.stem_conv, d0)
-            max_bnb = lib.icamd_bn_bwd_workspace_bytes(N * d0.OH * d0.OW, 64)
         h, w = PH, PW
         blocks_ws = []
-        max_se = 0
+        max_se = max_fused = 0
         for blk in self.blocks:
             b = {}
             ih, iw = h, w
@@ -569,6 +506,11 @@ class ResNet(ArenaModel):
                 max_stats = max(max_stats, self._stats_rows(conv, d) * 2 * conv.cout_p)
                 max_wg = max(max_wg, self._wgrad_workspace_bytes(conv, d))
                 max_bnb = max(max_bnb, lib.icamd_bn_bwd_workspace_bytes(N * d.OH * d.OW, conv.cout_p))
+            if self.block == "bottleneck" and "se" not in blk:
+                # what the fused convolution + BatchNorm backward may take (_bwd_last_bn): the last convolution and a stride-1 shortcut
+                for conv, d in launches[len(ys) - 1:]:
+                    if conv.stride == 1 and lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d)):
+                        max_fused = max(max_fused, lib.icamd_conv1x1_bn_bwd_fused_workspace_bytes(ctypes.byref(d)))
             if "se" in blk:
                 se = blk["se"]
                 hw_out = ih * iw
@@ -595,6 +537,9 @@ class ResNet(ArenaModel):
         ws["bnb_ws2"] = torch.zeros(max_bnb, dtype=torch.uint8, device=dev)   # second BatchNorm of icamd_bn_bwd_dual
         ws["bnb_ws_bytes"] = max_bnb
         ws["max_act"] = max_act
+        if max_fused > 0:     # slab workspace of icamd_conv1x1_bn_bwd_fused (main stream; the side stream's wgrads own wgrad_ws)
+            ws["fused_ws"] = torch.empty(max_fused, dtype=torch.uint8, device=dev)
+            ws["fused_ws_bytes"] = max_fused
         if self.se:
             ws["se_ws"] = torch.empty(max_se, dtype=torch.uint8, device=dev)
             ws["se_ws_bytes"] = max_se
@@ -640,15 +585,6 @@ class ResNet(ArenaModel):
         if self._thin(conv, d, "fwd"):
             return self.lib.icamd_conv3x3_thin_stats_rows(ctypes.byref(d))
         return self.lib.icamd_conv2d_stats_rows(ctypes.byref(d))
-
-    def _shortcut_input(self, blk, b, x, N, h, w, s):
-        """What a projection shortcut's convolution reads, with its size: the block input, or (D variants, stride-2 blocks) its
-        2x2 average into b["xp"]."""
-        if not blk.get("pool"):
-            return x, h, w
-        hip.check(self.lib.icamd_avgpool2x2_fwd(x.data_ptr(), b["xp"].data_ptr(), N, h, w, blk["down_conv"].cin_p, s),
-                  blk["name"] + " shortcut pool")
-        return (b["xp"],) + b["short_hw"]
 
     def _conv_fwd(self, conv, d, x, w, y, s, stats=None, shift=None, residual=None, relu=0):
         """y = conv(x) with filters `w`.  Training form (shift None): the raw output, BatchNorm statistic rows to `stats`.  Folded
@@ -704,43 +640,65 @@ class ResNet(ArenaModel):
             rc = self.lib.icamd_conv2d_dgrad(ctypes.byref(d), dy, self._wt(conv), dx, addend, addend_bits, s)
         hip.check(rc, conv.name + " dgrad")
 
-    def _conv_bn_fwd(self, ws, conv, bn, x, N, IH, IW, y, out, residual, relu, s, maskbits=None, res_bn=None, conv_launch=None):
-        """y = conv(x); out = act(bn(y) (+ residual)). Training: batch statistics from the conv epilogue.
-        conv_launch(stats_ptr): replaces the convolution launch (round 5: the fused "previous block's apply + this conv1" kernel)."""
-        lib = self.lib
-        d = conv.desc(N, IH, IW)
-        c = bn.c
-        stats = ws["stats"].data_ptr() if self.training else None
-        if conv_launch is not None:
-            conv_launch(stats)
-        else:
-            self._conv_fwd(conv, d, x, self._w(conv), y.data_ptr(), s, stats=stats)
-        rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
-        if self.training:
-            mean, invstd, scale, shift = self._stats(bn)
-            rows = self._stats_rows(conv, d)
-            hip.check(lib.icamd_bn_train_finalize(stats, rows, c, float(N * d.OH * d.OW), self._pf(bn.weight),
-                                                  self._pf(bn.bias), rm, rm + 4 * c, BN_MOMENTUM, BN_EPS, mean, invstd,
-                                                  scale, shift, ws["bn_ws"].data_ptr(), s), bn.name)
-        else:
-            scale = ws["scale_shift_eval"].data_ptr()
-            shift = scale + 4 * 2048
-            hip.check(lib.icamd_bn_eval_coeffs(c, self._pf(bn.weight), self._pf(bn.bias), rm, rm + 4 * c, BN_EPS, scale,
-                                               shift, s), bn.name)
-        if out is None:      # the caller fuses the apply into its own kernel (stem: BN + ReLU + max-pool)
-            return d, scale, shift
-        if res_bn is not None:   # residual = raw shortcut conv output; its BatchNorm is applied inside the same pass
-            hip.check(lib.icamd_bn_apply_res_bn(y.data_ptr(), scale, shift, residual, res_bn[0], res_bn[1], out.data_ptr(),
-                                                maskbits, y.numel(), c, int(relu), s), bn.name)
-            return d
-        hip.check(lib.icamd_bn_apply(y.data_ptr(), scale, shift, residual, out.data_ptr(), maskbits, y.numel(), c, int(relu),
-                                     s), bn.name)
+    # The per-layer primitives of the forward walk.  `fw` is _forward_begin's record; x, y, out are activation tensors, residual and
+    # mask pointers (or None), res_bn the (scale, shift) pointers of a BatchNorm to apply to the residual on the way (or None).
+    def _conv_folded(self, fw, conv, bn, x, ih, iw, out, relu, residual=None):
+        """Folded form: out = act(conv(x) + shift (+ residual)) on the BatchNorm-folded filters, one launch."""
+        d = conv.desc(fw.N, ih, iw)
+        self._conv_fwd(conv, d, x.data_ptr(), self.shadow_eval.data_ptr() + 2 * conv.w.offset, out.data_ptr(), fw.s,
+                       shift=self.eval_shift.data_ptr() + 4 * bn.shift_offset, residual=residual, relu=int(relu))
         return d
 
-    def _se_tail(self, ws, blk, b, scale, shift, res, res_bn, N, HW, s):
+    def _bn_coeffs(self, fw, conv, bn, d):
+        """(scale, shift) of `bn` over the raw output of `conv`: from the statistic rows the convolution just wrote (training; also
+        the saved mean / invstd and the running statistics), or from the running statistics (eval)."""
+        lib, c = self.lib, bn.c
+        rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
+        if fw.training:
+            mean, invstd, scale, shift = self._stats(bn)
+            rows = self._stats_rows(conv, d)
+            hip.check(lib.icamd_bn_train_finalize(fw.stats, rows, c, float(fw.N * d.OH * d.OW), self._pf(bn.weight),
+                                                  self._pf(bn.bias), rm, rm + 4 * c, BN_MOMENTUM, BN_EPS, mean, invstd,
+                                                  scale, shift, fw.ws["bn_ws"].data_ptr(), fw.s), bn.name)
+        else:
+            scale = fw.ws["scale_shift_eval"].data_ptr()
+            shift = scale + 4 * 2048
+            hip.check(lib.icamd_bn_eval_coeffs(c, self._pf(bn.weight), self._pf(bn.bias), rm, rm + 4 * c, BN_EPS, scale,
+                                               shift, fw.s), bn.name)
+        return scale, shift
+
+    def _conv_coeffs(self, fw, conv, bn, x, ih, iw, y):
+        """y = conv(x) with what turns y into the BatchNorm output, always as (d, scale, shift), for a caller that fuses the apply
+        into a kernel of its own.  Folded form: the filters carry the BatchNorm, so y is its output already and the coefficients
+        are the identity (SE models, the only ones that ask: ws["se_ident"])."""
+        if fw.folded:
+            one = fw.ws["se_ident"].data_ptr()
+            return self._conv_folded(fw, conv, bn, x, ih, iw, y, False), one, one + 4 * 4096
+        d = conv.desc(fw.N, ih, iw)
+        self._conv_fwd(conv, d, x.data_ptr(), self._w(conv), y.data_ptr(), fw.s, stats=fw.stats)
+        return (d,) + self._bn_coeffs(fw, conv, bn, d)
+
+    def _bn_apply(self, fw, bn, y, scale, shift, out, relu, residual=None, res_bn=None, mask=None):
+        """out = act(y * scale + shift (+ residual, through its own BatchNorm where res_bn is given)); mask: the ReLU bits."""
+        if res_bn is not None:   # residual = raw shortcut conv output; its BatchNorm is applied inside the same pass
+            rc = self.lib.icamd_bn_apply_res_bn(y.data_ptr(), scale, shift, residual, res_bn[0], res_bn[1], out.data_ptr(), mask,
+                                                y.numel(), bn.c, int(relu), fw.s)
+        else:
+            rc = self.lib.icamd_bn_apply(y.data_ptr(), scale, shift, residual, out.data_ptr(), mask, y.numel(), bn.c, int(relu), fw.s)
+        hip.check(rc, bn.name)
+
+    def _conv_bn_act(self, fw, conv, bn, x, ih, iw, y, out, relu, residual=None, res_bn=None, mask=None):
+        """out = act(bn(conv(x)) (+ residual)): the folded convolution alone, or convolution + coefficients into y, then the apply."""
+        if fw.folded:
+            return self._conv_folded(fw, conv, bn, x, ih, iw, out, relu, residual)
+        d, scale, shift = self._conv_coeffs(fw, conv, bn, x, ih, iw, y)
+        self._bn_apply(fw, bn, y, scale, shift, out, relu, residual, res_bn, mask)
+        return d
+
+    def _se_tail(self, fw, blk, b, scale, shift, res, res_bn, HW):
         """The SE block's tail on the raw output y of its last convolution: per-sample sums of y, the excitation from them, then
         out = relu((y * scale + shift) * e[n, c] + shortcut) in one pass (the BatchNorm output itself is never stored)."""
-        lib, se, y = self.lib, blk["se"], b["y"][-1]
+        lib, ws, N, s, se, y = self.lib, fw.ws, fw.N, fw.s, blk["se"], b["y"][-1]
         hip.check(lib.icamd_se_squeeze(y.data_ptr(), b["se_ysum"].data_ptr(), N, HW, se.c, ws["se_ws"].data_ptr(),
                                        ws["se_ws_bytes"], s), se.name + " squeeze")
         hip.check(lib.icamd_se_excite_fwd(b["se_ysum"].data_ptr(), scale, shift, 1.0 / HW, self._pf(se.w1), self._pf(se.b1),
@@ -748,113 +706,121 @@ class ResNet(ArenaModel):
                                           b["se_e"].data_ptr(), N, se.c, se.rd, s), se.name + " excite")
         hip.check(lib.icamd_se_bn_apply(y.data_ptr(), scale, shift, b["se_e"].data_ptr(), res, res_bn[0] if res_bn else None,
                                         res_bn[1] if res_bn else None, b["a"][-1].data_ptr(),
-                                        b["mask"].data_ptr() if self.training else None, N, HW, se.c, 1, s), se.name + " apply")
+                                        b["mask"].data_ptr() if fw.training else None, N, HW, se.c, 1, s), se.name + " apply")
 
     # ------------------------------------------------------------------ forward
     def pack(self, x_nchw, mix=None):
         """fp32 NCHW device tensor -> packed NHWC bf16 (channels zero-padded to 8), with optional mixup/cutmix."""
         N, C, H, W = x_nchw.shape
         # the deep stem's first convolution reads the plain 8-channel packed image, the 7x7 stem the rgb4 layout
-        return self._pack_input(self._workspace(N, H, W), x_nchw, mix, rgb4=not self.deep)
+        return self._pack_input(self._workspace(N, H, W), x_nchw, mix, rgb4=self.stem_conv.stem7)
 
     def forward_packed(self, ws, logits_only=False):   # logits_only: accepted for interface parity (BatchNorm needs every conv output)
-        lib = self.lib
+        """Stem, residual blocks, average pool + classifier -> ws["logits"], in one of three forms: training (batch statistics), eval
+        with running statistics, or -- fold_eval, the default -- eval on BatchNorm-folded filters, one kernel per convolution."""
+        fw = self._forward_begin(ws)
+        x, h, w = self._fwd_stem(fw)
+        pending = None
+        for bi in range(len(self.blocks)):
+            x, h, w, pending = self._fwd_block(fw, bi, x, h, w, pending)
+        return self._fwd_head(fw, x, h, w)
+
+    def _forward_begin(self, ws):
+        """What the steps of one forward pass share."""
         s = hip.stream_ptr()
-        N, H, W = ws["N"], ws["H"], ws["Ws"]
-        if not self.training and self.fold_eval:
-            return self._forward_eval_folded(ws)
+        folded = not self.training and self.fold_eval
+        if folded and self._fold_dirty:
+            self.fold_batchnorm()
         if self.training:
             self.num_batches_tracked += 1
-        # stem: conv -> BatchNorm + ReLU + max-pool in one pass over the conv output (the 112x112 activation is never
-        # stored: backward recomputes the ReLU mask from y0 and the pooling argmax is recorded)
-        if self.deep:
-            # deep stem: conv -> statistics -> finalize -> BatchNorm + ReLU twice, then the third convolution into the same fused
-            # BatchNorm + ReLU + max-pool pass as the plain stem
-            sh_, sw_ = H, W
-            for i, (conv, bn) in enumerate(self.stem_pairs[:-1]):
-                d0 = self._conv_bn_fwd(ws, conv, bn, ws["stem_in"][i].data_ptr(), N, sh_, sw_, ws["stem_y"][i], ws["stem_a"][i],
-                                       None, True, s)
-                sh_, sw_ = d0.OH, d0.OW
-            d0, sc0, sh0 = self._conv_bn_fwd(ws, self.stem_pairs[-1][0], self.stem_bn, ws["stem_in"][-1].data_ptr(), N, sh_, sw_,
-                                             ws["y0"], None, None, True, s)
+        return SimpleNamespace(ws=ws, N=ws["N"], s=s, training=self.training, folded=folded,
+                               stats=ws["stats"].data_ptr() if self.training else None)
+
+    def _fwd_stem(self, fw):
+        """conv -> BatchNorm + ReLU per stem pair; the last pair's BatchNorm + ReLU runs in one pass with the max-pool over the conv
+        output (the 112x112 activation is never stored: backward recomputes the ReLU mask from y0 and the pooling argmax is
+        recorded).  Folded: the last convolution applies its ReLU and a plain max-pool follows.  Returns the pooled x, h, w."""
+        lib, ws, N, s = self.lib, fw.ws, fw.N, fw.s
+        for i, (conv, bn) in enumerate(self.stem_pairs[:-1]):
+            self._conv_bn_act(fw, conv, bn, ws["stem_in"][i], *ws["stem_hw"][i], ws["stem_y"][i], ws["stem_a"][i], True)
+        conv, bn = self.stem_pairs[-1]
+        if fw.folded:
+            d = self._conv_folded(fw, conv, bn, ws["stem_in"][-1], *ws["stem_hw"][-1], ws["a0"], True)
+            hip.check(lib.icamd_maxpool3x3s2_fwd(ws["a0"].data_ptr(), ws["p0"].data_ptr(), None, N, d.OH, d.OW, 64, s), "maxpool")
         else:
-            d0, sc0, sh0 = self._conv_bn_fwd(ws, self.stem_conv, self.stem_bn, ws["x8"].data_ptr(), N, H, W, ws["y0"], None,
-                                             None, True, s)
-        hip.check(lib.icamd_bn_relu_maxpool3x3s2_fwd(ws["y0"].data_ptr(), sc0, sh0, ws["p0"].data_ptr(),
-                                                     ws["p0_idx"].data_ptr() if self.training else None, N, d0.OH, d0.OW, 64,
-                                                     s), "stem bn+relu+maxpool")
-        x = ws["p0"]
-        h, w = x.shape[1], x.shape[2]
-        # Round 5: the final BatchNorm apply (+ shortcut + ReLU + mask) of a bottleneck block may be DEFERRED into the next block's
-        # first convolution (icamd_bn_apply_conv1x1_fused: the block output is written once and multiplied while it is in LDS instead
-        # of being re-read by that convolution); `pending` then holds what the apply needs and x is the buffer it will fill.
-        pending = None
-        nblocks = len(self.blocks)
-        for bi, (blk, b) in enumerate(zip(self.blocks, ws["blocks"])):
-            b["in"] = x
-            b["in_hw"] = (h, w)
-            convs, bns = blk["convs"], blk["bns"]
-            first_done = False
-            if pending is not None:
-                # end of the previous block + this block's conv1 (+ statistics of its bn1) in one launch, then bn1 as usual
-                pd = pending
-                pending = None
-                c0, bn0 = convs[0], bns[0]
-                d0 = c0.desc(N, h, w)
+            d, scale, shift = self._conv_coeffs(fw, conv, bn, ws["stem_in"][-1], *ws["stem_hw"][-1], ws["y0"])
+            hip.check(lib.icamd_bn_relu_maxpool3x3s2_fwd(ws["y0"].data_ptr(), scale, shift, ws["p0"].data_ptr(),
+                                                         ws["p0_idx"].data_ptr() if fw.training else None, N, d.OH, d.OW, 64, s),
+                      "stem bn+relu+maxpool")
+        return ws["p0"], ws["p0"].shape[1], ws["p0"].shape[2]
 
-                def launch(stats_ptr, pd=pd, c0=c0, d0=d0, b=b):
-                    hip.check(lib.icamd_bn_apply_conv1x1_fused(ctypes.byref(d0), pd["y"].data_ptr(), pd["scale"], pd["shift"],
-                                                               pd["res"], pd["res_scale"], pd["res_shift"], pd["out"].data_ptr(),
-                                                               pd["mask"].data_ptr(), self._w(c0), b["y"][0].data_ptr(), stats_ptr, s),
-                              pd["name"] + " apply + " + c0.name)
+    def _fwd_shortcut(self, fw, blk, b, x, h, w):
+        """The block's residual as (tensor, res_bn).  A projection shortcut reads the block input or (D variants, stride-2 blocks)
+        its 2x2 average b["xp"].  Training: convolution + statistics only -- its BatchNorm is applied inside the block's last
+        BatchNorm pass (res_bn), the normalised shortcut is never stored (backward needs yd and the block mask, not it)."""
+        if "down_conv" not in blk:
+            return x, None
+        dc, dbn = blk["down_conv"], blk["down_bn"]
+        if blk.get("pool"):
+            hip.check(self.lib.icamd_avgpool2x2_fwd(x.data_ptr(), b["xp"].data_ptr(), fw.N, h, w, dc.cin_p, fw.s),
+                      blk["name"] + " shortcut pool")
+            x = b["xp"]
+        if fw.training:
+            _, scale, shift = self._conv_coeffs(fw, dc, dbn, x, *b["short_hw"], b["yd"])
+            return b["yd"], (scale, shift)
+        self._conv_bn_act(fw, dc, dbn, x, *b["short_hw"], b["yd"], b["ad"], False)
+        return b["ad"], None
 
-                self._conv_bn_fwd(ws, c0, bn0, x.data_ptr(), N, h, w, b["y"][0], b["a"][0], None, True, s, conv_launch=launch)
-                first_done = True
-            res_bn = None
-            if "down_conv" in blk and self.training:
-                # shortcut conv + statistics only: its BatchNorm is applied inside the block's last BatchNorm pass, the
-                # normalised shortcut is never stored (backward needs yd and the block mask, not it)
-                xs, sh_, sw_ = self._shortcut_input(blk, b, x, N, h, w, s)
-                _, scd, shd = self._conv_bn_fwd(ws, blk["down_conv"], blk["down_bn"], xs.data_ptr(), N, sh_, sw_, b["yd"], None,
-                                                None, False, s)
-                idn, res_bn = b["yd"], (scd, shd)
-            elif "down_conv" in blk:
-                xs, sh_, sw_ = self._shortcut_input(blk, b, x, N, h, w, s)
-                self._conv_bn_fwd(ws, blk["down_conv"], blk["down_bn"], xs.data_ptr(), N, sh_, sw_, b["yd"], b["ad"], None,
-                                  False, s)
-                idn = b["ad"]
+    def _defers_apply(self, fw, bi, h, w):
+        """May block bi's last BatchNorm apply (+ shortcut + ReLU + mask) wait for the next block's first convolution
+        (icamd_bn_apply_conv1x1_fused: the block output is written once and multiplied while it is in LDS instead of being
+        re-read by that convolution)?  h, w: the size of the block output."""
+        if not (fw.training and self.block == "bottleneck" and bi + 1 < len(self.blocks)):
+            return False
+        dn = self.blocks[bi + 1]["convs"][0].desc(fw.N, h, w)
+        return bool(self.lib.icamd_bn_apply_conv1x1_fused_supported(ctypes.byref(dn)))
+
+    def _fwd_block(self, fw, bi, x, h, w, pending):
+        """One residual block on its input x (h x w).  pending: None, or the previous block's deferred last apply -- then x is the
+        buffer that apply will fill, and it runs inside this block's first convolution.  Returns the block output, its size, and
+        this block's own deferred apply or None."""
+        N, s = fw.N, fw.s
+        blk, b = self.blocks[bi], fw.ws["blocks"][bi]
+        b["in"], b["in_hw"] = x, (h, w)
+        convs, bns = blk["convs"], blk["bns"]
+        first = 0
+        if pending is not None:
+            # end of the previous block + this block's conv1 (+ the statistics of its bn1) in one launch, then bn1 as usual
+            p, d = pending, convs[0].desc(N, h, w)
+            res_scale, res_shift = p.res_bn or (None, None)
+            hip.check(self.lib.icamd_bn_apply_conv1x1_fused(ctypes.byref(d), p.y.data_ptr(), p.scale, p.shift, p.residual, res_scale,
+                                                            res_shift, x.data_ptr(), p.mask, self._w(convs[0]), b["y"][0].data_ptr(),
+                                                            fw.stats, s), p.bn.name + " apply + " + convs[0].name)
+            self._bn_apply(fw, bns[0], b["y"][0], *self._bn_coeffs(fw, convs[0], bns[0], d), b["a"][0], True)
+            x, h, w, first = b["a"][0], d.OH, d.OW, 1
+        idn, res_bn = self._fwd_shortcut(fw, blk, b, b["in"], *b["in_hw"])
+        mask = b["mask"].data_ptr() if fw.training else None
+        deferred = None
+        for i in range(first, len(convs)):
+            conv, bn, y, out = convs[i], bns[i], b["y"][i], b["a"][i]
+            if i < len(convs) - 1:
+                d = self._conv_bn_act(fw, conv, bn, x, h, w, y, out, True)
+            elif "se" in blk:
+                # the gated apply takes the coefficients: no deferral into the next block
+                d, scale, shift = self._conv_coeffs(fw, conv, bn, x, h, w, y)
+                self._se_tail(fw, blk, b, scale, shift, idn.data_ptr(), res_bn, d.OH * d.OW)
+            elif self._defers_apply(fw, bi, h, w):
+                # convolution + statistics + finalize now; `out` is filled inside the next block's first convolution
+                d, scale, shift = self._conv_coeffs(fw, conv, bn, x, h, w, y)
+                deferred = SimpleNamespace(bn=bn, y=y, scale=scale, shift=shift, residual=idn.data_ptr(), res_bn=res_bn, mask=mask)
             else:
-                idn = x
-            cur, ch, cw = x, h, w
-            for i, (conv, bn) in enumerate(zip(convs, bns)):
-                last = i == len(convs) - 1
-                if i == 0 and first_done:
-                    d = conv.desc(N, ch, cw)
-                    cur, ch, cw = b["a"][i], d.OH, d.OW
-                    continue
-                defer = False
-                if last and "se" in blk:
-                    # conv3 + statistics + finalize (or the eval coefficients), then the gated apply: no deferral into the next block
-                    d, sc3, sh3 = self._conv_bn_fwd(ws, conv, bn, cur.data_ptr(), N, ch, cw, b["y"][i], None, None, True, s)
-                    self._se_tail(ws, blk, b, sc3, sh3, idn.data_ptr(), res_bn, N, d.OH * d.OW, s)
-                    cur, ch, cw = b["a"][i], d.OH, d.OW
-                    continue
-                if last and self.training and self.block == "bottleneck" and bi + 1 < nblocks:
-                    dn = self.blocks[bi + 1]["convs"][0].desc(N, ch, cw)
-                    defer = bool(lib.icamd_bn_apply_conv1x1_fused_supported(ctypes.byref(dn)))
-                if defer:
-                    # conv3 + statistics + finalize now; the apply pass happens inside the next block's first convolution
-                    d, sc3, sh3 = self._conv_bn_fwd(ws, conv, bn, cur.data_ptr(), N, ch, cw, b["y"][i], None, None, True, s)
-                    pending = {"y": b["y"][i], "scale": sc3, "shift": sh3, "res": idn.data_ptr(),
-                               "res_scale": res_bn[0] if res_bn else None, "res_shift": res_bn[1] if res_bn else None,
-                               "out": b["a"][i], "mask": b["mask"], "name": bn.name}
-                else:
-                    d = self._conv_bn_fwd(ws, conv, bn, cur.data_ptr(), N, ch, cw, b["y"][i], b["a"][i],
-                                          idn.data_ptr() if last else None, True, s,
-                                          b["mask"].data_ptr() if (last and self.training) else None,
-                                          res_bn if last else None)
-                cur, ch, cw = b["a"][i], d.OH, d.OW
-            x, h, w = cur, ch, cw
+                d = self._conv_bn_act(fw, conv, bn, x, h, w, y, out, True, idn.data_ptr(), res_bn, mask)
+            x, h, w = out, d.OH, d.OW
+        return x, h, w, deferred
+
+    def _fwd_head(self, fw, x, h, w):
+        """Global average pool + classifier -> ws["logits"]."""
+        lib, ws, N, s = self.lib, fw.ws, fw.N, fw.s
         hip.check(lib.icamd_avgpool_fwd(x.data_ptr(), ws["pooled"].data_ptr(), N, h * w, self.feat_dim, s), "avgpool")
         dfc = self.fc.desc(N, 1, 1)
         hip.check(lib.icamd_conv2d_fwd(ctypes.byref(dfc), ws["pooled"].data_ptr(), self._w(self.fc),
@@ -925,17 +891,12 @@ class ResNet(ArenaModel):
 
     def _fused_conv_bn(self, run, conv, bn, d, partials, nrows, g, y, x, dx, bn_ws, bn_ws_bytes):
         """BatchNorm-backward apply + data gradient + weight gradient of `conv` -> `bn` in one pass over g (already masked) and y
-        (round 5, icamd_conv1x1_bn_bwd_fused); main stream, its own slab workspace (the side stream's weight gradients own
-        ws["wgrad_ws"])."""
-        lib, ws = self.lib, run.ws
+        (round 5, icamd_conv1x1_bn_bwd_fused); main stream, on the slab workspace _workspace sized for it (ws["fused_ws"])."""
+        ws = run.ws
         mean, invstd, scale, _ = self._stats(bn)
-        need = lib.icamd_conv1x1_bn_bwd_fused_workspace_bytes(ctypes.byref(d))
-        fws = ws.get("fused_ws")
-        if fws is None or fws.numel() < need:
-            fws = ws["fused_ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        hip.check(lib.icamd_conv1x1_bn_bwd_fused(ctypes.byref(d), partials, nrows, g, y.data_ptr(), mean, invstd, scale,
+        hip.check(self.lib.icamd_conv1x1_bn_bwd_fused(ctypes.byref(d), partials, nrows, g, y.data_ptr(), mean, invstd, scale,
                                                  self._gf(bn.weight), self._gf(bn.bias), x, self._wt(conv), dx, self._gf(conv.w),
-                                                 run.acc, bn_ws, bn_ws_bytes, fws.data_ptr(), fws.numel(), run.s),
+                                                 run.acc, bn_ws, bn_ws_bytes, ws["fused_ws"].data_ptr(), ws["fused_ws_bytes"], run.s),
                   bn.name + " + " + conv.name + " bwd (fused)")
 
     def _bwd_classifier(self, run, dout):
@@ -1123,7 +1084,7 @@ class ResNet(ArenaModel):
         """maxpool -> BN+ReLU -> conv (no data gradient for the image); dy: buffer for the stem convolution's output gradient."""
         lib, ws, N, s = self.lib, run.ws, run.N, run.s
         last = self.stem_pairs[-1][0]
-        d0 = last.desc(N, *ws["stem_hw"][-1]) if self.deep else last.desc(N, ws["H"], ws["Ws"])
+        d0 = last.desc(N, *ws["stem_hw"][-1])
         bn0 = self.stem_bn
         if fused_pool:
             # max-pool backward folded into both BatchNorm-backward passes: the 112x112 gradient is never materialised
@@ -1134,10 +1095,7 @@ class ResNet(ArenaModel):
         else:
             hip.check(lib.icamd_maxpool3x3s2_bwd(dout, ws["p0_idx"].data_ptr(), run.DA, N, d0.OH, d0.OW, 64, s), "maxpool bwd")
             self._bn_bwd(run, bn0, run.DA, None, ws["y0"], dy, None, True)
-        if not self.deep:
-            self._side_wgrad(run, self.stem_conv, d0, ws["x8"].data_ptr(), dy)
-            return
-        # deep stem, last convolution to first: weight gradient (side lane) + data gradient, then the BatchNorm + ReLU in front
+        # The stem's convolutions, last to first: weight gradient (side lane) + data gradient, then the BatchNorm + ReLU in front
         # (mask recomputed from y); the first convolution reads the image: weight gradient only.  The two data gradients go to
         # different scratch buffers (run.DA, run.T) and ws["stem_dy"][i] / ws["stem_dx"][i] name the gradient of the i-th
         # convolution's output / input, so that all of them can be read back after the pass (tests/test_resnet_d_gpu.py)

@@ -1,4 +1,4 @@
-"""Generates tests/golden/call_traces.json: one SHA-256 per case over every library call a ViT, Swin or ConvNeXt step makes.
+"""Generates tests/golden/call_traces.json: one SHA-256 per case over every library call a ViT, Swin, ConvNeXt or ResNet step makes.
 
 Run at the commit whose launches are to be pinned (no GPU needed):
     python tests/golden/make_call_traces.py
@@ -6,20 +6,23 @@ To see what moved when the test fails, write the records themselves at both comm
     python tests/golden/make_call_traces.py --dump DIR
 
 The models run on the CPU under make_arena_layouts.install_stubs plus three more replacements (`install_recorders`): the library
-records (entry, arguments) and returns 0, torch.cuda.current_stream is a stand-in whose stream is 0, and streams.SideLane is a
+records (entry, arguments) and returns 0 (a ResNet case carries a table of other answers for the queries, `Case.answers`),
+torch.cuda.current_stream is a stand-in whose stream is 0, and streams.SideLane is a
 lane of the same interface that runs a launch with stream 1 when it is enabled (0 otherwise) and leaves a record for every
 before_write that meets a pending read and for every join.  grad_ready_hook records (lo, hi, events).  A case is: construct at
-seed 0, train(), pack, forward_packed, backward_packed, backward_packed(accumulate=True), eval(), forward_packed(logits_only=True),
-load_state_dict(state_dict()).
+seed 0, train(), pack, forward_packed, backward_packed, backward_packed(accumulate=True), eval(), forward_packed(logits_only=True)
+(a ResNet case: twice, the second one with the BatchNorm fold already done), load_state_dict(state_dict()).  PHASES keeps where each
+phase starts in TRACE.
 
 Arguments are written by their type in hip._SIGNATURES: a descriptor as its key(), a float as its repr, the last pointer as the
 stream id, any other pointer as [number of its buffer in order of first use, byte offset, bytes of the buffer] -- looked up
 among all tensors reachable from the model (collected after every phase and kept alive, so that an address is never used twice),
-"input" for the image batch, None for NULL.  No attribute or dictionary name enters the record; a pointer into no buffer is an
+"input" for the image batch, None for NULL; a byref(BnBwdFuse) as the list of its fields, pointers in the same form.  No attribute or dictionary name enters the record; a pointer into no buffer is an
 error.  Besides the trace the file keeps, per case, the number of stream queries (hip.stream_ptr, torch.cuda.current_stream) and,
 per model, what state_dict() holds at seed 0 (`state_record`).  tests/test_call_trace_cpu.py reruns every case and compares.
 """
 import bisect
+import collections
 import ctypes
 import hashlib
 import importlib
@@ -49,37 +52,89 @@ MODELS = {
     "swin_test_w12": ("swin", "SwinTransformer", {"arch": "swin_test_w12", "img_size": 96}, 96),
     "convnext_test": ("convnext", "ConvNeXt", {"arch": "convnext_test"}, 64),
 }
-# case id -> (model id, further constructor arguments, masks per block (None: none injected), environment (None: unset))
+RESNETS = ("resnet50", "resnet18", "resnext50_32x4d", "seresnet50", "resnet50d", "resnet18d", "seresnext26d_32x4d")
+MODELS.update({arch: ("nets", "ResNet", {"arch": arch}, 64) for arch in RESNETS})
+# the models whose seed-0 weights the fixture keeps
+STATE_MODELS = ("vit_tiny_test", "swin_test", "swin_test_w12", "convnext_test", "resnet50", "seresnext26d_32x4d")
+
+# One case.  more: further constructor arguments; masks: drop-path masks per block (None: none injected); env: environment
+# (None: unset).  A ResNet case also has answers = (what a *_supported query returns, {entry: another answer}) -- with a table
+# every *_rows query returns 4 and every *_bytes query 256, so that the statistics and workspace buffers are real tensors; None:
+# every entry returns 0 --, switches: the import-time switches of nets.py, attrs: attributes set on the model, hw: the input's
+# height and width where it is not the model's square size.
+Case = collections.namedtuple("Case", "model more masks env answers switches attrs hw", defaults=({}, None, {}, None, {}, {}, None))
+RESNET_ENV = {"ICAMD_WGRAD_STREAM": None, "ICAMD_EVAL_FOLD": None}
+
+
+# every ResNet case sets every switch (a test's setter undoes itself only when the module is done)
+SWITCHES = {"_FUSED_BNBWD": False, "_DUAL_BNBWD": True, "_SUB2_SHORTCUT": True, "_FUSED_POOL_BWD": True,
+            "_STEM_THIN": {"fwd": True, "dgrad": True, "wgrad": False}}
+
+
+def _resnet(arch, supported=1, by_entry=None, switches=None, **kw):
+    return Case(arch, env=RESNET_ENV, answers=(supported, by_entry or {}), switches={**SWITCHES, **(switches or {})}, **kw)
+
+
 CASES = {
-    "vit_tiny_test/lane_off": ("vit_tiny_test", {}, None, {VIT_ENV: None}),
-    "vit_tiny_test/lane_on": ("vit_tiny_test", {}, None, {VIT_ENV: "1"}),
-    "swin_test/no_drop": ("swin_test", {"drop_path_rate": 0.0}, None, {}),
-    "swin_test/drop": ("swin_test", {"drop_path_rate": DROP_PATH}, 2, {}),
-    "swin_test_w12/no_drop": ("swin_test_w12", {"drop_path_rate": 0.0}, None, {}),
-    "swin_test_w12/drop": ("swin_test_w12", {"drop_path_rate": DROP_PATH}, 2, {}),
-    "convnext_test/lane_on": ("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: None}),
-    "convnext_test/lane_off": ("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: "0"}),
+    "vit_tiny_test/lane_off": Case("vit_tiny_test", env={VIT_ENV: None}),
+    "vit_tiny_test/lane_on": Case("vit_tiny_test", env={VIT_ENV: "1"}),
+    "swin_test/no_drop": Case("swin_test", {"drop_path_rate": 0.0}),
+    "swin_test/drop": Case("swin_test", {"drop_path_rate": DROP_PATH}, 2),
+    "swin_test_w12/no_drop": Case("swin_test_w12", {"drop_path_rate": 0.0}),
+    "swin_test_w12/drop": Case("swin_test_w12", {"drop_path_rate": DROP_PATH}, 2),
+    "convnext_test/lane_on": Case("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: None}),
+    "convnext_test/lane_off": Case("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: "0"}),
+    "resnet50/routed": _resnet("resnet50"),
+    "resnet50/plain_odd_width": _resnet("resnet50", 0, hw=(64, 63)),
+    "resnet50/gy_partials": _resnet("resnet50", 0, {"icamd_conv2d_dgrad_bnred_supported": 1}),
+    "resnet50/switches_off": _resnet("resnet50", 0, switches={"_DUAL_BNBWD": False, "_SUB2_SHORTCUT": False,
+                                                                "_FUSED_POOL_BWD": False}),
+    "resnet50/fused_bnbwd": _resnet("resnet50", switches={"_FUSED_BNBWD": True}),
+    "resnet50/one_stream_unfolded": _resnet("resnet50", attrs={"wgrad_side_stream": False, "fold_eval": False}),
+    "resnet18/basic": _resnet("resnet18", 0),
+    "resnext50_32x4d/routed": _resnet("resnext50_32x4d"),
+    "seresnet50/routed": _resnet("seresnet50"),
+    "resnet50d/thin_default": _resnet("resnet50d"),
+    "resnet50d/thin_all": _resnet("resnet50d", switches={"_STEM_THIN": {"fwd": True, "dgrad": True, "wgrad": True}}),
+    "resnet50d/thin_none_unfolded": _resnet("resnet50d", switches={"_STEM_THIN": {"fwd": False, "dgrad": False, "wgrad": False}},
+                                            attrs={"fold_eval": False}),
+    "resnet18d/basic": _resnet("resnet18d"),
+    "seresnext26d_32x4d/folded": _resnet("seresnext26d_32x4d"),
+    "seresnext26d_32x4d/unfolded": _resnet("seresnext26d_32x4d", attrs={"fold_eval": False}),
 }
 
 TRACE = []          # the records of the case that is running
+PHASES = []         # (phase, index into TRACE of its first record)
 QUERIES = [0]       # its stream queries
 
 
+class FuseFields(list):
+    """The fields of a BnBwdFuse argument, taken when the call was made: seven pointers and the relu flag."""
+
+
 class RecordingLib:
-    """Stands in for libicamd.so: every entry of hip._SIGNATURES records its call and returns 0; any other name is an error."""
+    """Stands in for libicamd.so: every entry of hip._SIGNATURES records its call and returns 0 -- or, for a query, what the
+    running case's `answers` say (Case); any other name is an error."""
+    answers = None
 
     def __getattr__(self, name):
         from imageclassification_amd import hip
         argtypes = hip._SIGNATURES[name][1]
 
-        def desc_key(a):      # byref(ConvDesc) -> the descriptor's fields, taken now
+        def by_value(a):      # byref(ConvDesc) -> the descriptor's fields, byref(BnBwdFuse) -> its fields, taken now
             d = getattr(a, "_obj", None)
+            if isinstance(d, hip.BnBwdFuse):
+                return FuseFields(getattr(d, n) for n, _ in d._fields_)
             return d.key() if isinstance(d, hip.ConvDesc) else a
 
         def entry(*args):
             assert len(args) == len(argtypes), (name, len(args), len(argtypes))
-            TRACE.append((name, argtypes, tuple(desc_key(a) for a in args)))
-            return 0
+            TRACE.append((name, argtypes, tuple(by_value(a) for a in args)))
+            if self.answers is None:
+                return 0
+            if name.endswith("_supported"):
+                return self.answers[1].get(name, self.answers[0])
+            return 4 if name.endswith("_rows") else 256 if name.endswith("_bytes") else 0
         return entry
 
 
@@ -89,6 +144,7 @@ class _Stream:
 
 class RecordingLane:
     """streams.SideLane without streams or events: same interface, same bookkeeping, and a record of every wait it would make."""
+    main = _Stream()
 
     def __init__(self, device, enabled=True):
         self.enabled = bool(enabled)
@@ -163,11 +219,17 @@ def state_record(model):
             "values": [[float(f.sum()), float(f[0]), float(f[f.numel() // 2]), float(f[-1])] for f in flat]}
 
 
-def state_tol(numel):
-    """(tolerance of a parameter's sum, of one element): the weights are below 0.25 in magnitude except the LayerNorm ones, which are
-    exact, so one float32 ulp is at most 1.5e-8 and a few ulps of evaluation difference stay below 1e-7 per element -- summed over
-    the parameter in the worst case.  A parameter drawn from other random numbers moves its sum by about 0.02 * sqrt(numel)."""
-    return 1e-7 * numel, 1e-7
+# |weight| stays below this (0.25 where a model is not listed).  A ResNet's filters are Kaiming-normal with std sqrt(2 / (cout k k)),
+# at most 0.354 (the 16-row first SE convolution): 4.0 is more than 11 standard deviations
+STATE_BOUND = {"resnet50": 4.0, "seresnext26d_32x4d": 4.0}
+
+
+def state_tol(numel, bound=0.25):
+    """(tolerance of a parameter's sum, of one element): the weights are below `bound` = 0.25 in magnitude except the LayerNorm ones,
+    which are exact, so one float32 ulp is at most 1.5e-8 and a few ulps of evaluation difference stay below 1e-7 per element --
+    summed over the parameter in the worst case.  A larger bound scales the ulp, and both tolerances, with it.  A parameter drawn
+    from other random numbers moves its sum by about 0.02 * sqrt(numel)."""
+    return 1e-7 * (bound / 0.25) * numel, 1e-7 * (bound / 0.25)
 
 
 def _masks(model, per_block):
@@ -222,7 +284,9 @@ def canonical(trace, held, x):
     for name, argtypes, args in trace:
         row = [name]
         for k, (t, a) in enumerate(zip(argtypes, args)):
-            if isinstance(a, tuple):
+            if isinstance(a, FuseFields):
+                row.append([pointer(v, f"{name} argument {k}") for v in a[:-1]] + [int(a[-1])])
+            elif isinstance(a, tuple):
                 row.append(list(a))
             elif t is ctypes.c_void_p:
                 row.append(f"stream {a}" if k == len(args) - 1 else pointer(a, f"{name} argument {k}"))
@@ -234,52 +298,80 @@ def canonical(trace, held, x):
     return out
 
 
-def run_case(case_id, setenv=None, dump=None):
-    """-> {"sha256", "calls", "stream_queries"} of one case, under install_recorders; dump: a file for the records, one per line.  setenv(name, value or None) changes the
-    environment (a test passes a function that undoes itself); by default os.environ, restored at the end."""
-    model_id, more, per_block, env = CASES[case_id]
-    saved = {k: os.environ.get(k) for k in env}
+def run_case(case_id, setenv=None, dump=None, setattr_fn=None):
+    """-> {"sha256", "calls", "stream_queries"} of one case, under install_recorders; dump: a file for the records, one per line.
+    setenv(name, value or None) changes the environment and setattr_fn(nets, switch, value) a switch of nets.py (a test passes
+    functions that undo themselves); by default os.environ and setattr, restored at the end."""
+    from imageclassification_amd import hip
+    case = CASES[case_id]
+    saved = {k: os.environ.get(k) for k in case.env}
+    saved_switches = {}
 
     def default_setenv(k, v):
         os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
 
-    for k, v in env.items():
+    for k, v in case.env.items():
         (setenv or default_setenv)(k, v)
     try:
-        del TRACE[:]
+        if case.switches:
+            nets = importlib.import_module("imageclassification_amd.nets")
+            for k, v in case.switches.items():
+                saved_switches[k] = getattr(nets, k)
+                (setattr_fn or setattr)(nets, k, v)
+        hip.load().answers = case.answers
+        del TRACE[:], PHASES[:]
         QUERIES[0] = 0
         held = {}
-        model = build_model(model_id, **more)
+        model = build_model(case.model, **case.more)
+        for k, v in case.attrs.items():
+            assert hasattr(model, k), k
+            setattr(model, k, v)
 
-        def phase(result=None):
+        def phase(name, run):
+            PHASES.append((name, len(TRACE)))
+            result = run()
             _collect(vars(model), held, set())
             return result
 
         model.grad_ready_hook = lambda lo, hi, events=(): TRACE.append(
             ("hook", (ctypes.c_int, ctypes.c_int, None), (lo, hi, tuple(events))))
-        if per_block:
-            model.injected_keep = _masks(model, per_block)
-        size = MODELS[model_id][3]
-        x = torch.randn(BATCH, 3, size, size, generator=torch.Generator().manual_seed(1))
+        if case.masks:
+            model.injected_keep = _masks(model, case.masks)
+        h, w = case.hw or (MODELS[case.model][3],) * 2
+        x = torch.randn(BATCH, 3, h, w, generator=torch.Generator().manual_seed(1))
         held[x.untyped_storage().data_ptr()] = (x.untyped_storage().nbytes(), x)
-        phase(model.train())
-        ws = phase(model.pack(x))
-        phase(model.forward_packed(ws))
-        phase(model.backward_packed(ws))
-        phase(model.backward_packed(ws, accumulate=True))
-        phase(model.eval())
-        phase(model.forward_packed(ws, logits_only=True))
-        phase(model.load_state_dict(model.state_dict()))
+        PHASES.append(("construct", 0))
+        phase("train", model.train)
+        ws = phase("pack", lambda: model.pack(x))
+        phase("forward", lambda: model.forward_packed(ws))
+        phase("backward", lambda: model.backward_packed(ws))
+        phase("backward_accumulate", lambda: model.backward_packed(ws, accumulate=True))
+        phase("eval", model.eval)
+        phase("eval_forward", lambda: model.forward_packed(ws, logits_only=True))
+        if MODELS[case.model][0] == "nets":
+            phase("eval_forward_again", lambda: model.forward_packed(ws, logits_only=True))
+        phase("reload", lambda: model.load_state_dict(model.state_dict()))
         rows = canonical(TRACE, held, x)
     finally:
+        hip.load().answers = None
         if setenv is None:
             for k, v in saved.items():
                 default_setenv(k, v)
+        if setattr_fn is None:
+            for k, v in saved_switches.items():
+                setattr(nets, k, v)
     blob = json.dumps(rows, separators=(",", ":"))
     if dump:
         with open(dump, "w") as f:
             f.writelines(json.dumps(r) + "\n" for r in rows)
     return {"sha256": hashlib.sha256(blob.encode()).hexdigest(), "calls": len(rows), "stream_queries": QUERIES[0]}
+
+
+def phase_records(name):
+    """The records of TRACE that phase `name` of the case just run made."""
+    starts = [i for _, i in PHASES] + [len(TRACE)]
+    k = [n for n, _ in PHASES].index(name)
+    return TRACE[starts[k]:starts[k + 1]]
 
 
 def main():
@@ -294,7 +386,7 @@ def main():
     for case_id in CASES:
         out["cases"][case_id] = run_case(case_id)
         print(case_id, out["cases"][case_id])
-    for model_id in MODELS:
+    for model_id in STATE_MODELS:
         out["state_dict_seed0"][model_id] = state_record(build_model(model_id))
         print(model_id, out["state_dict_seed0"][model_id]["names_and_shapes_sha256"])
     with open(os.path.join(HERE, "call_traces.json"), "w") as f:

@@ -1,5 +1,5 @@
-"""The library calls of a ViT, Swin and ConvNeXt training step, without a GPU: every launch of construct / pack / forward / backward /
-accumulating backward / eval forward / reload -- entry, arguments, buffers, stream, order, side-lane waits and gradient-hook calls --
+"""The library calls of a ViT, Swin, ConvNeXt and ResNet (nets.py) training step, without a GPU: every launch of construct / pack / forward / backward /
+accumulating backward / eval forward (ResNet: twice) / reload -- entry, arguments, buffers, stream, order, side-lane waits and gradient-hook calls --
 is the recorded one (tests/golden/call_traces.json, written by tests/golden/make_call_traces.py, whose docstring states what a
 record holds), and a seed still gives the weights it gave.
 
@@ -8,6 +8,7 @@ import ctypes
 import importlib.util
 import json
 import os
+import re
 
 import pytest
 import torch
@@ -31,7 +32,7 @@ def recorders():
 
 def test_fixture_lists_the_cases():
     assert FIXTURE["num_classes"] == G.L.NUM_CLASSES == 10 and FIXTURE["batch"] == G.BATCH == 2
-    assert list(FIXTURE["cases"]) == list(G.CASES) and list(FIXTURE["state_dict_seed0"]) == list(G.MODELS)
+    assert list(FIXTURE["cases"]) == list(G.CASES) and list(FIXTURE["state_dict_seed0"]) == list(G.STATE_MODELS)
     assert {G.CASES[c][0] for c in G.CASES} == set(G.MODELS)
 
 
@@ -40,18 +41,23 @@ def test_calls_are_the_recorded_ones(recorders, case_id):
     def setenv(name, value):
         recorders.delenv(name, raising=False) if value is None else recorders.setenv(name, value)
 
-    got = G.run_case(case_id, setenv)
+    got = G.run_case(case_id, setenv, setattr_fn=recorders.setattr)
     want = FIXTURE["cases"][case_id]
     assert got["calls"] == want["calls"]
     assert got["stream_queries"] == want["stream_queries"]
     assert got["sha256"] == want["sha256"]
 
 
+def _run(recorders, case_id):
+    return G.run_case(case_id, lambda k, v: recorders.delenv(k, raising=False) if v is None else recorders.setenv(k, v),
+                      setattr_fn=recorders.setattr)
+
+
 def test_the_cases_take_the_paths_they_are_there_for(recorders):
     """The side lane's launches carry stream 1 and make the main stream wait; the drop-path detour adds its kernels."""
     def launches(case_id):
         """(entry, its last argument: the stream of a launch) of every record but the size and support queries"""
-        G.run_case(case_id, lambda k, v: recorders.delenv(k, raising=False) if v is None else recorders.setenv(k, v))
+        _run(recorders, case_id)
         return [(r[0], r[2][-1]) for r in G.TRACE if not r[0].endswith(("_bytes", "_supported"))]
 
     for on, off in (("vit_tiny_test/lane_on", "vit_tiny_test/lane_off"), ("convnext_test/lane_on", "convnext_test/lane_off")):
@@ -66,17 +72,77 @@ def test_the_cases_take_the_paths_they_are_there_for(recorders):
         assert all(s == 0 for n, s in drop + plain if n.startswith("icamd_"))      # Swin has no side lane
 
 
-@pytest.mark.parametrize("model_id", list(G.MODELS))
+FUSED = ["icamd_bn_apply_conv1x1_fused", "icamd_conv2d_dgrad_bnred", "icamd_conv1x1_bn_bwd_fused"]
+THIN = ["icamd_conv3x3_thin_fwd", "icamd_conv3x3_thin_dgrad", "icamd_conv3x3_thin_wgrad"]
+# ResNet case -> (entries it must call, entries it must not call)
+RESNET_PATHS = {
+    "resnet50/routed": (FUSED + ["icamd_bn_bwd_maxpool3x3s2", "icamd_stem7x7s2_fwd", "icamd_stem7x7s2_wgrad"], ["icamd_bn_bwd_dual"]),
+    "resnet50/plain_odd_width": (["icamd_bn_bwd_dual", "icamd_conv2d_dgrad_sub2", "icamd_pack_input_rgb4"], FUSED),
+    "resnet50/gy_partials": (["icamd_bn_bwd_from_gy_partials", "icamd_conv2d_dgrad_bnred", "icamd_bn_bwd_dual"],
+                             ["icamd_conv1x1_bn_bwd_fused"]),
+    "resnet50/switches_off": (["icamd_maxpool3x3s2_bwd"], ["icamd_bn_bwd_dual", "icamd_conv2d_dgrad_sub2", "icamd_bn_bwd_maxpool3x3s2"]),
+    "resnet50/fused_bnbwd": (["icamd_conv2d_dgrad_bnbwd", "icamd_bn_bwd_from_partials"], []),
+    "resnet50/one_stream_unfolded": (["icamd_bn_eval_coeffs"], ["icamd_conv2d_fwd_act", "icamd_bn_fold_filters", "lane.before_write"]),
+    "resnet18/basic": (["icamd_bn_bwd_dual", "icamd_conv2d_dgrad_sub2"], []),
+    "resnext50_32x4d/routed": (["icamd_gconv3x3_fwd", "icamd_gconv3x3_fwd_act", "icamd_gconv3x3_dgrad", "icamd_gconv3x3_wgrad"], []),
+    "seresnet50/routed": (["icamd_se_squeeze", "icamd_se_excite_fwd", "icamd_se_bn_apply", "icamd_se_bn_bwd"],
+                          ["icamd_bn_apply_conv1x1_fused"]),
+    "resnet50d/thin_default": (["icamd_conv3x3_thin_fwd", "icamd_conv3x3_thin_dgrad", "icamd_avgpool2x2_fwd", "icamd_avgpool2x2_bwd"],
+                               ["icamd_conv3x3_thin_wgrad"]),
+    "resnet50d/thin_all": (["icamd_conv3x3_thin_wgrad"], []),
+    "resnet50d/thin_none_unfolded": (["icamd_avgpool2x2_fwd"], THIN),
+    "resnet18d/basic": (["icamd_avgpool2x2_bwd"], []),
+    "seresnext26d_32x4d/folded": (["icamd_gconv3x3_fwd_act", "icamd_se_bn_apply"], []),
+    "seresnext26d_32x4d/unfolded": (["icamd_se_bn_apply"], ["icamd_gconv3x3_fwd_act"]),
+}
+
+
+@pytest.fixture(scope="module")
+def resnet_calls(recorders):
+    """ResNet case -> (the entries it calls, the records of its second eval forward, the streams of its launches)"""
+    out = {}
+    for case_id in RESNET_PATHS:
+        _run(recorders, case_id)
+        streams = {r[2][-1] for r in G.TRACE if r[0].startswith("icamd_") and not r[0].endswith(("_bytes", "_supported", "_rows"))}
+        out[case_id] = ({r[0] for r in G.TRACE}, [r[0] for r in G.phase_records("eval_forward_again")], streams)
+    return out
+
+
+def test_resnet_cases_are_the_listed_ones():
+    assert set(RESNET_PATHS) == {c for c in G.CASES if G.MODELS[G.CASES[c].model][0] == "nets"}
+
+
+@pytest.mark.parametrize("case_id", list(RESNET_PATHS))
+def test_the_resnet_cases_take_the_paths_they_are_there_for(resnet_calls, case_id):
+    called, again, streams = resnet_calls[case_id]
+    must, must_not = RESNET_PATHS[case_id]
+    assert [n for n in must if n not in called] == [] and [n for n in must_not if n in called] == []
+    # the second eval forward finds the BatchNorm fold done (or, unfolded, never folds), and still runs every layer
+    assert "icamd_bn_fold_filters" not in again and "icamd_avgpool_fwd" in again
+    if case_id == "resnet50/one_stream_unfolded":
+        assert streams == {0}
+
+
+def test_the_resnet_cases_call_every_entry_nets_names(resnet_calls):
+    from imageclassification_amd import hip, nets
+    with open(nets.__file__) as f:
+        named = {n for n in re.findall(r"\bicamd_\w+", f.read()) if n in hip._SIGNATURES}
+    called = set().union(*(c for c, _, _ in resnet_calls.values()))
+    assert len(named) > 50 and sorted(named - called) == []
+
+
+@pytest.mark.parametrize("model_id", list(G.STATE_MODELS))
 def test_seed_0_gives_the_recorded_weights(recorders, model_id):
     """Names and shapes exactly; sums and sampled elements to the generator's state_tol (last-bit differences between CPUs)."""
     model = G.build_model(model_id)
     got, want = G.state_record(model), FIXTURE["state_dict_seed0"][model_id]
     assert got["names_and_shapes_sha256"] == want["names_and_shapes_sha256"]
-    assert len(got["values"]) == len(want["values"]) == len(model.params)
+    assert len(got["values"]) == len(want["values"]) == len(model.state_dict()) >= len(model.params)
     worst = [0.0, 0.0]
     for (name, t), g, w in zip(model.state_dict().items(), got["values"], want["values"]):
-        assert float(t.abs().max()) < 0.25 or bool((t == 1).all()), name          # what state_tol assumes
-        tol_sum, tol_el = G.state_tol(t.numel())
+        bound = G.STATE_BOUND.get(model_id, 0.25)
+        assert float(t.abs().max()) < bound or bool((t == 1).all()), name          # what state_tol assumes
+        tol_sum, tol_el = G.state_tol(t.numel(), bound)
         worst = [max(worst[0], abs(g[0] - w[0]) / tol_sum), max(worst[1], max(abs(a - b) for a, b in zip(g[1:], w[1:])) / tol_el)]
         assert abs(g[0] - w[0]) <= tol_sum, name
         assert all(abs(a - b) <= tol_el for a, b in zip(g[1:], w[1:])), name
