@@ -458,7 +458,7 @@ __global__ __launch_bounds__(PTHREADS, 4) void attn_bwd_dkv_kernel(const bf16_t*
 // ICAMD_ATTN_LONG (read once per process): 1 / unset = T > 208 runs on the tiled kernels of attention_long.hip, T <= 208 on the
 // resident ones above; 2 = every T on the tiled kernels (tests, A/B runs); 0 = no tiled route (T > 208 is refused, as before it existed)
 bool attn_long_wanted(int T) {
-  static const int mode = [] { const char* e = getenv("ICAMD_ATTN_LONG"); return e ? atoi(e) : 1; }();
+  static const int mode = icamd_env_int("ICAMD_ATTN_LONG", 1);
   return mode == 2 || (mode != 0 && T > 208);
 }
 

@@ -56,9 +56,8 @@ static int conv_fwd_impl(const icamd_conv_desc* d, const void* x, const void* w,
     return icamd_halo3x3_launch(h, (hipStream_t)stream);
   }
   // round 5: a 1x1 / stride-2 convolution (ResNet's projection shortcuts) is the same pointwise problem on the rows (n, 2 oh, 2 ow):
-  // the register-resident kernel gathers them in its LDS-DMA staging (ICAMD_PW_S2=0: back on conv_igemm)
-  static const bool pw_s2 = [] { const char* e = getenv("ICAMD_PW_S2"); return !(e && atoi(e) == 0); }();
-  const bool pw_gather = d->KH == 1 && d->KW == 1 && d->stride == 2 && d->pad == 0 && pw_s2 && addend == nullptr;
+  // the register-resident kernel gathers them in its LDS-DMA staging
+  const bool pw_gather = d->KH == 1 && d->KW == 1 && d->stride == 2 && d->pad == 0 && addend == nullptr;
   if (d->KH == 1 && d->KW == 1 && (d->stride == 1 || pw_gather) && d->pad == 0 && bias == nullptr && addend == nullptr && !relu &&
       gelu_out == nullptr && !gelu_inplace && icamd_pw_resident_wanted((long long)d->N * d->OH * d->OW, d->Cout, d->Cin)) {
     PwResidentParams g;
@@ -71,7 +70,7 @@ static int conv_fwd_impl(const icamd_conv_desc* d, const void* x, const void* w,
   // evaluate()'s BatchNorm-folded forward (bias = the folded shift, optional residual addend, ReLU): the same register-resident
   // kernel with the inference epilogue (round 4; these launches ran on conv_igemm's single-stage tiles before)
   if (d->KH == 1 && d->KW == 1 && (d->stride == 1 || pw_gather) && d->pad == 0 && (bias != nullptr || relu) && stats == nullptr &&
-      gelu_out == nullptr && !gelu_inplace && icamd_pw_resident_epi_wanted() &&
+      gelu_out == nullptr && !gelu_inplace &&
       icamd_pw_resident_wanted((long long)d->N * d->OH * d->OW, d->Cout, d->Cin, addend != nullptr)) {
     PwResidentParams g;
     memset(&g, 0, sizeof(g));
@@ -150,7 +149,7 @@ static int dgrad_impl(const icamd_conv_desc* d, const void* dy, const void* w_t,
   const int st = d->stride;
   // (ICAMD_PW_RESIDENT=5: the residual / even-grid addend launches stay on conv_igemm -- the A/B switch for the
   // LDS-DMA-staged addend of conv1x1_resident.hip)
-  static const bool pw_addend = [] { const char* e = getenv("ICAMD_PW_RESIDENT"); return !(e && atoi(e) == 5); }();
+  const bool pw_addend = icamd_pw_resident_mode() != 5;
   if (d->KH == 1 && d->KW == 1 && st == 1 && d->pad == 0 && f == nullptr && gelu_z == nullptr &&
       (addend == nullptr || pw_addend) && !(addend_bits != nullptr && addend_sub2) &&
       icamd_pw_resident_wanted((long long)d->N * d->IH * d->IW, d->Cin, d->Cout, addend != nullptr)) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define ICAMD_OK 0
 #define ICAMD_ERR_BAD_ARG 1
@@ -23,8 +24,8 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define LPTR(p) ((void __attribute__((address_space(3)))*)(p))
 
 // Streaming loads of once-read tensors (round 5).  ICAMD_STREAM_NT (per translation unit, compile time): 1 = non-temporal.  The
-// BatchNorm passes gained 1.4 % of a ResNet-50 step from it (norm_pool.hip's own switch); tools/r5_stream_nt_variants.sh builds the
-// A/B variants of the other elementwise translation units.
+// BatchNorm passes gained 1.4 % of a ResNet-50 step from it (norm_pool.hip's own switch); -DICAMD_STREAM_NT=1 builds the A/B variant
+// of any other elementwise translation unit.
 #ifndef ICAMD_STREAM_NT
 #define ICAMD_STREAM_NT 0
 #endif
@@ -197,6 +198,13 @@ static inline int icamd_num_xccs() {
     return x;
   }();
   return n;
+}
+
+// The one reader of the run-time route switches (host side): unset -> dflt, otherwise atoi.  Callers keep the value in a
+// `static const int`, so a switch is read once per process; README.md lists the switches and the tests that force them.
+static inline int icamd_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
 }
 
 static inline int icamd_launch_status() {

@@ -432,19 +432,26 @@ __global__ __launch_bounds__(256, 2) void conv1x1_resident_kernel(const PwReside
   }
 }
 
-int mode() {
-  static const int m = [] { const char* e = getenv("ICAMD_PW_RESIDENT"); return e ? atoi(e) : 1; }();
-  return m;
-}
-int pw_nt() {   // non-temporal LDS-DMA for once-read streams (round 5): 1 = the activation tile of single-channel-tile launches, 2 (default)
-                // = also the addend / BatchNorm-input / z patches of every launch (ResNet-50: 17.89 -> 17.87 ms with 1, 18.02-18.09 ->
-                // 17.96 with 2 on another box; never worse); ICAMD_PW_NT=0: default cache policy
-  static const int m = [] { const char* e = getenv("ICAMD_PW_NT"); return e ? atoi(e) : 2; }();
-  return m;
-}
-int xcd_order() {   // ICAMD_PW_XCD=0: the consecutive numbering of rounds 2-3 (A/B runs); off when the device does not report 8 XCDs
-  static const int m = [] { const char* e = getenv("ICAMD_PW_XCD"); return (e ? atoi(e) : 1) && icamd_num_xccs() == 8; }();
-  return m;
+// The split plan of the three launchers (p.ntiles_n set, tm = rows per tile): two workgroups per CU, S row splits of whole tiles;
+// cap_rows: one partial row per split at most in a [ceil(M/128)] statistics table.  Returns S.
+int plan_splits(PwResidentParams& p, int tm, bool cap_rows) {
+  const int wgs = 2 * icamd_num_cus();
+  int S = (wgs + p.ntiles_n - 1) / p.ntiles_n;
+  const int cap_tiles = (p.M + tm - 1) / tm, table_rows = (p.M + 127) / 128;
+  if (S > cap_tiles) S = cap_tiles;
+  if (cap_rows && S > table_rows) S = table_rows;
+  if (S < 1) S = 1;
+  int rows = (p.M + S - 1) / S;
+  rows = (rows + tm - 1) / tm * tm;
+  p.rows_per_split = rows;
+  // Both kernel parameters stay (no device-code change) and are fed the fixed policies.  XCD-aware workgroup order of round 4:
+  // off when the device does not report 8 XCDs.
+  p.xcd_groups = icamd_num_xccs() == 8;
+  // non-temporal LDS-DMA for once-read streams (round 5): bit 0 = the activation tile of single-channel-tile launches, bit 1 =
+  // the addend / BatchNorm-input / z patches of every launch (ResNet-50: 17.89 -> 17.87 ms with bit 0, 18.02-18.09 -> 17.96
+  // with both on another box; never worse)
+  p.nt_loads = (p.ntiles_n == 1 ? 1 : 0) | 2;
+  return (p.M + rows - 1) / rows;
 }
 
 struct Config { int ks, nf, mf, wn; };
@@ -487,12 +494,18 @@ int launch(const PwResidentParams& p, int grid, hipStream_t stream) {
 
 }  // namespace
 
+// ICAMD_PW_RESIDENT: 0 = every pointwise launch stays on conv_igemm / gemm_nt, 1 (default) = the size floors below, 2 = no size
+// floor (tests), 5 = the residual / even-grid addend data gradients stay on conv_igemm (read in capi.hip's dgrad_impl)
+int icamd_pw_resident_mode() {
+  static const int m = icamd_env_int("ICAMD_PW_RESIDENT", 1);
+  return m;
+}
+
 // The residual data gradients of ResNet-50's identity blocks: (K, N) = (planes, 4 * planes) for layer1..layer3.  Half the row
 // fragments per tile of the plain kernel (MF = 2), so that the second patch fits the 80 KB of two workgroups per CU; layer4
 // (K = 512: 64 KB of activation buffers) does not fit and keeps the two-pass BatchNorm backward.
 bool icamd_pw_resident_bnred_wanted(long long M, int N, int K) {
-  static const int on = [] { const char* e = getenv("ICAMD_BNRED"); return e ? atoi(e) : 1; }();
-  if (!on || mode() == 0 || M < 8192 || M >= (1ll << 30) || N % 256 != 0) return false;
+  if (icamd_pw_resident_mode() == 0 || M < 8192 || M >= (1ll << 30) || N % 256 != 0) return false;
   return K == 64 || K == 128 || K == 256;
 }
 
@@ -503,22 +516,11 @@ int icamd_pw_resident_bnred_launch(PwResidentParams& p, hipStream_t stream) {
     return ICAMD_ERR_UNSUPPORTED;
   constexpr int tm = 32;                         // WM = 1, MF = 2
   p.ntiles_n = p.N / 256;
-  const int wgs = 2 * icamd_num_cus();
-  int S = (wgs + p.ntiles_n - 1) / p.ntiles_n;
-  const int cap_tiles = (p.M + tm - 1) / tm, cap_rows = (p.M + 127) / 128;
-  if (S > cap_tiles) S = cap_tiles;
-  if (S > cap_rows) S = cap_rows;                // one partial row per split in the [ceil(M/128)] table
-  if (S < 1) S = 1;
-  int rows = (p.M + S - 1) / S;
-  rows = (rows + tm - 1) / tm * tm;
-  p.rows_per_split = rows;
-  S = (p.M + rows - 1) / rows;
+  const int S = plan_splits(p, tm, /*cap_rows=*/true);
   if (p.sub2_h > 0) {
     p.divHW = make_fastdiv((unsigned)(p.sub2_h * p.sub2_w));
     p.divW = make_fastdiv((unsigned)p.sub2_w);
   }
-  p.xcd_groups = xcd_order();
-  p.nt_loads = pw_nt() ? ((p.ntiles_n == 1 ? 1 : 0) | (pw_nt() >= 2 ? 2 : 0)) : 0;
   const dim3 grid((unsigned)(S * p.ntiles_n)), block(256);
   if (p.K == 64) hipLaunchKernelGGL((conv1x1_resident_kernel<2, 4, 2, 4, true, false, true>), grid, block, 0, stream, p);
   else if (p.K == 128) hipLaunchKernelGGL((conv1x1_resident_kernel<4, 4, 2, 4, true, false, true>), grid, block, 0, stream, p);
@@ -530,12 +532,11 @@ int icamd_pw_resident_bnred_launch(PwResidentParams& p, hipStream_t stream) {
 // 64-wide stages of conv_igemm / gemm_nt and ran on conv_igemm's general-channel path at 391 us per launch at batch 256
 // (M = 802 816; 0.77-1.4 GB of HBM traffic: 120-220 us).  Here it is four 32-wide k-steps over 256 B staged rows.
 bool icamd_pw_resident_ext_wanted(long long M, int N, int K) {
-  if (mode() == 0 || M < 8192 || M >= (1ll << 30)) return false;
+  if (icamd_pw_resident_mode() == 0 || M < 8192 || M >= (1ll << 30)) return false;
   if (K == 96 && N % 128 == 0) return true;
   // round 4: K = 192 (ConvNeXt-T stage 1: 192 -> 768 forward + GELU, data gradient of 768 -> 192 + GELU') as eight k-steps over
-  // 512 B staged rows, 256 channels per workgroup.  ICAMD_PW_EXT192=0: back on conv_igemm.
-  static const int k192 = [] { const char* e = getenv("ICAMD_PW_EXT192"); return e ? atoi(e) : 1; }();
-  return k192 && K == 192 && N % 256 == 0;
+  // 512 B staged rows, 256 channels per workgroup.
+  return K == 192 && N % 256 == 0;
 }
 
 int icamd_pw_resident_ext_launch(PwResidentParams& p, hipStream_t stream) {
@@ -543,24 +544,13 @@ int icamd_pw_resident_ext_launch(PwResidentParams& p, hipStream_t stream) {
   const bool k96 = p.K == 96;
   // K = 96 forward forms (bias / GELU, no z to read): 128-row tiles.  After the latency fixes of round 4 these kernels are bound by
   // their per-tile chain (barrier -> LDS transposition -> GELU -> stores), so rows per barrier are what counts; the LDS the z patch
-  // would take pays for the second half of the tile.  ICAMD_PW_EXT_TM128=0: 64-row tiles for every form.
-  static const int tm128 = [] { const char* e = getenv("ICAMD_PW_EXT_TM128"); return e ? atoi(e) : 1; }();
+  // would take pays for the second half of the tile.
   // (64-row tiles at THREE workgroups per CU -- 40 KB and 138 VGPRs each -- measured a wash in round 4 and are gone)
-  const bool big = k96 && p.gelu_z == nullptr && tm128 == 1;
+  const bool big = k96 && p.gelu_z == nullptr;
   p.lda = p.K; p.Ktrue = p.K; p.K = k96 ? 128 : 256;
   const int tm = k96 ? (big ? 128 : 64) : 32;    // <4, 2, 4|8, 4>: 64 | 128 rows x 128 channels per workgroup; <8, 4, 2, 4>: 32 x 256
   p.ntiles_n = p.N / (k96 ? 128 : 256);
-  const int wgs = 2 * icamd_num_cus();
-  int S = (wgs + p.ntiles_n - 1) / p.ntiles_n;
-  const int cap_tiles = (p.M + tm - 1) / tm;
-  if (S > cap_tiles) S = cap_tiles;
-  if (S < 1) S = 1;
-  int rows = (p.M + S - 1) / S;
-  rows = (rows + tm - 1) / tm * tm;
-  p.rows_per_split = rows;
-  S = (p.M + rows - 1) / rows;
-  p.xcd_groups = xcd_order();
-  p.nt_loads = pw_nt() ? ((p.ntiles_n == 1 ? 1 : 0) | (pw_nt() >= 2 ? 2 : 0)) : 0;
+  const int S = plan_splits(p, tm, /*cap_rows=*/false);
   const dim3 grid((unsigned)(S * p.ntiles_n)), block(256);
   if (big) hipLaunchKernelGGL((conv1x1_resident_kernel<4, 2, 8, 4, false, 2>), grid, block, 0, stream, p);
   else if (k96) hipLaunchKernelGGL((conv1x1_resident_kernel<4, 2, 4, 4, false, 1>), grid, block, 0, stream, p);
@@ -568,19 +558,14 @@ int icamd_pw_resident_ext_launch(PwResidentParams& p, hipStream_t stream) {
   return icamd_launch_status();
 }
 
-bool icamd_pw_resident_epi_wanted() {
-  static const int on = [] { const char* e = getenv("ICAMD_PW_RESIDENT_EPI"); return e ? atoi(e) : 1; }();
-  return on != 0 && mode() != 0;
-}
-
 bool icamd_pw_resident_wanted(long long M, int N, int K, bool with_addend) {
   Config c;
-  if (mode() == 0 || M <= 0 || M >= (1ll << 30) || !pick(N, K, &c)) return false;
+  if (icamd_pw_resident_mode() == 0 || M <= 0 || M >= (1ll << 30) || !pick(N, K, &c)) return false;
   if (with_addend && c.ks == 8 && c.nf == 2 && c.wn == 4) return false;
   // persistent workgroups need rows to amortise the filter load: at least ~8 tiles per workgroup at 512 workgroups
   const int tm = (4 / c.wn) * c.mf * 16;
   const int ntn = N / (c.wn * c.nf * 16);
-  if (mode() == 2) return true;
+  if (icamd_pw_resident_mode() == 2) return true;
   // K = 512 leaves room for 32 filter rows per wave only: measured on MI355X (batch 256) it wins on the 7x7 layers and on
   // 512 -> 256 at 28x28, ties at N = 128 and LOSES at N = 1024, M = 50176 (64 -> 83 us), so that one stays on conv_igemm
   if (K == 512 && !(M < 32768 || N == 256)) return false;
@@ -594,17 +579,7 @@ int icamd_pw_resident_launch(PwResidentParams& p, hipStream_t stream) {
   if (!pick(p.N, p.K, &c) || (p.stats != nullptr && p.addend != nullptr)) return ICAMD_ERR_UNSUPPORTED;
   const int tm = (4 / c.wn) * c.mf * 16;
   p.ntiles_n = p.N / (c.wn * c.nf * 16);
-  // two workgroups per CU; the statistics table has ceil(M/128) rows, one per split at most
-  const int wgs = 2 * icamd_num_cus();
-  int S = (wgs + p.ntiles_n - 1) / p.ntiles_n;
-  const int cap_tiles = (p.M + tm - 1) / tm, cap_rows = (p.M + 127) / 128;
-  if (S > cap_tiles) S = cap_tiles;
-  if (p.stats != nullptr && S > cap_rows) S = cap_rows;
-  if (S < 1) S = 1;
-  int rows = (p.M + S - 1) / S;
-  rows = (rows + tm - 1) / tm * tm;
-  p.rows_per_split = rows;
-  S = (p.M + rows - 1) / rows;
+  const int S = plan_splits(p, tm, /*cap_rows=*/p.stats != nullptr);
   if (p.sub2_h > 0) {
     p.divHW = make_fastdiv((unsigned)(p.sub2_h * p.sub2_w));
     p.divW = make_fastdiv((unsigned)p.sub2_w);
@@ -615,8 +590,6 @@ int icamd_pw_resident_launch(PwResidentParams& p, hipStream_t stream) {
     p.gdivW = make_fastdiv((unsigned)p.gat_ow);
   }
   const int grid = S * p.ntiles_n;
-  p.xcd_groups = xcd_order();
-  p.nt_loads = pw_nt() ? ((p.ntiles_n == 1 ? 1 : 0) | (pw_nt() >= 2 ? 2 : 0)) : 0;
   if (c.ks == 2 && c.wn == 4) return launch<2, 4, 4, 4>(p, grid, stream);
   if (c.ks == 2) return launch<2, 4, 1, 1>(p, grid, stream);
   if (c.ks == 4) return launch<4, 4, 4, 4>(p, grid, stream);

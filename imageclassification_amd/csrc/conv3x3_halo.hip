@@ -579,7 +579,7 @@ int launch_halo(const Halo3x3Params& p, hipStream_t stream) {
 }
 
 int halo_mode() {
-  static const int m = [] { const char* e = getenv("ICAMD_CONV3X3_HALO"); return e ? atoi(e) : 1; }();
+  static const int m = icamd_env_int("ICAMD_CONV3X3_HALO", 1);
   return m;
 }
 
@@ -587,7 +587,7 @@ int halo_mode() {
 
 // register-resident filter kernel: exactly 64 -> 64 channels, W a multiple of 8, tile + halo within 255 slots
 static bool resident_c64_ok(int W, int C, int Cout) {
-  static const int on = [] { const char* e = getenv("ICAMD_CONV3X3_RESIDENT"); return e ? atoi(e) : 1; }();
+  static const int on = icamd_env_int("ICAMD_CONV3X3_RESIDENT", 1);
   return on != 0 && C == 64 && Cout == 64 && W % 8 == 0 && 128 + 2 * W + 2 <= 255;
 }
 

@@ -432,20 +432,14 @@ __global__ __launch_bounds__(512, 2) void conv1x1_bn_bwd_fused_kernel(const Fuse
   else run(std::false_type{});
 }
 
-int fused_mode() {
-  static const int m = [] { const char* e = getenv("ICAMD_FUSED_CONV_BN_BWD"); return e ? atoi(e) : 1; }();
-  return m;
-}
-
 }  // namespace
 
 // (Cin, Cout) = (64, 256) and (128, 512): conv3 of ResNet-50's layer1 / layer2 bottlenecks (the widest tensors of the network;
-// at Cout = 1024 the g / y tiles of 32 rows no longer fit LDS beside a ring).  ICAMD_FUSED_CONV_BN_BWD=0 switches it off (A/B),
-// 2 lifts the size floor (tests).
+// at Cout = 1024 the g / y tiles of 32 rows no longer fit LDS beside a ring).
 bool icamd_conv1x1_bn_bwd_fused_wanted(long long M, int Cin, int Cout) {
-  if (fused_mode() == 0 || M <= 0 || M >= (1ll << 30)) return false;
+  if (M <= 0 || M >= (1ll << 30)) return false;
   if (!((Cin == 64 && Cout == 256) || (Cin == 128 && Cout == 512))) return false;
-  return fused_mode() == 2 || M >= 16384;
+  return M >= 16384;
 }
 
 void icamd_conv1x1_bn_bwd_fused_plan(int M, int Cin, int* S, int* rows_per_split) {
@@ -466,9 +460,9 @@ int icamd_conv1x1_bn_bwd_fused_launch(FusedBwdParams& p, hipStream_t stream) {
   icamd_conv1x1_bn_bwd_fused_plan(p.M, p.CI, &p.S, &p.rows_per_split);
   p.xcd_pairs = (p.S % 8 == 0 && icamd_num_xccs() == 8) ? 1 : 0;
   // g, y and x are read once when one workgroup owns a row range: non-temporal LDS-DMA (64 -> 256 at 56 x 56: 217 -> 180 us =
-  // 5.7 TB/s; with two input-channel slices the second one reads them from L2 and the default policy stays).  ICAMD_FUSED_NT=0: off.
-  static const int nt = [] { const char* e = getenv("ICAMD_FUSED_NT"); return e ? atoi(e) : 1; }();
-  p.nt = (nt && p.nslices == 1) ? 1 : 0;
+  // 5.7 TB/s; with two input-channel slices the second one reads them from L2 and the default policy stays).  The kernel
+  // parameter stays (no device-code change).
+  p.nt = p.nslices == 1 ? 1 : 0;
   const dim3 grid((unsigned)(p.S * p.nslices)), block(512);
   if (p.CO == 256) hipLaunchKernelGGL((conv1x1_bn_bwd_fused_kernel<256>), grid, block, 0, stream, p);
   else hipLaunchKernelGGL((conv1x1_bn_bwd_fused_kernel<512>), grid, block, 0, stream, p);

@@ -372,20 +372,14 @@ __global__ __launch_bounds__(512, 2) void bn_apply_conv1x1_fused_kernel(const Fu
   }
 }
 
-int ffwd_mode() {
-  static const int m = [] { const char* e = getenv("ICAMD_FUSED_APPLY_CONV"); return e ? atoi(e) : 1; }();
-  return m;
-}
-
 }  // namespace
 
 // (K, N) = the block boundaries of ResNet-50's layer1 / layer2: 256 -> 64, 256 -> 128, 512 -> 128 (512 -> 256, the one boundary into
 // layer3, would need 128 filter VGPRs per wave beside the transform's working set: it keeps the two launches).
-// ICAMD_FUSED_APPLY_CONV=0 switches it off (A/B), 2 lifts the size floor (tests).
 bool icamd_bn_apply_conv1x1_fused_wanted(long long M, int K, int N) {
-  if (ffwd_mode() == 0 || M <= 0 || M >= (1ll << 30)) return false;
+  if (M <= 0 || M >= (1ll << 30)) return false;
   if (!((K == 256 && (N == 64 || N == 128)) || (K == 512 && N == 128))) return false;
-  return ffwd_mode() == 2 || M >= 16384;
+  return M >= 16384;
 }
 
 int icamd_bn_apply_conv1x1_fused_launch(FusedFwdParams& p, hipStream_t stream) {
@@ -399,10 +393,9 @@ int icamd_bn_apply_conv1x1_fused_launch(FusedFwdParams& p, hipStream_t stream) {
   rows = (rows + GTM - 1) / GTM * GTM;
   p.rows_per_split = rows;
   p.S = (p.M + rows - 1) / rows;
-  // y3 and the residual are read once: non-temporal LDS-DMA by default (ResNet-50 18.08 -> 17.89 ms together with the fused
-  // backward's, two A/B pairs on one box; ICAMD_FUSED_NT=0: default policy)
-  static const int nt = [] { const char* e = getenv("ICAMD_FUSED_NT"); return e ? atoi(e) : 1; }();
-  p.nt = nt;
+  // y3 and the residual are read once: non-temporal LDS-DMA (ResNet-50 18.08 -> 17.89 ms together with the fused
+  // backward's, two A/B pairs on one box).  The kernel parameter stays (no device-code change) and is fed the constant.
+  p.nt = 1;
   const dim3 grid((unsigned)p.S), block(512);
   if (p.K == 256 && p.N == 64) hipLaunchKernelGGL((bn_apply_conv1x1_fused_kernel<256, 64>), grid, block, 0, stream, p);
   else if (p.K == 256) hipLaunchKernelGGL((bn_apply_conv1x1_fused_kernel<256, 128>), grid, block, 0, stream, p);

@@ -520,13 +520,11 @@ int icamd_igemm_launch(IgemmParams& p, hipStream_t stream) {
   const bool tail = !cin8 && (p.Cin % 64 != 0);   // single tap, channel count not a multiple of the k-step
   const bool plain = p.bias == nullptr && p.addend == nullptr && !p.relu && p.gelu_out == nullptr && !p.gelu_inplace &&
                      p.gelu_z == nullptr;
-  static const bool lean_on = [] { const char* e = getenv("ICAMD_IGEMM_LEAN"); return !(e && atoi(e) == 0); }();
   const bool addend_only = p.bias == nullptr && p.addend != nullptr && !p.addend_sub2 && !p.relu && p.gelu_out == nullptr &&
                            !p.gelu_inplace && p.gelu_z == nullptr && p.ostr == 1 && p.ooff_h == 0 && p.ooff_w == 0 &&
                            p.P == p.OH && p.Q == p.OW && p.stats == nullptr;
-  static const bool epi3_on = [] { const char* e = getenv("ICAMD_IGEMM_LEAN"); return !(e && atoi(e) == 2); }();
-  if (lean_on && epi3_on && addend_only && bn == 128 && p.Cout % 128 == 0 && !cin8 && !tail) return launch<128, 0, 3>(p, stream);
-  if (lean_on && plain && !cin8 && !tail) return bn == 64 ? launch<64, 0, 2>(p, stream) : launch<128, 0, 2>(p, stream);
+  if (addend_only && bn == 128 && p.Cout % 128 == 0 && !cin8 && !tail) return launch<128, 0, 3>(p, stream);
+  if (plain && !cin8 && !tail) return bn == 64 ? launch<64, 0, 2>(p, stream) : launch<128, 0, 2>(p, stream);
   if (bn == 64) return cin8 ? launch<64, 1, 0>(p, stream) : (tail ? launch<64, 2, 0>(p, stream) : launch<64, 0, 0>(p, stream));
   return cin8 ? launch<128, 1, 0>(p, stream) : (tail ? launch<128, 2, 0>(p, stream) : launch<128, 0, 0>(p, stream));
 }

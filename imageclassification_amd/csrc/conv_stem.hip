@@ -327,11 +327,6 @@ __global__ __launch_bounds__(512, 2) void stem7x7s2_wgrad_resident_kernel(const 
   *(f32x4*)(slab + co * 256 + 7 * 32 + kh * 16 + 4 * (lane >> 4)) = f32x4{0.f, 0.f, 0.f, 0.f};   // kernel row 7 of the layout
 }
 
-int mode() {
-  static const int m = [] { const char* e = getenv("ICAMD_STEM_RESIDENT"); return e ? atoi(e) : 1; }();
-  return m;
-}
-
 template <int MF>
 int launch(const StemParams& p, hipStream_t stream) {
   const int ntiles = p.N * (p.OH / 2);
@@ -372,7 +367,7 @@ int icamd_stem_wgrad_resident_launch(StemWgradParams& p, int S, hipStream_t stre
 
 // 64 output channels, square-ish maps whose output width is 64..128 in steps of 16 and whose output height is even
 bool icamd_stem_resident_wanted(int N, int H, int W, int Cout) {
-  if (mode() == 0 || Cout != 64 || W % 2 != 0 || H % 2 != 0) return false;
+  if (Cout != 64 || W % 2 != 0 || H % 2 != 0) return false;
   const int OW = W / 2, OH = H / 2;
   return OW % 16 == 0 && OW >= 64 && OW <= 128 && OH % 2 == 0 && (long long)N * OH * OW < (1ll << 30);
 }

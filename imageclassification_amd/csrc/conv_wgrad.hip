@@ -729,7 +729,7 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 
 // Tile choice.  ICAMD_WGRAD_RING=0 selects the single-stage 128x128 kernel of round 1 (kept for A/B runs).
 int ring_mode() {
-  static const int d = [] { const char* e = getenv("ICAMD_WGRAD_RING"); return e ? atoi(e) : 1; }();
+  static const int d = icamd_env_int("ICAMD_WGRAD_RING", 1);
   return d;
 }
 // widest tile side whose last tile is not mostly padding: 256 when the extent is a multiple of 256 or large, else 128 / 64
@@ -946,8 +946,8 @@ void icamd_wgrad_tile(long long M, int Ktot, int Cout, int* bmk, int* bnc) {
   // barrier rate: they stay on the single-stage 128 / 64 tiles.
   // (round 3) also the >= 50 GFLOP pointwise layers whose sides are multiples of 64 but not of 256 -- ConvNeXt-T's 192 <-> 768
   // and 384 <-> 1536 Linear layers -- on the 128 x 256 / 256 x 128 ring shapes: 130-140 -> 112-124 us and 100-104 -> 87-91 us.
-  static const double work_floor = [] { const char* e = getenv("ICAMD_WGRAD_WORK"); return e ? atof(e) : 2.5e10; }();   // (A/B runs)
-  const bool work = (double)M * Ktot * Cout >= work_floor;
+  constexpr double kRingWorkFloor = 2.5e10;   // M * Ktot * Cout: 2 flops each = the ~50 GFLOP above
+  const bool work = (double)M * Ktot * Cout >= kRingWorkFloor;
   const bool both256 = Ktot % 256 == 0 && Cout % 256 == 0;
   const bool wide = Ktot % 64 == 0 && Cout % 64 == 0 && (Ktot < Cout ? Ktot : Cout) >= 192 &&
                     (pick_side(Ktot) == 256 || pick_side(Cout) == 256);
@@ -978,9 +978,9 @@ void icamd_wgrad_plan(int M, int Cout, int Ktot, int* S, int* rows_per_split) {
   const int tiles = ((Ktot + bmk - 1) / bmk) * ((Cout + bnc - 1) / bnc);
   if (!use_ring(bmk, bnc)) {
     // single-stage kernel (round 1): ~64 stages (4096 pixels) per workgroup, grid within [512, 2048] workgroups
+    constexpr int kMinWorkgroups = 512, kMaxWorkgroups = 2048;
     int s = (M + 4095) / 4096;
-    static const int minwg = [] { const char* e = getenv("ICAMD_WGRAD_MINWG"); return e ? atoi(e) : 512; }();
-    const int smin = (minwg + tiles - 1) / tiles, smax = (2048 + tiles - 1) / tiles;
+    const int smin = (kMinWorkgroups + tiles - 1) / tiles, smax = (kMaxWorkgroups + tiles - 1) / tiles;
     if (s < smin) s = smin;
     if (s > smax) s = smax;
     const int cap = (M + BKR - 1) / BKR;
@@ -993,7 +993,7 @@ void icamd_wgrad_plan(int M, int Cout, int Ktot, int* S, int* rows_per_split) {
     return;
   }
   const int resident = 256 * wgs_per_cu(bmk, bnc);
-  static const int overhead_rows = []() { const char* e = getenv("ICAMD_WGRAD_OVERHEAD_ROWS"); return e ? atoi(e) : 256; }();
+  constexpr int kOverheadRows = 256;   // the fixed prologue + slab-store cost of a workgroup, in pixel rows (cost model above)
   // 256 x 256 tiles: whole 64-row reduction tiles per split, what the 8-phase kernel walks (the ring kernel takes any multiple of 32)
   const int gran = (bmk == 256 && bnc == 256) ? 64 : RKR;
   int scap = (M + gran - 1) / gran;
@@ -1007,7 +1007,7 @@ void icamd_wgrad_plan(int M, int Cout, int Ktot, int* S, int* rows_per_split) {
     rows = (rows + gran - 1) / gran * gran;
     const int s_eff = (M + rows - 1) / rows;
     const long long rounds = ((long long)tiles * s_eff + resident - 1) / resident;
-    const long long cost = rounds * (rows + overhead_rows);
+    const long long cost = rounds * (rows + kOverheadRows);
     if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_s = s; }
   }
   int rows = (M + best_s - 1) / best_s;
@@ -1017,7 +1017,7 @@ void icamd_wgrad_plan(int M, int Cout, int Ktot, int* S, int* rows_per_split) {
 }
 
 static int halo_wgrad_mode() {
-  static const int m = [] { const char* e = getenv("ICAMD_WGRAD_HALO"); return e ? atoi(e) : 1; }();
+  static const int m = icamd_env_int("ICAMD_WGRAD_HALO", 1);
   return m;
 }
 
@@ -1064,16 +1064,15 @@ int icamd_wgrad_launch(WgradParams& p, hipStream_t stream) {
   p.divCin = make_fastdiv((unsigned)p.Cin);
   p.divKW = make_fastdiv((unsigned)p.KW);
   p.pointwise = (!p.stem7 && p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0) ? 1 : 0;
-  // ICAMD_WGRAD_XCD=0: the order of rounds 1-4 (A/B); both orders are bijections on any device
-  static const int xcd_chunk = [] { const char* e = getenv("ICAMD_WGRAD_XCD"); return (e ? atoi(e) : 1) && icamd_num_xccs() == 8; }();
-  p.xcd_chunk = xcd_chunk;
+  // XCD-chunked workgroup order (a bijection on any device) when the device reports 8 XCDs; the kernel parameter stays (no
+  // device-code change) and is fed that
+  p.xcd_chunk = icamd_num_xccs() == 8;
   if (!use_ring(bmk, bnc)) {
     if (bmk == 64) return bnc == 64 ? launch<64, 64>(p, stream) : launch<64, 128>(p, stream);
     return bnc == 64 ? launch<128, 64>(p, stream) : launch<128, 128>(p, stream);
   }
-  // 256 x 256 tiles of pointwise layers with whole tiles everywhere: the 8-phase kernel (ICAMD_WGRAD_8PHASE=0: the ring kernel, A/B)
-  static const int eight = [] { const char* e = getenv("ICAMD_WGRAD_8PHASE"); return e ? atoi(e) : 1; }();
-  if (eight && bmk == 256 && bnc == 256 && p.pointwise && p.Ktot % 256 == 0 && p.Cout % 256 == 0 && p.M % 64 == 0 &&
+  // 256 x 256 tiles of pointwise layers with whole tiles everywhere: the 8-phase kernel (any other 256 x 256 problem: the ring kernel)
+  if (bmk == 256 && bnc == 256 && p.pointwise && p.Ktot % 256 == 0 && p.Cout % 256 == 0 && p.M % 64 == 0 &&
       p.rows_per_split % 64 == 0 && (long long)p.M * p.Cin < (1ll << 30) && (long long)p.M * p.Cout < (1ll << 30)) {
     hipLaunchKernelGGL(conv_wgrad_8phase_kernel, dim3((unsigned)(p.ntiles_k * p.ntiles_c * p.S)), dim3(512), 0, stream, p);
     return icamd_launch_status();

@@ -508,7 +508,7 @@ __global__ __launch_bounds__(256) void layerscale_bwd_kernel(const bf16_t* __res
 }  // namespace
 
 static int dw_rows_mode() {   // ICAMD_DWCONV_ROWS=0: the LDS tile kernels of round 1/2 (tests compare both)
-  static const int m = [] { const char* e = getenv("ICAMD_DWCONV_ROWS"); return e ? atoi(e) : 1; }();
+  static const int m = icamd_env_int("ICAMD_DWCONV_ROWS", 1);
   return m;
 }
 // The register sliding-window kernels address x / dy with 32-bit byte offsets: tensors of 4 GB and more take the LDS tile
@@ -532,8 +532,6 @@ int icamd_dwconv7_launch(const bf16_t* x, const bf16_t* w, const float* bias, co
     const long long per_part = (long long)(C / 2) * nstrips * N;
     int hsplit = H >= 28 ? 2 : 1;
     while (per_part * hsplit < 1536ll * 64 / 2 && H / (hsplit * 2) >= 7) hsplit *= 2;
-    static const int force = [] { const char* e = getenv("ICAMD_DW_HSPLIT"); return e ? atoi(e) : 0; }();
-    if (force > 0) hsplit = force;
     const long long blocks = (per_part + 255) / 256;
     if (blocks <= 0 || blocks >= (1ll << 31)) return ICAMD_ERR_BAD_ARG;
     const unsigned int last_off = (unsigned int)((long long)N * H * W * C * 2 - 4);

@@ -551,14 +551,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_8phase_kernel(const GemmNtPara
 // ICAMD_GEMM_TN: 128 / 256 force the ring kernel at that tile width; 8 (default) = the 8-phase 256 x 256 kernel wherever K is a
 // multiple of 64 (else the 128-wide ring)
 int tile_n_width() {
-  static const int tn = [] { const char* e = getenv("ICAMD_GEMM_TN"); const int v = e ? atoi(e) : 8; return v == 256 || v == 128 ? v : 8; }();
+  static const int tn = [] { const int v = icamd_env_int("ICAMD_GEMM_TN", 8); return v == 256 || v == 128 ? v : 8; }();
   return tn;
 }
 
 }  // namespace
 
 bool icamd_gemm_nt_wanted(long long M, int N, int K) {
-  static const int mode = [] { const char* e = getenv("ICAMD_GEMM_NT"); return e ? atoi(e) : 1; }();
+  static const int mode = icamd_env_int("ICAMD_GEMM_NT", 1);
   if (mode == 0 || K % TK != 0 || N % 8 != 0 || M >= (1ll << 31)) return false;
   if (mode == 2) return true;   // forced (tests)
   // MFMA-bound problems only: enough K to amortise the big-tile prologue / epilogue and enough tiles to fill 256 CUs.
@@ -570,10 +570,9 @@ bool icamd_gemm_nt_wanted(long long M, int N, int K) {
   const long long pairs = ((M + TM - 1) / TM) * ((N + 255) / 256);
   // (round 3, K = 1024 / N = 256 at 14x14 -- ResNet-50 layer3's 1024 -> 256 forward and 256 -> 1024 data gradient: 196 tiles,
   // one per CU, sixteen K tiles each: 38.7 -> 30.6 us and 37.5 -> 29.5 us against the resident-filter kernel)
-  static const bool k1024 = [] { const char* e = getenv("ICAMD_GEMM_K1024"); return !(e && atoi(e) == 0); }();
-  if (k1024 && K == 1024 && N == 256 && pairs >= 160 && pairs <= 256) return true;
-  static const int mink = [] { const char* e = getenv("ICAMD_GEMM_MINK"); return e ? atoi(e) : 768; }();   // (A/B: 384 = ConvNeXt-T stage 2's fc1)
-  return K >= mink && N >= 256 && (pairs >= 256 || (K >= 2048 && pairs >= 96));
+  if (K == 1024 && N == 256 && pairs >= 160 && pairs <= 256) return true;
+  constexpr int kMinK = 768;   // ViT's K, see above (384, ConvNeXt-T stage 2's fc1, measured no gain)
+  return K >= kMinK && N >= 256 && (pairs >= 256 || (K >= 2048 && pairs >= 96));
 }
 
 int icamd_gemm_nt_launch(GemmNtParams& p, hipStream_t stream) {
@@ -588,14 +587,14 @@ int icamd_gemm_nt_launch(GemmNtParams& p, hipStream_t stream) {
     p.divW = make_fastdiv((unsigned)p.sub2_w);
   }
   const long long tiles = (long long)((p.M + TM - 1) / TM) * p.ntiles_n;
-  // output stores non-temporal by default (round 5): the output tile is never re-read by this kernel, and as plain stores the 32
+  // output stores non-temporal (round 5): the output tile is never re-read by this kernel, and as plain stores the 32
   // resident workgroups' 128 KB tiles competed with the operand lines their XCD shares (ViT-B/16 36.84 -> 36.30-36.33 ms in two A/B
-  // pairs on one box, ConvNeXt-T neutral; isolated N = 2304 / K = 768: 850 -> 887 TFLOP/s).  ICAMD_GEMM_OUT_POLICY=0: plain, 1: sc1.
-  static const int out_policy = [] { const char* e = getenv("ICAMD_GEMM_OUT_POLICY"); return e ? atoi(e) : 2; }();
-  p.out_policy = out_policy;
+  // pairs on one box, ConvNeXt-T neutral; isolated N = 2304 / K = 768: 850 -> 887 TFLOP/s).
+  // out_policy and group_n stay kernel parameters (no device-code change) and are fed these constants.
+  constexpr int kOutPolicyNonTemporal = 2, kGroupN = 4;   // kGroupN: n-tiles per group of the 8-phase kernel's tile order
+  p.out_policy = kOutPolicyNonTemporal;
   if (eight) {
-    static const int gn = [] { const char* e = getenv("ICAMD_GEMM_GROUP_N"); return e ? atoi(e) : 4; }();
-    p.group_n = gn > 0 && gn < p.ntiles_n ? gn : p.ntiles_n;
+    p.group_n = kGroupN < p.ntiles_n ? kGroupN : p.ntiles_n;
     hipLaunchKernelGGL(gemm_nt_8phase_kernel, dim3((unsigned)tiles), dim3(512), 0, stream, p);
   }
   else if (tn == 256) hipLaunchKernelGGL(gemm_nt_kernel<256>, dim3((unsigned)tiles), dim3(512), 0, stream, p);

@@ -172,7 +172,7 @@ struct PwResidentParams {
   FastDiv gdivHW, gdivW;          // filled by the launcher when gat_ow > 0
 };
 bool icamd_pw_resident_wanted(long long M, int N, int K, bool with_addend = false);
-bool icamd_pw_resident_epi_wanted();   // ICAMD_PW_RESIDENT_EPI=0: evaluate()'s pointwise layers stay on conv_igemm (A/B, tests)
+int icamd_pw_resident_mode();   // ICAMD_PW_RESIDENT, read once: 0 = off, 1 = size floors, 2 = no floor, 5 = addend data gradients off
 // the ext form: plain pointwise problems with K = 96 (bias / GELU epilogues allowed, no addend / statistics)
 bool icamd_pw_resident_ext_wanted(long long M, int N, int K);
 int icamd_pw_resident_launch(PwResidentParams& p, hipStream_t stream);

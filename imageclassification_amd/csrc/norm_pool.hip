@@ -11,7 +11,7 @@
 #include <string.h>
 
 // Cache policy of the streaming 16 B loads / stores of the BatchNorm passes: bit 0 = non-temporal loads, bit 1 = non-temporal stores
-// (compile-time: the product value is set below; tools/r5_bn_nt_variants.sh builds the others for A/B runs).
+// (compile-time: the product value is set below; -DICAMD_BN_NT=0..3 builds the others for A/B runs).
 #ifndef ICAMD_BN_NT
 #define ICAMD_BN_NT 1   // round 5: non-temporal LOADS (ResNet-50 17.94-17.99 -> 17.68-17.76 ms, two A/B pairs on one box); non-temporal stores lost (18.0-18.1)
 #endif
@@ -1020,21 +1020,18 @@ __global__ __launch_bounds__(256) void pack_input_rgb4_kernel(const float* __res
   }
 }
 
+constexpr long long kMaxElementwiseBlocks = 1024;   // grid cap of the grid-stride elementwise kernels
 inline unsigned int grid_for(long long work_items, int threads, int multiple_of) {
-  static const long long cap = []() { const char* e = getenv("ICAMD_EW_BLOCKS"); return e ? atoll(e) : 1024ll; }();
   long long blocks = (work_items + threads - 1) / threads;
-  if (blocks > cap) blocks = cap;
+  if (blocks > kMaxElementwiseBlocks) blocks = kMaxElementwiseBlocks;
   if (blocks < 1) blocks = 1;
   if (multiple_of > 1) blocks = (blocks + multiple_of - 1) / multiple_of * multiple_of;
   return (unsigned int)blocks;
 }
-// ICAMD_BN_REVERSE=1: back-to-front traversal of the second BatchNorm-backward pass.  Measured on MI355X (ResNet-50 bs 256,
-// round 2): 5.50-5.53 ms/step of BatchNorm backward either way -- the pass is not helped by Infinity-Cache hits -- so it
-// stays off.
-inline int bn_reverse() {
-  static const int v = []() { const char* e = getenv("ICAMD_BN_REVERSE"); return e ? atoi(e) : 0; }();
-  return v;
-}
+// Back-to-front traversal of the second BatchNorm-backward pass: measured on MI355X (ResNet-50 bs 256, round 2) 5.50-5.53 ms/step
+// of BatchNorm backward either way -- the pass is not helped by Infinity-Cache hits -- so it is off.  The `reverse` parameter of
+// bn_bwd_apply_kernel / bn_bwd_dual_apply_kernel stays (no device-code change) and is fed this constant.
+constexpr int kBnBwdReverse = 0;
 inline int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
 
 }  // namespace
@@ -1130,9 +1127,8 @@ static PoolGather pool_gather_for(const unsigned char* idx, int IH, int IW, int 
 }
 
 int icamd_bn_bwd_rows_per_block(long long rows, int C) {
-  // aim for ~N blocks (default 2048), at least 32 rows each
-  static const long long nb = []() { const char* e = getenv("ICAMD_BNBWD_BLOCKS"); return e ? atoll(e) : 1024ll; }();
-  long long rpb = (rows + nb - 1) / nb;
+  constexpr long long kBnBwdBlocks = 1024;   // aim for about this many blocks, at least 32 rows each
+  long long rpb = (rows + kBnBwdBlocks - 1) / kBnBwdBlocks;
   if (rpb < 32) rpb = 32;
   (void)C;
   return (int)rpb;
@@ -1179,7 +1175,7 @@ int icamd_bn_bwd_launch(const bf16_t* dout, const bf16_t* act, const bf16_t* y, 
                        shift, c1, c2, dy, (unsigned)rows, C, (unsigned)rpb, pg);
   else
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(elementwise_grid(nvec, C / 8)), dim3(256), 0, s, dout, act, y, mean, invstd,
-                       scale, shift, c1, c2, dy, gout, maskbits, nvec, C / 8, relu, bn_reverse());
+                       scale, shift, c1, c2, dy, gout, maskbits, nvec, C / 8, relu, kBnBwdReverse);
   return icamd_launch_status();
 }
 
@@ -1208,7 +1204,7 @@ int icamd_bn_bwd_dual_launch(const bf16_t* dout, const unsigned char* maskbits, 
   }
   const long long nvec = rows * (C / 8);
   hipLaunchKernelGGL(bn_bwd_dual_apply_kernel, dim3(elementwise_grid(nvec, C / 8)), dim3(256), 0, s, dout, maskbits, yA, meanA,
-                     invstdA, scaleA, cA, dyA, yB, meanB, invstdB, scaleB, cB, dyB, nvec, C / 8, C, bn_reverse());
+                     invstdA, scaleA, cA, dyA, yB, meanB, invstdB, scaleB, cB, dyB, nvec, C / 8, C, kBnBwdReverse);
   return icamd_launch_status();
 }
 

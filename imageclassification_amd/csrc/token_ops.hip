@@ -358,7 +358,7 @@ static inline int ln_lanes_per_row(int C) { return C <= 128 ? 16 : (C <= 256 ? 3
 // ConvNeXt-T (C = 96 ... 384, one vector per lane today) 26.8-27.0 either way -- so only the 768-wide rows take it by default.
 // ICAMD_LN_NV3: bit 0 forward, bit 1 backward (default 3), bit 2 every eligible width.
 static inline int ln_nv3_lanes(int C, int mode_bit) {
-  static const int mode = [] { const char* e = getenv("ICAMD_LN_NV3"); return e ? atoi(e) : 3; }();
+  static const int mode = icamd_env_int("ICAMD_LN_NV3", 3);
   const int nvec = C >> 3;
   if (!(mode & mode_bit) || nvec % 3 != 0) return 0;
   const int l = nvec / 3;
