@@ -217,9 +217,12 @@ __global__ __launch_bounds__(PTHREADS, 4) void attn_fwd_kernel(const bf16_t* __r
 
 // ----------------------------------------------------------------------------------------------------------------
 // backward, part 1: dQ (query on the lane) and delta = rowsum(dO * O).  Persistent form (see above): K and V of the next
-// head are staged by the producer waves.  No masks in the loop: a query row past T gets lse = +inf (p = 2^-inf = 0), a key
-// past T is a zero row of K, so whatever its dS is it adds nothing to dQ = K^T dS.  The softmax scale is applied once to
-// the dQ accumulators (dS = p (dP - delta) here, without the factor).
+// head are staged by the producer waves.  No masks in the loop: a query row past T gets lse = +inf (p = 2^-inf = 0); a key
+// past T is a zero row of K and V, so its s and dP are 0, its p = e^-lse and its dS = -p delta, which adds nothing to
+// dQ = K^T dS PROVIDED dS IS FINITE (0 * inf is NaN, and the MFMA would spread it over the query's whole dQ row).  clamp01() holds
+// p to [0, 1] -- free, the clamp bit of v_exp_f32 --, so that holds for any lse: without it a query whose lse is below -88.7 got
+// p = +inf there (found by tests/test_attention_ranges_gpu.py; T = 64 has no such rows in <4>, every T does in <13>).  The
+// softmax scale is applied once to the dQ accumulators (dS = p (dP - delta) here, without the factor).
 // ----------------------------------------------------------------------------------------------------------------
 template <int NKB>
 __global__ __launch_bounds__(PTHREADS, 4) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
@@ -304,7 +307,7 @@ __global__ __launch_bounds__(PTHREADS, 4) void attn_bwd_dq_kernel(const bf16_t* 
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lq2));
+            const float p = clamp01(__builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lq2)));
             ds2[u][r] = p * (dp[r] - dl);
           }
         }

@@ -71,6 +71,10 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
   asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
+// A probability recomputed from a stored log-sum-exp, p = 2^(s c1 - lse log2 e), held to [0, 1]: it is <= 1 for every key the lse was
+// taken over (an fp32 rounding above 1 becomes 1), so this changes nothing there, and for a zero-filled key row past T (s = 0, p = e^-lse) of a query whose lse is below
+// -88.7 it is 1 instead of +inf.  med3(p, 0, 1) folds into the clamp bit of v_exp_f32: no instruction, no register.
+__device__ __forceinline__ float clamp01(float p) { return __builtin_amdgcn_fmed3f(p, 0.f, 1.f); }
 __device__ __forceinline__ float group_max(float v) {   // across the 4 lane groups that share a column
   v = fmaxf(v, __shfl_xor(v, 16, 64));
   return fmaxf(v, __shfl_xor(v, 32, 64));

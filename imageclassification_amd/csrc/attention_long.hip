@@ -26,7 +26,8 @@
 //
 // Rows past T: tile rows >= T are filled from the zero page.  Forward: only the LAST key tile can hold them, and only there the
 // scores are masked to -inf.  Backward: a key past T is a zero row of K and V (its dS meets a zero row of K^T; its own dK / dV are
-// never stored), a query past T gets lse = +inf, i.e. p = 0.  Nothing is stored for a row >= T.
+// never stored), a query past T gets lse = +inf, i.e. p = 0.  The dQ kernel holds p to [0, 1] (clamp01()), so that such a key's
+// dS = -e^-lse delta is finite whatever lse is: 0 * inf would be NaN in the whole dQ row.  Nothing is stored for a row >= T.
 //
 // Grid: one workgroup per (pair, block of 128 rows).  With 8 XCDs dispatched round-robin, workgroup w runs on XCD w % 8; the
 // order below gives all blocks of a pair to ONE XCD, consecutively, so the pair's K / V (or Q / dO) tiles are fetched into one L2
@@ -354,7 +355,7 @@ __global__ __launch_bounds__(LTHREADS, 3) void attn_long_bwd_dq_kernel(const bf1
           }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lq2[u]));
+            const float p = clamp01(__builtin_amdgcn_exp2f(__builtin_fmaf(s[r], c1, -lq2[u])));
             ds2[kk][r] = p * (dp[r] - dl[u]);
           }
         }

@@ -474,6 +474,42 @@ def attention_bwd(qkv, dout, B, T, H, D, scale, acc=torch.float32):
     return bf16_round(x.grad)
 
 
+def _bf16_grid(t):
+    """fp64 values rounded to the bf16 grid and kept in fp64 (fp64 -> fp32 -> bf16 double-rounds only on an fp32 tie: 2^-30 of values)."""
+    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
+
+
+def attention_written_out(qkv, dout, B, T, H, D, scale, rounding_points=False):
+    """Forward and backward of softmax attention written out product by product in fp64 (no autograd).
+
+    rounding_points=False: exact arithmetic; out and dqkv equal attention_fwd / attention_bwd with acc=torch.float64.
+    rounding_points=True: the operands the HIP kernels round to bf16 on their way into an MFMA are rounded here too, everything
+    else stays fp64 -- the unnormalised exp(s - max) in front of P V (the row sum is taken unrounded), p in front of dV = P^T dO,
+    dS = p (dP - delta) in front of dQ = dS K and dK = dS^T Q, and delta = rowsum(dO * out) of the ROUNDED out the forward stored.
+    The distance between the two is what those roundings alone cost, whatever the kernels do.
+
+    Returns a dict: out [B*T, H*D] and dqkv [B*T, 3*H*D] on the bf16 grid (fp32), the same two before that last rounding (out64,
+    dqkv64), lse, delta [B, H, T] and ds [B, H, T, T] (the unrounded dS, without the softmax scale) in fp64."""
+    rnd = _bf16_grid if rounding_points else (lambda t: t)
+    q, k, v = qkv.to(torch.float64).reshape(B, T, 3, H, D).permute(2, 0, 3, 1, 4)
+    do = dout.to(torch.float64).reshape(B, T, H, D).permute(0, 2, 1, 3)
+    s = (q @ k.transpose(-1, -2)) * scale
+    m = s.amax(-1, keepdim=True)
+    e = torch.exp(s - m)
+    l = e.sum(-1, keepdim=True)
+    lse = (m + torch.log(l)).squeeze(-1)
+    o = (rnd(e) @ v) / l
+    p = torch.exp(s - lse[..., None])
+    delta = (do * rnd(o)).sum(-1)
+    ds = p * (do @ v.transpose(-1, -2) - delta[..., None])
+    dv = rnd(p).transpose(-1, -2) @ do
+    dq = (rnd(ds) @ k) * scale
+    dk = (rnd(ds).transpose(-1, -2) @ q) * scale
+    dqkv = torch.stack([dq, dk, dv], 0).permute(1, 3, 0, 2, 4).reshape(B * T, 3 * H * D)
+    o = o.permute(0, 2, 1, 3).reshape(B * T, H * D)
+    return {"out": bf16_round(o), "out64": o, "lse": lse, "delta": delta, "ds": ds, "dqkv": bf16_round(dqkv), "dqkv64": dqkv}
+
+
 # ---- ConvNeXt pieces ------------------------------------------------------------------------------------------------
 def dwconv7_fwd(x_nhwc, w_c77, bias, acc=torch.float32):
     """x [N,H,W,C], w [C,7,7] (torch depthwise layout), bias [C]. Returns y NHWC on the bf16 grid."""
