@@ -12,6 +12,12 @@ waits before a buffer is overwritten) are blocks.py's.  The block itself is writ
 
 NHWC activations make every "channels-first LayerNorm" an ordinary row LayerNorm over pixels, and every Linear a 1x1
 convolution on the same tensor (bias fused); the depthwise stencil and the layer-scale tail are dedicated kernels.
+
+ConvNeXt V2 (the `convnextv2_*` names, GRN_ARCHS) is the same class: its block has no layer scale and carries timm's
+GlobalResponseNorm between GELU and fc2 (`mlp.grn.weight` / `mlp.grn.bias`, shape (4 dim,), initialised to zero; restated from
+memory like the V1 block, not pinned to a timm release): dw -> LN -> fc1 + GELU (z1, a) -> GRN (g) -> fc2 -> drop path -> residual.
+GRN is csrc/grn.hip (icamd_grn_fwd / icamd_grn_bwd; the backward also applies gelu'(z1), as fc2's data gradient does for V1).  Every
+V2 step is taken only where `self.grn` is set; the V1 names keep their layouts, call sequences and both tail routes.
 """
 import ctypes
 import os
@@ -36,7 +42,16 @@ CONFIGS = {
     # the backbone of tests/golden/convnext_ref_vectors.npz (vectors from the reference's own ConvNeXt class,
     # /root/reference/semantic_segmentation/backbone/convnext.py:58-150)
     "convnext_pin": ((1, 1, 1, 1), (32, 64, 96, 192)),
+    # ConvNeXt V2 (timm convnextv2_*; atto / femto / nano have dims that are no multiple of 32, which icamd_dwconv7_* requires)
+    "convnextv2_pico": ((2, 2, 6, 2), (64, 128, 256, 512)),
+    "convnextv2_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
+    "convnextv2_base": ((3, 3, 27, 3), (128, 256, 512, 1024)),
+    "convnextv2_large": ((3, 3, 27, 3), (192, 384, 768, 1536)),
+    "convnextv2_test": ((1, 1, 2, 1), (32, 64, 128, 192)),   # parity tests only
 }
+# the names whose block is the V2 one: global response norm in the Mlp, no layer scale
+GRN_ARCHS = frozenset({"convnextv2_pico", "convnextv2_tiny", "convnextv2_base", "convnextv2_large", "convnextv2_test"})
+GRN_EPS = 1e-6
 
 
 class _Conv:
@@ -60,6 +75,7 @@ class ConvNeXt(ArenaModel):
     def __init__(self, arch="convnext_tiny", num_classes=1000, device="cuda", drop_path_rate=0.0, seed=None):
         super().__init__(arch, num_classes, device)
         self.depths, self.dims = CONFIGS[arch]
+        self.grn = arch in GRN_ARCHS
         self.drop_path_rate = drop_path_rate
         self.injected_keep = None     # tests: list of per-block keep tensors (float [B]) to use instead of drawing
         self._build()
@@ -105,8 +121,12 @@ class ConvNeXt(ArenaModel):
                 blk["nw"] = add(f"{n}.norm.weight", (dim,), "vec", (dim,))
                 blk["nb"] = add(f"{n}.norm.bias", (dim,), "vec", (dim,))
                 blk["fc1"] = conv(f"{n}.mlp.fc1", dim, 4 * dim, 1, 1, lin=True)
+                if self.grn:
+                    blk["grn_w"] = add(f"{n}.mlp.grn.weight", (4 * dim,), "vec", (4 * dim,))
+                    blk["grn_b"] = add(f"{n}.mlp.grn.bias", (4 * dim,), "vec", (4 * dim,))
                 blk["fc2"] = conv(f"{n}.mlp.fc2", 4 * dim, dim, 1, 1, lin=True)
-                blk["gamma"] = add(f"{n}.gamma", (dim,), "vec", (dim,))
+                if not self.grn:
+                    blk["gamma"] = add(f"{n}.gamma", (dim,), "vec", (dim,))
                 st["blocks"].append(blk)
                 bi += 1
             self.stages.append(st)
@@ -117,7 +137,9 @@ class ConvNeXt(ArenaModel):
         self._allocate(layout, [(c, c.cout_p, c.k * c.k, c.cin_p) for c in self.gemms])
         # folded layer scale: one folded fc2 bias per block; the folded filter takes fc2's place in the bf16 shadow (and, through
         # refresh_transposed, in the transposed shadow), so _w(fc2) / _wt(fc2) are the folded operands
-        self.fused_ls = _FUSED_LS
+        self.fused_ls = _FUSED_LS and not self.grn     # V2 has no layer scale to fold
+        if self.grn:     # the drop-path tail runs icamd_layerscale_fwd / _bwd with this constant in gamma's place
+            self.ones = torch.ones(max(self.dims), dtype=torch.float32, device=dev)
         fb = 0
         for st in self.stages:
             for blk in st["blocks"]:
@@ -131,7 +153,8 @@ class ConvNeXt(ArenaModel):
         return {"arch": self.arch, "num_classes": self.num_classes, "drop_path_rate": self.drop_path_rate}
 
     def init_weights(self, seed=None):
-        """timm ConvNeXt init: trunc_normal(std .02) conv / linear weights, zero biases, LayerNorm 1 / 0, gamma 1e-6."""
+        """timm ConvNeXt init: trunc_normal(std .02) conv / linear weights, zero biases, LayerNorm 1 / 0, gamma 1e-6; V2: both
+        GRN vectors zero."""
         g = torch.Generator()
         g.manual_seed(seed if seed is not None else torch.initial_seed() % (2 ** 63))
         sd = OrderedDict()
@@ -140,6 +163,8 @@ class ConvNeXt(ArenaModel):
                 sd[name] = torch.nn.init.trunc_normal_(torch.empty(p.torch_shape), std=0.02, generator=g)
             elif name.endswith(".gamma"):
                 sd[name] = torch.full(p.torch_shape, 1e-6)
+            elif ".mlp.grn." in name:
+                sd[name] = torch.zeros(p.torch_shape)
             elif name.endswith("weight"):
                 sd[name] = torch.ones(p.torch_shape)
             else:
@@ -205,7 +230,7 @@ class ConvNeXt(ArenaModel):
         ws["st_stem"] = f32(2 * N * h * w)
         max_act, max_rows = N * h * w * 4 * d0, N * h * w
         wg = lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(self.stem.desc(N, H, W)))
-        dwg = 0
+        dwg = grn = 0
         stages = []
         for si, st in enumerate(self.stages):
             dim = st["dim"]
@@ -222,6 +247,9 @@ class ConvNeXt(ArenaModel):
                 sw["blocks"].append({"d": act(N, h, w, dim), "h": act(N, h, w, dim), "z1": act(N, h, w, 4 * dim),
                                      "a": act(N, h, w, 4 * dim), "z2": None if self.fused_ls else act(N, h, w, dim), "out": act(N, h, w, dim),
                                      "st": f32(2 * rows), "keep": None})
+                if self.grn:     # g = GRN(a) is fc2's input (kept for its weight gradient); gx: the statistic the backward reads
+                    sw["blocks"][-1].update(g=act(N, h, w, 4 * dim), gx=f32(N * 4 * dim))
+                    grn = max(grn, lib.icamd_grn_workspace_bytes(N, h * w, 4 * dim))
                 wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(blk["fc1"].desc(N, h, w))),
                          lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(blk["fc2"].desc(N, h, w))))
                 dwg = max(dwg, lib.icamd_dwconv7_wgrad_workspace_bytes(N, h, w, dim))
@@ -246,6 +274,13 @@ class ConvNeXt(ArenaModel):
                              lib.icamd_layerscale_bwd_workspace_bytes(max_rows, max(self.dims)))
         ws["cs_ws"] = torch.zeros(ws["cs_bytes"], dtype=torch.uint8, device=dev)
         ws["max_act"] = max_act
+        if self.grn:
+            ws["grn_bytes"] = grn
+            ws["grn_ws"] = torch.empty(max(grn, 256), dtype=torch.uint8, device=dev)
+            ws["ls_dg"] = f32(max(self.dims))     # the gradient of the constant `ones`: discarded
+            # a dropped block's masked output gradient; a buffer of its own, so that fc2's weight gradient (side lane) can read it
+            # while the main stream goes on through G[1]
+            ws["d2"] = act(max_act // 4)
         if self.fused_ls:     # side-lane scratch of the folded layer's parameter gradients
             dmax = max(self.dims)
             ws["ls_G"] = f32(4 * dmax * dmax)
@@ -256,7 +291,8 @@ class ConvNeXt(ArenaModel):
 
     def _scratch(self, ws):
         if "g" not in ws:
-            ws["g"] = [torch.empty(ws["max_act"], dtype=torch.bfloat16, device=self.device) for _ in range(5)]
+            # V2: a sixth buffer for d g, so that d z1 and the buffers after it stay where the side lane expects them
+            ws["g"] = [torch.empty(ws["max_act"], dtype=torch.bfloat16, device=self.device) for _ in range(6 if self.grn else 5)]
         return ws["g"]
 
     def pack(self, x_nchw, mix=None):
@@ -305,7 +341,18 @@ class ConvNeXt(ArenaModel):
                     else:
                         keep = drop_rows[bi]
                 b["keep"] = keep
-                if self.fused_ls:
+                if self.grn:
+                    c2 = blk["fc2"]
+                    hip.check(lib.icamd_grn_fwd(b["a"].data_ptr(), self._pf(blk["grn_w"]), self._pf(blk["grn_b"]), b["g"].data_ptr(),
+                                                b["gx"].data_ptr(), N, h * w, 4 * dim, GRN_EPS, ws["grn_ws"].data_ptr(),
+                                                ws["grn_bytes"], s), blk["name"] + " grn")
+                    if keep is None:     # out = x + fc2(g) in fc2's store pass
+                        f.linear(c2, c2.desc(N, h, w), b["g"].data_ptr(), b["out"].data_ptr(), x.data_ptr())
+                    else:                # out = x + keep * fc2(g)
+                        f.linear(c2, c2.desc(N, h, w), b["g"].data_ptr(), b["z2"].data_ptr())
+                        hip.check(lib.icamd_layerscale_fwd(b["z2"].data_ptr(), x.data_ptr(), self.ones.data_ptr(), keep.data_ptr(),
+                                                           b["out"].data_ptr(), rows, dim, h * w, s), "drop path")
+                elif self.fused_ls:
                     # out = x + a W2'^T + b2' in fc2's store pass; the dropped samples: out = x, and their rows of `a` are cleared
                     # so that they vanish from fc2's weight gradient (which then runs on the unmasked output gradient)
                     c2 = blk["fc2"]
@@ -362,7 +409,18 @@ class ConvNeXt(ArenaModel):
             rows = N * h * w
             for blk, b in zip(reversed(st["blocks"]), reversed(sw["blocks"])):
                 keep = None if b["keep"] is None else b["keep"].data_ptr()
-                if self.fused_ls:
+                if self.grn:
+                    d2 = dout     # gradient of fc2's output: the block's output gradient, masked where the branch was dropped
+                    if keep is not None:
+                        d2 = ws["d2"].data_ptr()
+                        hip.check(lib.icamd_layerscale_bwd(dout, dout, self.ones.data_ptr(), keep, W(d2), ws["ls_dg"].data_ptr(),
+                                                           rows, dim, h * w, 0, csp, csb, s), "drop path bwd")
+                    bw.gemm(blk["fc2"], blk["fc2"].desc(N, h, w), b["g"].data_ptr(), d2, G[5])                        # G5 = d g
+                    hip.check(lib.icamd_grn_bwd(G[5], b["a"].data_ptr(), b["gx"].data_ptr(), self._pf(blk["grn_w"]),
+                                                b["z1"].data_ptr(), W(G[4]), self._gf(blk["grn_w"]), self._gf(blk["grn_b"]), acc, N,
+                                                h * w, 4 * dim, GRN_EPS, ws["grn_ws"].data_ptr(), ws["grn_bytes"], s),
+                              blk["name"] + " grn bwd + gelu bwd")                                                  # G4 = d z1
+                elif self.fused_ls:
                     # fc2 with the layer scale folded in: its data gradient reads the block's output gradient itself (the folded,
                     # transposed filter carries cb * gamma); the side lane forms G = dout^T a and the column sums of dout over the
                     # kept samples, and from them the gradients of W2, b2 and gamma (icamd_layerscale_param_grads)

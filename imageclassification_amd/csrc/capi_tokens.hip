@@ -1,5 +1,5 @@
 // C-ABI entry points of the token models (ViT, Swin, ConvNeXt): LayerNorm, GELU, token assembly and reductions, depthwise 7x7,
-// layer scale, attention, window attention, relative-position bias and patch merging.
+// layer scale, global response normalisation, attention, window attention, relative-position bias and patch merging.
 #include "capi_common.h"
 
 extern "C" {
@@ -231,6 +231,37 @@ int icamd_layerscale_param_grads(const float* G, const float* w, const float* bi
     return ICAMD_ERR_BAD_ARG;
   return icamd_layerscale_param_grads_launch(G, w, bias, gamma, colsum_all, dropped, n_images, cb, C, K, dw, dbias, dgamma,
                                              accumulate, (hipStream_t)stream);
+}
+
+// ---- ConvNeXt V2: global response normalisation (grn.hip) ----------------------------------------------------------
+int icamd_grn_supported(int N, long long rows_per_image, int C) { return icamd_grn_ok(N, rows_per_image, C) ? 1 : 0; }
+
+size_t icamd_grn_workspace_bytes(int N, long long rows_per_image, int C) {
+  return icamd_grn_ok(N, rows_per_image, C) ? icamd_grn_bytes(N, (int)rows_per_image, C) : 0;
+}
+
+int icamd_grn_fwd(const void* a, const float* gamma, const float* beta, void* g, float* gx_out, int N, long long rows_per_image,
+                  int C, float eps, void* workspace, size_t workspace_bytes, void* stream) {
+  ProfScope _prof(PC_ELEMWISE, stream);
+  _prof.work(6.0 * N * rows_per_image * C);   // a twice, g once
+  if (a == nullptr || gamma == nullptr || beta == nullptr || g == nullptr || gx_out == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_grn_ok(N, rows_per_image, C)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace == nullptr || workspace_bytes < icamd_grn_workspace_bytes(N, rows_per_image, C)) return ICAMD_ERR_WORKSPACE;
+  return icamd_grn_fwd_launch((const bf16_t*)a, gamma, beta, (bf16_t*)g, gx_out, N, (int)rows_per_image, C, eps, workspace,
+                              (hipStream_t)stream);
+}
+
+int icamd_grn_bwd(const void* dg, const void* a, const float* gx, const float* gamma, const void* z, void* dx, float* dgamma,
+                  float* dbeta, int accumulate, int N, long long rows_per_image, int C, float eps, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+  ProfScope _prof(PC_ELEMWISE, stream);
+  _prof.work((z ? 12.0 : 10.0) * N * rows_per_image * C);   // dg and a twice, z once, dx once
+  if (dg == nullptr || a == nullptr || gx == nullptr || gamma == nullptr || dx == nullptr || dgamma == nullptr || dbeta == nullptr)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_grn_ok(N, rows_per_image, C)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace == nullptr || workspace_bytes < icamd_grn_workspace_bytes(N, rows_per_image, C)) return ICAMD_ERR_WORKSPACE;
+  return icamd_grn_bwd_launch((const bf16_t*)dg, (const bf16_t*)a, gx, gamma, (const bf16_t*)z, (bf16_t*)dx, dgamma, dbeta,
+                              accumulate, N, (int)rows_per_image, C, eps, workspace, (hipStream_t)stream);
 }
 
 // ---- attention (ViT) --------------------------------------------------------------------------------------------

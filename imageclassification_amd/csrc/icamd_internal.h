@@ -417,3 +417,13 @@ int icamd_layerscale_param_grads_launch(const float* G, const float* w, const fl
                                         float* dw, float* dbias, float* dgamma, int accumulate, hipStream_t s);
 int icamd_layerscale_bwd_launch(const bf16_t* dout, const bf16_t* z, const float* gamma, const float* keep, bf16_t* dz,
                                 float* part, long long rows, int C, long long rows_per_image, hipStream_t s);
+
+// ConvNeXt V2: global response normalisation (grn.hip)
+bool icamd_grn_ok(int N, long long HW, int C);
+void icamd_grn_plan(int N, int HW, int C, int* S, int* rps, int* B, int* rpb);
+size_t icamd_grn_bytes(int N, int HW, int C);
+int icamd_grn_fwd_launch(const bf16_t* a, const float* gamma, const float* beta, bf16_t* g, float* gx_out, int N, int HW, int C,
+                         float eps, void* workspace, hipStream_t s);
+int icamd_grn_bwd_launch(const bf16_t* dg, const bf16_t* a, const float* gx, const float* gamma, const bf16_t* z, bf16_t* dx,
+                         float* dgamma, float* dbeta, int accumulate, int N, int HW, int C, float eps, void* workspace,
+                         hipStream_t s);

@@ -57,7 +57,7 @@ def conv_desc(N, IH, IW, Cin, Cout, KH, KW, stride, pad):
     return ConvDesc(N, IH, IW, Cin, OH, OW, Cout, KH, KW, stride, pad)
 
 
-# name -> (restype, argtypes); mirrors include/icamd.h one to one
+# name -> (restype, argtypes); with _SIGNATURES_ADDED below it mirrors include/icamd.h one to one
 _P = c_void_p
 _SIGNATURES = {
     "icamd_abi_version": (c_int, []),
@@ -203,7 +203,18 @@ _SIGNATURES = {
     "icamd_prof_collect": (c_int, [POINTER(c_double), POINTER(c_longlong), POINTER(c_double), POINTER(c_double), c_int]),
 }
 
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# Entries added after the host layer's answers were recorded (tests/golden/capi_answers.json pins what every entry of _SIGNATURES
+# answers without a GPU, recorded from the library before the C-ABI layer was split into units; that record covers _SIGNATURES and
+# stays as it is).  Same form, bound by load() like the others; the tests that arrive with an entry hold its host layer.
+_SIGNATURES_ADDED = {
+    # ConvNeXt V2 (csrc/grn.hip): global response normalisation over [N][rows_per_image][C], C % 64 == 0, 128 <= C <= 6144
+    "icamd_grn_supported": (c_int, [c_int, c_longlong, c_int]),
+    "icamd_grn_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),
+    "icamd_grn_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_float, _P, c_size_t, _P]),
+    "icamd_grn_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_longlong, c_int, c_float, _P, c_size_t, _P]),
+}
+
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_ADDED)
 
 _lib = None
 
@@ -218,7 +229,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in {**_SIGNATURES, **_SIGNATURES_ADDED}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -315,6 +315,22 @@ int icamd_layerscale_param_grads(const float* G, const float* w, const float* bi
                                  const float* dropped, int n_images, float cb, int C, int K, float* dw, float* dbias,
                                  float* dgamma, int accumulate, void* stream);
 
+/* ConvNeXt V2: global response normalisation over a bf16 [N][rows_per_image][C] (channels last; timm GlobalResponseNorm):
+ *   Gx[n][c] = sqrt(sum over the rows of a^2),  Nx = Gx / (mean_c Gx[n][:] + eps),  g = a * (1 + gamma[c] * Nx[n][c]) + beta[c].
+ * fwd leaves gx_out = Gx (fp32 [N][C]) for bwd.  bwd: dx = dg * s + a * t, the full derivative through Gx and its channel mean (t = 0
+ * where Gx = 0); with z given (the tensor a = gelu(z) came from) dx = d z = that value * gelu'(z), rounded once.  dgamma / dbeta: fp32
+ * [C], (+)= under `accumulate`.  Two passes over the wide tensors each way (per-workgroup partial sums in the workspace, summed in a
+ * fixed order: no atomics, the same bits on every launch), and one [N][C]-sized launch for the parameter gradients.
+ * _supported: C % 64 == 0, 128 <= C <= 6144, N <= 65535, rows_per_image * C < 2^31; elsewhere both calls return
+ * ICAMD_ERR_UNSUPPORTED before anything is written and _workspace_bytes returns 0. */
+int icamd_grn_supported(int N, long long rows_per_image, int C);
+size_t icamd_grn_workspace_bytes(int N, long long rows_per_image, int C);
+int icamd_grn_fwd(const void* a, const float* gamma, const float* beta, void* g, float* gx_out, int N, long long rows_per_image,
+                  int C, float eps, void* workspace, size_t workspace_bytes, void* stream);
+int icamd_grn_bwd(const void* dg, const void* a, const float* gx, const float* gamma, const void* z, void* dx, float* dgamma,
+                  float* dbeta, int accumulate, int N, long long rows_per_image, int C, float eps, void* workspace,
+                  size_t workspace_bytes, void* stream);
+
 /* ViT token plumbing: tokens[b][0] = cls + pos[0], tokens[b][1+i] = patches[b][i] + pos[1+i] (bf16 out, fp32 parameters);
  * batch_sum: out[j] (+)= sum_b x[b*stride + j] (cls_token / pos_embed gradients); strided row copies; zero fill. */
 int icamd_vit_tokens_fwd(const void* patches, const float* cls_token, const float* pos_embed, void* tokens, int B, int T, int C,

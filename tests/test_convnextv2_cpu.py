@@ -1,0 +1,299 @@
+"""ConvNeXt V2 without a GPU: parameter counts, timm's names and order, the zero GRN init, state-dict round trips (4-D fc filters
+included), the command-line surface, the library calls of a V2 block in both passes, the V1 layouts untouched, the closed forms of
+tests/_convnextv2_ref.py against fp64 autograd, and the loop counts of csrc/grn.hip at the shapes tests/test_grn_gpu.py runs.
+
+The models construct on the CPU under the replacements of tests/golden/make_arena_layouts.py (install_stubs) and, for the call
+lists, tests/golden/make_call_traces.py (install_recorders)."""
+import importlib.util
+import json
+import os
+import sys
+
+import pytest
+import torch
+
+from _convnextv2_ref import CONFIGS, PARAM_COUNTS, ConvNeXtV2Ref, grn_closed_form, grn_plan, grn_timm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(GOLDEN, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+L = _load("make_arena_layouts")
+T = _load("make_call_traces")
+
+
+@pytest.fixture()
+def stubs(monkeypatch):
+    L.install_stubs(monkeypatch.setattr)
+
+
+def _build(arch, num_classes=10, **kw):
+    from imageclassification_amd.convnext import ConvNeXt
+    return ConvNeXt(arch, num_classes, device="cpu", seed=0, **kw)
+
+
+def _count(shapes):
+    total = 0
+    for s in shapes:
+        n = 1
+        for d in s:
+            n *= d
+        total += n
+    return total
+
+
+@pytest.mark.parametrize("arch", list(PARAM_COUNTS))
+def test_parameter_count(stubs, arch):
+    from imageclassification_amd import convnext
+    assert convnext.CONFIGS[arch] == CONFIGS[arch] and arch in convnext.GRN_ARCHS
+    net = _build(arch, 1000)
+    assert _count(p.torch_shape for p in net.params.values()) == PARAM_COUNTS[arch]
+    assert net.grn and not net.fused_ls and net.num_classes == 1000 and net.dims == CONFIGS[arch][1]
+    assert [st["dim"] for st in net.stages] == list(net.dims) and all("name" in b for st in net.stages for b in st["blocks"])
+
+
+def test_configs_stay_pairs_and_v1_keeps_its_count(stubs):
+    from imageclassification_amd import convnext
+    for name, cfg in convnext.CONFIGS.items():
+        depths, dims = cfg
+        assert len(depths) == len(dims) == 4
+    assert convnext.GRN_ARCHS == set(CONFIGS) and convnext.GRN_ARCHS < set(convnext.CONFIGS)
+    assert not any(n in convnext.GRN_ARCHS for n in ("convnext_tiny", "convnext_small", "convnext_test", "convnext_pin"))
+    # the same count, by the same formula, gives V1 tiny's known figure
+    v1 = _build("convnext_tiny", 1000)
+    assert _count(p.torch_shape for p in v1.params.values()) == 28589128 and not v1.grn
+
+
+def test_names_order_and_init(stubs):
+    net = _build("convnextv2_test")
+    ref = ConvNeXtV2Ref("convnextv2_test", 10)
+    sd = net.state_dict()
+    assert list(sd) == list(ref.state_dict())                      # the oracle registers timm's order
+    assert {k: tuple(v.shape) for k, v in sd.items()} == {k: tuple(v.shape) for k, v in ref.state_dict().items()}
+    block = [k for k in sd if k.startswith("stages.2.blocks.1.")]
+    assert block == ["stages.2.blocks.1." + n for n in (
+        "conv_dw.weight", "conv_dw.bias", "norm.weight", "norm.bias", "mlp.fc1.weight", "mlp.fc1.bias", "mlp.grn.weight",
+        "mlp.grn.bias", "mlp.fc2.weight", "mlp.fc2.bias")]
+    assert not any(k.endswith(".gamma") for k in sd)
+    assert sd["stages.2.blocks.1.mlp.grn.weight"].shape == (512,) and sd["stages.2.blocks.1.mlp.grn.bias"].shape == (512,)
+    for k, v in sd.items():
+        if ".mlp.grn." in k:
+            assert bool((v == 0).all()), k                          # both GRN vectors start at zero
+        elif k.endswith("norm.weight") or k in ("stem.1.weight",) or k.endswith("downsample.0.weight"):
+            assert bool((v == 1).all()), k
+    assert float(sd["stages.0.blocks.0.mlp.fc1.weight"].std()) > 0.01
+
+
+def test_state_dict_round_trip_with_4d_fc_filters(stubs):
+    net = _build("convnextv2_test")
+    first = net.state_dict()
+    sd = {k: v * 2 + 1 for k, v in first.items()}
+    four_d = {k: (v[:, :, None, None] if (".mlp.fc1.weight" in k or ".mlp.fc2.weight" in k) else v) for k, v in sd.items()}
+    assert any(v.dim() == 4 and v.shape[2:] == (1, 1) for k, v in four_d.items() if ".mlp.fc" in k)
+    for given in (sd, four_d):
+        net.load_state_dict({k: torch.zeros_like(v) for k, v in first.items()})
+        assert net.load_state_dict(given) == []
+        out = net.state_dict()
+        assert list(out) == list(first)
+        for k in first:
+            assert out[k].shape == first[k].shape and torch.equal(out[k], sd[k]), k      # fc filters come back as [out, in]
+    with pytest.raises(ValueError):
+        net.load_state_dict({**sd, "stages.0.blocks.0.mlp.grn.weight": torch.zeros(64)})
+
+
+def test_create_model_reaches_the_constructor(stubs, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import train as TR
+    from imageclassification_amd.convnext import ConvNeXt
+
+    class OnCpu(ConvNeXt):
+        def __init__(self, arch, num_classes, **kw):
+            super().__init__(arch, num_classes, device="cpu", seed=0, **kw)
+
+    monkeypatch.setattr(TR, "ConvNeXt", OnCpu)
+    net = TR.create_model("convnextv2_tiny", 10, 224, 0.1)
+    assert isinstance(net, ConvNeXt) and net.arch == "convnextv2_tiny" and net.grn
+    assert net.drop_path_rate == 0.1 and net.stages[0]["blocks"][0]["rate"] == 0.0
+    assert abs(net.stages[-1]["blocks"][-1]["rate"] - 0.1) < 1e-7
+    assert TR.get_args_parser().parse_args(["--model", "convnextv2_tiny", "--drop_path", "0.1"]).drop_path == 0.1
+    with pytest.raises(ValueError, match="convnextv2_tiny"):
+        TR.create_model("convnextv2_atto", 10, 224, 0.1)
+
+
+def test_v1_layouts_still_hash_to_the_fixture(stubs):
+    with open(os.path.join(GOLDEN, "arena_layouts.json")) as f:
+        fixture = json.load(f)["models"]
+    for model_id in ("convnext_test", "convnext_tiny"):
+        m = L.build_model(model_id)
+        assert L.layout_hash(m) == fixture[model_id]["sha256"]
+        assert not m.grn and not hasattr(m, "ones")
+
+
+def test_new_entries_are_in_the_ctypes_table():
+    from imageclassification_amd import hip
+    for name in ("icamd_grn_supported", "icamd_grn_workspace_bytes", "icamd_grn_fwd", "icamd_grn_bwd"):
+        assert name in hip._SIGNATURES_ADDED and name not in hip._SIGNATURES and name in hip.EXPORTED_SYMBOLS
+    assert len(hip._SIGNATURES_ADDED["icamd_grn_fwd"][1]) == 12 and len(hip._SIGNATURES_ADDED["icamd_grn_bwd"][1]) == 16
+    assert hip.EXPORTED_SYMBOLS == tuple(hip._SIGNATURES) + tuple(hip._SIGNATURES_ADDED)
+    lib = hip.load()                                      # binds both tables
+    assert lib.icamd_grn_workspace_bytes.restype is hip.c_size_t and lib.icamd_grn_fwd.argtypes is not None
+    assert hip.ABI_VERSION == 6
+    header = open(os.path.join(ROOT, "include", "icamd.h")).read()
+    internal = open(os.path.join(ROOT, "imageclassification_amd", "csrc", "icamd_internal.h")).read()
+    assert "int icamd_grn_fwd(" in header and "int icamd_grn_bwd(" in header
+    assert "icamd_grn_fwd_launch(" in internal and "icamd_grn_bwd_launch(" in internal
+    units = open(os.path.join(ROOT, "imageclassification_amd", "csrc", "build.sh")).read().split('UNITS="')[1].split('"')[0].split()
+    assert "grn" in units
+
+
+def test_library_calls_of_a_v2_step(monkeypatch):
+    """The launch list per block: forward dw, LN, fc1 + GELU, GRN, fc2 (+ residual; a dropped block: fc2 and the
+    drop-path kernel); backward tail, fc2 weight gradient on the side lane with g as input, plain data gradient, GRN backward with
+    z1, fc1 and the rest as in V1.  Every pointer of every call lies in a tensor of the model."""
+    from imageclassification_amd import hip
+    T.install_recorders(monkeypatch.setattr)
+    monkeypatch.setattr(hip, "_SIGNATURES", {**hip._SIGNATURES, **hip._SIGNATURES_ADDED})     # the recorder reads argument types here
+    monkeypatch.delenv("ICAMD_WGRAD_STREAM", raising=False)
+    net = _build("convnextv2_test", drop_path_rate=0.2)
+    hooks = []
+    net.grad_ready_hook = lambda lo, hi, events=(): hooks.append((lo, hi))
+    net.injected_keep = T._masks(net, 1)
+    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(1))
+    net.train()
+    ws = net.pack(x)
+    del T.TRACE[:]
+    net.forward_packed(ws)
+    fwd = [r[0] for r in T.TRACE]
+    plain = ["icamd_dwconv7_fwd", "icamd_layernorm_fwd", "icamd_conv2d_fwd_gelu", "icamd_grn_fwd", "icamd_conv2d_fwd"]
+    dropped = plain + ["icamd_layerscale_fwd"]
+    assert fwd[:2] == ["icamd_conv2d_fwd", "icamd_layernorm_fwd"]
+    assert fwd[2:2 + len(plain)] == plain                                           # block 0: rate 0
+    assert fwd[2 + len(plain):4 + len(plain)] == ["icamd_layernorm_fwd", "icamd_conv2d_fwd"]
+    assert fwd[4 + len(plain):4 + len(plain) + len(dropped)] == dropped              # block 1: dropped
+    assert fwd.count("icamd_grn_fwd") == 5 and fwd.count("icamd_layerscale_fwd") == 4
+    assert not any(n in fwd for n in ("icamd_rows_fix", "icamd_layerscale_fold"))
+    grn_calls = [r for r in T.TRACE if r[0] == "icamd_grn_fwd"]
+    assert [(r[2][5], r[2][6], r[2][7]) for r in grn_calls] == [(2, 256, 128), (2, 64, 256), (2, 16, 512), (2, 16, 512), (2, 4, 768)]
+    n_fwd = len(T.TRACE)
+    net.backward_packed(ws)
+    bwd = T.TRACE[n_fwd:]
+    names = [r[0] for r in bwd]
+    last = names.index("icamd_layerscale_bwd")                                       # the last block's tail comes first
+    assert names[last:last + 4] == ["icamd_layerscale_bwd", "icamd_conv2d_wgrad_bias", "icamd_conv2d_dgrad", "icamd_grn_bwd"]
+    assert names[last + 4:last + 7] == ["icamd_conv2d_wgrad_bias", "icamd_conv2d_dgrad", "icamd_layernorm_bwd"]
+    wgrad, dgrad, grn = bwd[last + 1], bwd[last + 2], bwd[last + 3]
+    blk = ws["stages"][3]["blocks"][0]
+    assert wgrad[2][1] == blk["g"].data_ptr() and wgrad[2][-1] == 1                  # g is fc2's input; side lane
+    assert grn[2][0] == dgrad[2][3] and grn[2][1] == blk["a"].data_ptr() and grn[2][2] == blk["gx"].data_ptr()
+    assert grn[2][4] == blk["z1"].data_ptr() and grn[2][5] not in (grn[2][0], grn[2][1]) and grn[2][8] == 0 and grn[2][-1] == 0
+    p = net.params["stages.3.blocks.0.mlp.grn.weight"]
+    assert grn[2][6] == net._gf(p) and grn[2][7] == net._gf(net.params["stages.3.blocks.0.mlp.grn.bias"])
+    assert names.count("icamd_grn_bwd") == 5 and names.count("icamd_layerscale_bwd") == 4
+    assert not any(n in names for n in ("icamd_conv2d_dgrad_gelu", "icamd_gelu_bwd", "icamd_layerscale_param_grads"))
+    # the GRN gradients lie in the range of their block handed to the hook
+    lo = [h for h in hooks if h[0] == net.params["stages.3.blocks.0.conv_dw.weight"].offset]
+    assert lo and net.params["stages.3.blocks.0.conv_dw.weight"].offset < p.offset < net.params["head.norm.weight"].offset
+    net.backward_packed(ws, accumulate=True)
+    assert [r[2][8] for r in T.TRACE if r[0] == "icamd_grn_bwd"][5:] == [1] * 5
+    net.eval()
+    n0 = len(T.TRACE)
+    net.forward_packed(ws, logits_only=True)
+    ev = [r[0] for r in T.TRACE[n0:]]
+    assert ev.count("icamd_grn_fwd") == 5 and "icamd_layerscale_fwd" not in ev        # eval: the residual rides in fc2's store pass
+    held = {}
+    T._collect(vars(net), held, set())
+    T._collect(ws, held, set())
+    held[x.untyped_storage().data_ptr()] = (x.untyped_storage().nbytes(), x)
+    T.canonical(T.TRACE, held, x)                                                    # LookupError for a pointer into no tensor
+
+
+def test_host_layer_of_the_grn_entries():
+    """What the four entries answer without a GPU: the queries by shape (the sizes are grn_plan's), and the refusals in the order
+    the header states -- NULL pointers, then the shape, then the workspace -- each before anything could be launched."""
+    import ctypes
+    from imageclassification_amd import hip
+    lib = hip.load()
+
+    def up(v):
+        return (v + 255) // 256 * 256
+
+    for N, HW, C in [(32, 3136, 384), (2, 49, 3072), (2, 196, 6144), (1, 1, 128), (256, 196, 1536), (65535, 1, 128)]:
+        p = grn_plan(N, HW, C)
+        assert lib.icamd_grn_supported(N, HW, C) == 1
+        assert lib.icamd_grn_workspace_bytes(N, HW, C) == up(N * p["S"] * 2 * C * 4) + up(N * 2 * C * 4)
+    for N, HW, C in [(0, 49, 256), (2, 0, 256), (2, 49, 100), (2, 49, 64), (2, 49, 96), (2, 196, 6208), (65536, 49, 256),
+                     (1, 1 << 24, 128), (-1, 49, 256)]:
+        assert lib.icamd_grn_supported(N, HW, C) == 0 and lib.icamd_grn_workspace_bytes(N, HW, C) == 0
+    host = ctypes.create_string_buffer(4096)               # never read: every call below is refused first
+    P = ctypes.addressof(host)
+    BAD_ARG, UNSUPPORTED, WORKSPACE = 1, 2, 3
+    big = 1 << 30
+    assert lib.icamd_grn_fwd(None, None, None, None, None, 0, 0, 0, 0.0, None, 0, None) == BAD_ARG
+    assert lib.icamd_grn_bwd(None, None, None, None, None, None, None, None, 0, 0, 0, 0, 0.0, None, 0, None) == BAD_ARG
+    assert lib.icamd_grn_fwd(P, P, P, None, P, 2, 49, 256, 1e-6, P, big, None) == BAD_ARG
+    assert lib.icamd_grn_bwd(P, P, None, P, None, P, P, P, 0, 2, 49, 256, 1e-6, P, big, None) == BAD_ARG
+    assert lib.icamd_grn_fwd(P, P, P, P, P, 2, 49, 100, 1e-6, P, 0, None) == UNSUPPORTED        # the shape before the workspace
+    assert lib.icamd_grn_bwd(P, P, P, P, None, P, P, P, 0, 2, 49, 64, 1e-6, P, 0, None) == UNSUPPORTED
+    need = lib.icamd_grn_workspace_bytes(2, 49, 256)
+    assert lib.icamd_grn_fwd(P, P, P, P, P, 2, 49, 256, 1e-6, P, need - 1, None) == WORKSPACE
+    assert lib.icamd_grn_bwd(P, P, P, P, P, P, P, P, 0, 2, 49, 256, 1e-6, P, need - 1, None) == WORKSPACE
+    assert lib.icamd_grn_fwd(P, P, P, P, P, 2, 49, 256, 1e-6, None, big, None) == WORKSPACE
+    assert bytes(host) == bytes(4096)
+
+
+# ---------------------------------------------------------------------------------------------------------------- closed forms
+@pytest.mark.parametrize("shape", [(3, 49, 256, True), (2, 196, 384, False), (1, 1, 128, True), (2, 64, 6144, True)])
+def test_closed_form_matches_fp64_autograd(shape):
+    N, HW, C, zero = shape
+    g = torch.Generator().manual_seed(0)
+    a = torch.nn.functional.gelu(torch.randn(N, HW, C, generator=g, dtype=torch.float64)).to(torch.bfloat16).double()
+    if zero:
+        a[0, :, 5] = 0                       # an all-zero channel
+        if N > 1:
+            a[-1] = 0                        # an all-zero sample
+    a.requires_grad_(True)
+    w = (0.5 * torch.randn(C, generator=g, dtype=torch.float64)).requires_grad_(True)
+    b = (0.1 * torch.randn(C, generator=g, dtype=torch.float64)).requires_grad_(True)
+    dg = torch.randn(N, HW, C, generator=g, dtype=torch.float64).to(torch.bfloat16).double()
+    out = grn_timm(a, w, b)
+    out.backward(dg)
+    assert bool(torch.isfinite(a.grad).all())                     # autograd's subgradient at Gx = 0 is 0: the t = 0 guard
+    cf = grn_closed_form(a.detach(), w.detach(), b.detach(), dg)
+
+    def rel(x, y):
+        return float((x - y).norm() / y.norm().clamp_min(1e-300))
+
+    assert rel(cf["g"], out.detach()) <= 1e-14 and rel(cf["da"], a.grad) <= 1e-14
+    assert rel(cf["dweight"], w.grad) <= 1e-13 and rel(cf["dbias"], b.grad) <= 1e-14
+    assert rel(cf["gx"], a.detach().norm(dim=1)) <= 1e-15
+    # NHWC input of the model: the same function on [N, H, W, C]
+    if HW == 49:
+        assert torch.equal(grn_timm(a.detach().view(N, 7, 7, C), w.detach(), b.detach()).view(N, HW, C), out.detach())
+
+
+def test_every_loop_of_the_kernels_runs_more_than_once_in_the_gpu_cases():
+    """grn_plan mirrors icamd_grn_plan / reduce_tcols of csrc/grn.hip (tests/test_grn_gpu.py checks it against the library's
+    workspace size).  The multi-trip case drives every problem-sized loop at least twice but the prologue's channel loop (four
+    channels per thread and trip: more than one trip needs C > 1024, which leaves a reduction workgroup one row lane), and the
+    6144-channel case drives that one 6 times; the figures are the ones the GPU test's docstring quotes."""
+    p = grn_plan(40, 784, 768)
+    assert (p["S"], p["rps"], p["B"], p["rpb"], p["tcols"], p["rlanes"], p["ctiles"]) == (25, 32, 72, 11, 96, 2, 1)
+    assert p["trips"] == {"reduce rows": 16, "reduce lds outputs": 3, "reduce row lanes": 2, "prologue channels": 1,
+                          "prologue segments": 25, "apply vectors": 5, "parameter-gradient samples": 10}
+    assert all(v >= 2 for k, v in p["trips"].items() if k != "prologue channels")
+    wide = grn_plan(2, 196, 6144)
+    assert (wide["tcols"], wide["ctiles"], wide["rlanes"]) == (256, 3, 1) and wide["trips"]["prologue channels"] == 6
+    assert (wide["S"], wide["B"], wide["rpb"]) == (7, 25, 8) and wide["trips"]["apply vectors"] == 24
+    capped = grn_plan(512, 160, 128)       # the batch caps the segments and the row blocks
+    assert (capped["S"], capped["rps"], capped["B"]) == (4, 40, 3) and capped["rlanes"] == 16
+    one = grn_plan(1, 1, 128)
+    assert (one["S"], one["B"], one["tcols"]) == (1, 1, 16)
+    stage0 = grn_plan(256, 3136, 384)      # convnextv2_tiny, stage 0, batch 256: 2048 reduce and 4096 apply workgroups
+    assert (stage0["S"], stage0["B"]) == (8, 16)
