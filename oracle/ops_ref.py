@@ -136,12 +136,25 @@ def conv2d_wgrad(x_nhwc, dy_nhwc, ksize, stride, pad, acc=torch.float32):
 
 
 # ---- BatchNorm: icamd_bn_train_finalize / _apply / _bwd ---------------------------------------------
-def bn_train_coeffs(y_nhwc, gamma, beta, running_mean, running_var, momentum, eps):
-    """Batch statistics of the (bf16-rounded) conv output; returns mean, invstd, scale, shift, new running stats."""
+def bn_train_coeffs(y_nhwc, gamma, beta, running_mean, running_var, momentum, eps, acc=torch.float32):
+    """Batch statistics of the (bf16-rounded) conv output; returns mean, invstd, scale, shift, new running stats.
+
+    acc=torch.float32 (the pinned default): var = E[y^2] - mean^2 from fp64 raw moments, every result rounded to fp32 where the
+    kernel stores one.  acc=torch.float64: the centred form var = mean((y - mean)^2), which does not cancel however far the channel
+    mean lies from zero, and every result left in fp64 -- the exact reference of tests/_numeric_ranges.py."""
     C = y_nhwc.shape[-1]
     y = y_nhwc.double().reshape(-1, C)
     n = y.shape[0]
     mean = y.mean(0)
+    if _wide(acc):
+        var = ((y - mean) ** 2).mean(0)
+        invstd = 1.0 / torch.sqrt(var + eps)
+        scale = gamma.double() * invstd
+        shift = beta.double() - mean * scale
+        unbiased = var * (n / (n - 1)) if n > 1 else var
+        rm = (1 - momentum) * running_mean.double() + momentum * mean
+        rv = (1 - momentum) * running_var.double() + momentum * unbiased
+        return mean, invstd, scale, shift, rm, rv
     var = (y * y).mean(0) - mean * mean
     var = var.clamp_min(0)
     invstd = (1.0 / torch.sqrt(var + eps)).float()
@@ -242,19 +255,21 @@ def pack_input(x_nchw, mode=0, lam=1.0, box=None):
 
 
 # ---- loss ------------------------------------------------------------------------------------------
-def soft_targets(y1, y2, lam, smoothing, C):
+def soft_targets(y1, y2, lam, smoothing, C, dtype=torch.float32):
     off = smoothing / C
     on = 1.0 - smoothing + off
-    t1 = torch.full((y1.shape[0], C), off).scatter_(1, y1.view(-1, 1), on)
-    t2 = torch.full((y2.shape[0], C), off).scatter_(1, y2.view(-1, 1), on)
+    t1 = torch.full((y1.shape[0], C), off, dtype=dtype).scatter_(1, y1.view(-1, 1), on)
+    t2 = torch.full((y2.shape[0], C), off, dtype=dtype).scatter_(1, y2.view(-1, 1), on)
     return t1 * lam + t2 * (1.0 - lam)
 
 
-def softmax_xent(logits, y1, y2=None, lam=1.0, smoothing=0.0, gscale=1.0):
-    """logits [B,C] (bf16-representable). Returns per-row loss, argmax, dlogits (bf16 grid)."""
-    x = logits.float().requires_grad_(True)
+def softmax_xent(logits, y1, y2=None, lam=1.0, smoothing=0.0, gscale=1.0, acc=torch.float32):
+    """logits [B,C] (bf16-representable). Returns per-row loss, argmax, dlogits (bf16 grid).  acc=torch.float64: the same formula in
+    fp64 (loss rows stay fp64) -- under a common logit offset of 1024 the fp32 log_softmax alone is off by 1e-4."""
+    _wide(acc)
+    x = logits.detach().to(acc).clone().requires_grad_(True)
     B, C = x.shape
-    t = soft_targets(y1, y1 if y2 is None else y2, lam, smoothing, C)
+    t = soft_targets(y1, y1 if y2 is None else y2, lam, smoothing, C, dtype=acc)
     logp = F.log_softmax(x, dim=-1)
     loss_rows = -(t * logp).sum(-1)
     (loss_rows.sum() * gscale).backward()
