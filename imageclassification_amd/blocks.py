@@ -2,7 +2,7 @@
 (ViT, Swin, ConvNeXt), and the pre-LayerNorm transformer block of ViT and Swin -- its parameters, its activations and its two
 chains, each written once.
 
-  Forward    one forward pass: linear, linear_gelu, layernorm, and `block`
+  Forward    one forward pass: linear, linear_gelu, layernorm, residual (a branch that stochastic depth may drop), and `block`
              norm1 -> qkv -> attention -> proj (+ x) -> norm2 -> fc1 + GELU -> fc2 (+ x1)
   Backward   one backward pass: gemm (weight and bias gradient on the side lane, then the data gradient), layernorm, and `block`,
              the same chain in reverse
@@ -96,32 +96,32 @@ class Forward:
         hip.check(self.lib.icamd_layernorm_fwd(x_ptr, self.m._pf(wp), self.m._pf(bp), y_ptr, st, st + 4 * rows, rows, C, self.eps,
                                                self.s), wp.name)
 
+    def residual(self, l, desc, x_ptr, res_ptr, y_ptr, keep, tmp_ptr, rows, C, tokens_per_image):
+        """y = res + x W^T + b in one kernel -- or, under a stochastic-depth mask `keep` (float [B], 0 or 1 / keep_prob), the branch
+        into the scratch `tmp` and y = res + keep * branch"""
+        if keep is None:
+            return self.linear(l, desc, x_ptr, y_ptr, res_ptr)
+        self.linear(l, desc, x_ptr, tmp_ptr)
+        hip.check(self.lib.icamd_layerscale_fwd(tmp_ptr, res_ptr, self.m.ones.data_ptr(), keep.data_ptr(), y_ptr, rows, C,
+                                                tokens_per_image, self.s), "drop path")
+
     def block(self, blk, b, x, rows, dim, attn_fwd, keep1=None, keep2=None, tokens_per_image=None):
         """One block on the tensor `x`; returns its output b["x2"].  attn_fwd(blk, b) launches qkv -> ao (and lse).  keep1 / keep2:
         this step's per-sample stochastic-depth masks of the two branches (float [B], 0 or 1 / keep_prob), None for a branch that
         is never dropped."""
-        m, lib, s = self.m, self.lib, self.s
         b["keep1"], b["keep2"], b["x"] = keep1, keep2, x
         h, h2, x1 = b["h"].data_ptr(), b["h2"].data_ptr(), b["x1"].data_ptr()
         self.layernorm(x.data_ptr(), blk["n1w"], blk["n1b"], h, b["st1"].data_ptr(), rows, dim)
         self.linear(blk["qkv"], blk["qkv"].desc(rows), h, b["qkv"].data_ptr())
         attn_fwd(blk, b)
         proj, fc2 = blk["proj"], blk["fc2"]
-        if keep1 is None:
-            self.linear(proj, proj.desc(rows), b["ao"].data_ptr(), x1, x.data_ptr())                  # x1 = x + proj(attn)
-        else:     # x1 = x + keep * proj(attn); the branch passes through h2's buffer (LayerNorm 2 overwrites it next)
-            self.linear(proj, proj.desc(rows), b["ao"].data_ptr(), h2)
-            hip.check(lib.icamd_layerscale_fwd(h2, x.data_ptr(), m.ones.data_ptr(), keep1.data_ptr(), x1, rows, dim,
-                                               tokens_per_image, s), "drop path")
+        # x1 = x + keep1 * proj(attn); a dropped branch passes through h2's buffer (LayerNorm 2 overwrites it next)
+        self.residual(proj, proj.desc(rows), b["ao"].data_ptr(), x.data_ptr(), x1, keep1, h2, rows, dim, tokens_per_image)
         self.layernorm(x1, blk["n2w"], blk["n2b"], h2, b["st2"].data_ptr(), rows, dim)
         self.linear_gelu(blk["fc1"], blk["fc1"].desc(rows), h2, b["z"].data_ptr(), b["a"].data_ptr())
-        if keep2 is None:
-            self.linear(fc2, fc2.desc(rows), b["a"].data_ptr(), b["x2"].data_ptr(), x1)               # x2 = x1 + mlp
-        else:     # x2 = x1 + keep * mlp; every buffer of the block is still needed by the backward: a scratch of its own
-            t = m._branch_tmp(self.ws).data_ptr()
-            self.linear(fc2, fc2.desc(rows), b["a"].data_ptr(), t)
-            hip.check(lib.icamd_layerscale_fwd(t, x1, m.ones.data_ptr(), keep2.data_ptr(), b["x2"].data_ptr(), rows, dim,
-                                               tokens_per_image, s), "drop path")
+        # x2 = x1 + keep2 * mlp; every buffer of the block is still needed by the backward: a dropped branch has a scratch of its own
+        t = None if keep2 is None else self.m._branch_tmp(self.ws).data_ptr()
+        self.residual(fc2, fc2.desc(rows), b["a"].data_ptr(), x1, b["x2"].data_ptr(), keep2, t, rows, dim, tokens_per_image)
         return b["x2"]
 
 
@@ -169,7 +169,7 @@ class Backward:
                                                m._gf(wp), m._gf(bp), rows, C, self.acc, *self.ln, self.s), wp.name + " bwd")
 
     def drop_path(self, dout_ptr, keep, dz_ptr, rows, C, tokens_per_image):
-        """gradient of a dropped branch: dz = dout * keep (the entry's dgamma goes to a scratch vector)"""
+        """gradient of a dropped branch (Swin's two, ConvNeXt V2's): dz = dout * keep (the entry's dgamma goes to a scratch vector)"""
         m, ws = self.m, self.ws
         hip.check(self.lib.icamd_layerscale_bwd(dout_ptr, dout_ptr, m.ones.data_ptr(), keep.data_ptr(), self.writes(dz_ptr),
                                                 ws["ls_dg"].data_ptr(), rows, C, tokens_per_image, 0, ws["ls_ws"].data_ptr(),

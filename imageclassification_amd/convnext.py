@@ -7,8 +7,13 @@ Linear -> gamma -> drop_path -> residual; stem 4x4/4 conv + channels-first LN :7
 names are used here: `stem.{0,1}`, `stages.S.downsample.{0,1}`, `stages.S.blocks.B.{conv_dw,norm,mlp.fc1,mlp.fc2,gamma}`,
 `head.{norm,fc}`.  Stochastic depth follows timm: linearly increasing rates up to `drop_path_rate`
 (train.py:189-192 passes --drop_path, default 0.05), per-sample masks drawn on the host from torch's RNG.  The flat arenas are
-arena.py's; the GEMM and LayerNorm steps of both passes (blocks.Forward, blocks.Backward: weight gradients on the side lane, the
-waits before a buffer is overwritten) are blocks.py's.  The block itself is written here.
+arena.py's; the GEMM, LayerNorm and drop-path steps of both passes (blocks.Forward, blocks.Backward: weight gradients on the side
+lane, the waits before a buffer is overwritten) are blocks.py's.  The block itself is written here.
+
+forward_packed and backward_packed are the walk: stem, per stage `_downsample_*` and per block `_block_*` (dw -> LN -> fc1 + GELU ->
+tail; backward: tail -> fc1 -> LN -> `_dw_bwd`), head.  The tail, from GELU's output to the block's, is one of three pairs of methods,
+chosen once in `_build`: `_v2_*` (GRN, fc2, drop path), `_folded_*` (layer scale folded into fc2's filter), `_unfolded_*` (the
+layer-scale kernels, ICAMD_FUSED_LAYERSCALE=0).
 
 NHWC activations make every "channels-first LayerNorm" an ordinary row LayerNorm over pixels, and every Linear a 1x1
 convolution on the same tensor (bias fused); the depthwise stencil and the layer-scale tail are dedicated kernels.
@@ -16,8 +21,7 @@ convolution on the same tensor (bias fused); the depthwise stencil and the layer
 ConvNeXt V2 (the `convnextv2_*` names, GRN_ARCHS) is the same class: its block has no layer scale and carries timm's
 GlobalResponseNorm between GELU and fc2 (`mlp.grn.weight` / `mlp.grn.bias`, shape (4 dim,), initialised to zero; restated from
 memory like the V1 block, not pinned to a timm release): dw -> LN -> fc1 + GELU (z1, a) -> GRN (g) -> fc2 -> drop path -> residual.
-GRN is csrc/grn.hip (icamd_grn_fwd / icamd_grn_bwd; the backward also applies gelu'(z1), as fc2's data gradient does for V1).  Every
-V2 step is taken only where `self.grn` is set; the V1 names keep their layouts, call sequences and both tail routes.
+GRN is csrc/grn.hip (icamd_grn_fwd / icamd_grn_bwd; the backward also applies gelu'(z1), as fc2's data gradient does for V1).
 """
 import ctypes
 import os
@@ -63,11 +67,9 @@ class _Conv:
         self.descs = {}
 
     def desc(self, N, H, W):
-        key = (N, H, W)
-        d = self.descs.get(key)
+        d = self.descs.get((N, H, W))
         if d is None:
-            d = hip.conv_desc(N, H, W, self.cin_p, self.cout_p, self.k, self.k, self.stride, 0)
-            self.descs[key] = d
+            d = self.descs[N, H, W] = hip.conv_desc(N, H, W, self.cin_p, self.cout_p, self.k, self.k, self.stride, 0)
         return d
 
 
@@ -103,9 +105,8 @@ class ConvNeXt(ArenaModel):
         self.stem = conv("stem.0", 3, d0, 4, 4, cin_p=8, needs_dgrad=False)
         self.stem_nw = add("stem.1.weight", (d0,), "vec", (d0,))
         self.stem_nb = add("stem.1.bias", (d0,), "vec", (d0,))
-        self.stages = []
+        self.stages, self.blocks = [], []     # blocks: every stage's, in order; a block's "index" is its place in this list
         rates = torch.linspace(0, self.drop_path_rate, sum(self.depths)).tolist()
-        bi = 0
         for si, (depth, dim) in enumerate(zip(self.depths, self.dims)):
             st = {"dim": dim, "blocks": []}
             if si > 0:
@@ -115,7 +116,7 @@ class ConvNeXt(ArenaModel):
                 st["ds"] = conv(f"stages.{si}.downsample.1", prev, dim, 2, 2)
             for j in range(depth):
                 n = f"stages.{si}.blocks.{j}"
-                blk = {"name": n, "rate": rates[bi]}
+                blk = {"name": n, "index": len(self.blocks), "dim": dim, "rate": rates[len(self.blocks)]}
                 blk["dw_w"] = add(f"{n}.conv_dw.weight", (dim, 1, 7, 7), "dw", (7, 7, dim))
                 blk["dw_b"] = add(f"{n}.conv_dw.bias", (dim,), "vec", (dim,))
                 blk["nw"] = add(f"{n}.norm.weight", (dim,), "vec", (dim,))
@@ -128,7 +129,7 @@ class ConvNeXt(ArenaModel):
                 if not self.grn:
                     blk["gamma"] = add(f"{n}.gamma", (dim,), "vec", (dim,))
                 st["blocks"].append(blk)
-                bi += 1
+                self.blocks.append(blk)
             self.stages.append(st)
         dl = self.dims[-1]
         self.head_nw = add("head.norm.weight", (dl,), "vec", (dl,))
@@ -138,16 +139,19 @@ class ConvNeXt(ArenaModel):
         # folded layer scale: one folded fc2 bias per block; the folded filter takes fc2's place in the bf16 shadow (and, through
         # refresh_transposed, in the transposed shadow), so _w(fc2) / _wt(fc2) are the folded operands
         self.fused_ls = _FUSED_LS and not self.grn     # V2 has no layer scale to fold
-        if self.grn:     # the drop-path tail runs icamd_layerscale_fwd / _bwd with this constant in gamma's place
+        if self.grn:     # the drop-path steps run icamd_layerscale_fwd / _bwd with this constant in gamma's place
             self.ones = torch.ones(max(self.dims), dtype=torch.float32, device=dev)
+            self._tail_fwd, self._tail_bwd = self._v2_fwd, self._v2_bwd
+        elif self.fused_ls:
+            self._tail_fwd, self._tail_bwd = self._folded_fwd, self._folded_bwd
+        else:
+            self._tail_fwd, self._tail_bwd = self._unfolded_fwd, self._unfolded_bwd
         fb = 0
-        for st in self.stages:
-            for blk in st["blocks"]:
-                blk["fb_off"] = fb
-                fb = align(fb + blk["fc2"].cout_p, 64)
+        for blk in self.blocks:
+            blk["fb_off"] = fb
+            fb = align(fb + blk["fc2"].cout_p, 64)
         self.fold_bias = torch.zeros(max(fb, 64), dtype=torch.float32, device=dev)
-        self._ls_cbs = None          # the per-block constants the shadow is currently folded with
-        self._ls_jobs = None
+        self._ls_cbs = self._ls_jobs = None     # the per-block constants the shadow is currently folded with, and their job table
 
     def _ctor_kwargs(self):
         return {"arch": self.arch, "num_classes": self.num_classes, "drop_path_rate": self.drop_path_rate}
@@ -163,9 +167,7 @@ class ConvNeXt(ArenaModel):
                 sd[name] = torch.nn.init.trunc_normal_(torch.empty(p.torch_shape), std=0.02, generator=g)
             elif name.endswith(".gamma"):
                 sd[name] = torch.full(p.torch_shape, 1e-6)
-            elif ".mlp.grn." in name:
-                sd[name] = torch.zeros(p.torch_shape)
-            elif name.endswith("weight"):
+            elif name.endswith("weight") and ".mlp.grn." not in name:
                 sd[name] = torch.ones(p.torch_shape)
             else:
                 sd[name] = torch.zeros(p.torch_shape)
@@ -173,24 +175,22 @@ class ConvNeXt(ArenaModel):
 
     def _ls_mode_cbs(self):
         """timm drop_path scales the kept samples by 1 / keep_prob in training; identity in eval."""
-        blocks = [blk for st in self.stages for blk in st["blocks"]]
         if self.training and self.injected_keep is not None:      # tests: the scale is whatever the injected masks carry
             cbs = []
-            for blk, k in zip(blocks, self.injected_keep):
+            for blk, k in zip(self.blocks, self.injected_keep):
                 k = k.float().cpu()
                 cb = float(k.max()) if float(k.max()) > 0.0 else 1.0
                 assert bool(((k == 0) | (k == cb)).all()), "folded layer scale: a keep mask is {0, c} per block"
                 cbs.append(cb if blk["rate"] > 0.0 else 1.0)
             return cbs
-        return [1.0 / (1.0 - blk["rate"]) if (self.training and blk["rate"] > 0.0) else 1.0 for blk in blocks]
+        return [1.0 / (1.0 - blk["rate"]) if (self.training and blk["rate"] > 0.0) else 1.0 for blk in self.blocks]
 
     def _fold_layerscale(self):
         import struct
         cbs = self._ls_mode_cbs()
         if self._ls_jobs is None or cbs != self._ls_cbs:
             rows, row0, elems = [], 0, 0
-            blocks = [blk for st in self.stages for blk in st["blocks"]]
-            for blk, cb in zip(blocks, cbs):
+            for blk, cb in zip(self.blocks, cbs):
                 c = blk["fc2"]
                 bits = struct.unpack("<i", struct.pack("<f", cb))[0]
                 rows.append([c.w.offset, blk["gamma"].offset, c.b.offset, blk["fb_off"], c.cout, c.cin, row0, bits])
@@ -221,17 +221,11 @@ class ConvNeXt(ArenaModel):
         def f32(n):
             return torch.empty(n, dtype=torch.float32, device=dev)
 
-        ws = {"N": N, "H": H, "W": W}
-        ws["x8"] = act(N, H, W, 8)
-        h, w = H // 4, W // 4
-        d0 = self.dims[0]
-        ws["s"] = act(N, h, w, d0)
-        ws["x0"] = act(N, h, w, d0)
-        ws["st_stem"] = f32(2 * N * h * w)
+        h, w, d0 = H // 4, W // 4, self.dims[0]
+        ws = {"N": N, "H": H, "W": W, "x8": act(N, H, W, 8), "s": act(N, h, w, d0), "x0": act(N, h, w, d0), "st_stem": f32(2 * N * h * w)}
         max_act, max_rows = N * h * w * 4 * d0, N * h * w
         wg = lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(self.stem.desc(N, H, W)))
-        dwg = grn = 0
-        stages = []
+        dwg, grn, stages = 0, 0, []
         for si, st in enumerate(self.stages):
             dim = st["dim"]
             sw = {"blocks": []}
@@ -239,6 +233,7 @@ class ConvNeXt(ArenaModel):
                 sw["ln"] = act(N, h, w, self.dims[si - 1])
                 sw["st"] = f32(2 * N * h * w)
                 wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(st["ds"].desc(N, h, w))))
+                sw["in_hw"] = (h, w)
                 h, w = h // 2, w // 2
                 sw["x"] = act(N, h, w, dim)
             sw["hw"] = (h, w)
@@ -255,37 +250,27 @@ class ConvNeXt(ArenaModel):
                 dwg = max(dwg, lib.icamd_dwconv7_wgrad_workspace_bytes(N, h, w, dim))
                 max_act = max(max_act, rows * 4 * dim)
             stages.append(sw)
-        ws["stages"] = stages
-        ws["final_hw"] = (h, w)
         dl = self.dims[-1]
-        ws["pool"] = act(N, dl)
-        ws["pn"] = act(N, dl)
-        ws["st_head"] = f32(2 * N)
+        ws.update(stages=stages, final_hw=(h, w), max_act=max_act, pool=act(N, dl), pn=act(N, dl), st_head=f32(2 * N))
         loss_workspace(ws, N, self.ncls_p, dev)
         wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(self.head.desc(N, 1, 1))))
-        ws["wg_ws"] = torch.empty(wg, dtype=torch.uint8, device=dev)
-        ws["wg_bytes"] = wg
-        ws["dwg_ws"] = torch.empty(max(dwg, 256), dtype=torch.uint8, device=dev)
-        ws["dwg_bytes"] = dwg
-        maxc = 4 * max(self.dims)
+        ws["wg_ws"], ws["wg_bytes"] = torch.empty(wg, dtype=torch.uint8, device=dev), wg
+        ws["dwg_ws"], ws["dwg_bytes"] = torch.empty(max(dwg, 256), dtype=torch.uint8, device=dev), dwg
+        dmax = max(self.dims)
         ws["ln_bytes"] = max(lib.icamd_layernorm_bwd_workspace_bytes(max_rows, c) for c in self.dims)
         ws["ln_ws"] = torch.zeros(ws["ln_bytes"], dtype=torch.uint8, device=dev)
-        ws["cs_bytes"] = max(lib.icamd_colsum_rows_workspace_bytes(max_rows, min(maxc, 4096)),
-                             lib.icamd_layerscale_bwd_workspace_bytes(max_rows, max(self.dims)))
+        ws["cs_bytes"] = max(lib.icamd_colsum_rows_workspace_bytes(max_rows, min(4 * dmax, 4096)),
+                             lib.icamd_layerscale_bwd_workspace_bytes(max_rows, dmax))
         ws["cs_ws"] = torch.zeros(ws["cs_bytes"], dtype=torch.uint8, device=dev)
-        ws["max_act"] = max_act
         if self.grn:
-            ws["grn_bytes"] = grn
-            ws["grn_ws"] = torch.empty(max(grn, 256), dtype=torch.uint8, device=dev)
-            ws["ls_dg"] = f32(max(self.dims))     # the gradient of the constant `ones`: discarded
+            ws["grn_ws"], ws["grn_bytes"] = torch.empty(max(grn, 256), dtype=torch.uint8, device=dev), grn
+            # Backward.drop_path's names: the column-sum workspace, and the gradient of the constant `ones` (discarded)
+            ws["ls_ws"], ws["ls_bytes"], ws["ls_dg"] = ws["cs_ws"], ws["cs_bytes"], f32(dmax)
             # a dropped block's masked output gradient; a buffer of its own, so that fc2's weight gradient (side lane) can read it
             # while the main stream goes on through G[1]
             ws["d2"] = act(max_act // 4)
         if self.fused_ls:     # side-lane scratch of the folded layer's parameter gradients
-            dmax = max(self.dims)
-            ws["ls_G"] = f32(4 * dmax * dmax)
-            ws["ls_S"] = f32(dmax)
-            ws["ls_drop"] = f32(N * dmax)
+            ws.update(ls_G=f32(4 * dmax * dmax), ls_S=f32(dmax), ls_drop=f32(N * dmax))
         self._ws[key] = ws
         return ws
 
@@ -304,73 +289,81 @@ class ConvNeXt(ArenaModel):
         """logits_only: a forward whose activations no backward will read (the reference's second, accuracy-only forward under
         mixup): tensors kept only for the backward pass (the pre-GELU Mlp activations) are not written."""
         f = Forward(self, ws, LN_EPS, logits_only)
-        lib, s = self.lib, f.s
-        N, H, W = ws["N"], ws["H"], ws["W"]
-        f.linear(self.stem, self.stem.desc(N, H, W), ws["x8"].data_ptr(), ws["s"].data_ptr())
-        h, w = H // 4, W // 4
+        N, (h, w) = ws["N"], ws["stages"][0]["hw"]
+        f.linear(self.stem, self.stem.desc(N, ws["H"], ws["W"]), ws["x8"].data_ptr(), ws["s"].data_ptr())
         f.layernorm(ws["s"].data_ptr(), self.stem_nw, self.stem_nb, ws["x0"].data_ptr(), ws["st_stem"].data_ptr(), N * h * w,
                     self.dims[0])
-        x = ws["x0"]
-        bi = 0
-        drop_rows = None      # stochastic depth: every block's mask for this step
-        if self.training and self.injected_keep is None:
-            drop_rows = self._draw_keep(ws, [blk["rate"] for st in self.stages for blk in st["blocks"]], N)
+        x, keeps = ws["x0"], self._keeps(ws)
         if self.fused_ls and self._ls_cbs != self._ls_mode_cbs():
             self.refresh_transposed()     # train() <-> eval(), or a test's injected masks: fold with this mode's constants
-        for si, (st, sw) in enumerate(zip(self.stages, ws["stages"])):
-            dim = st["dim"]
-            if si > 0:
-                sw["in"] = x
-                f.layernorm(x.data_ptr(), st["ds_nw"], st["ds_nb"], sw["ln"].data_ptr(), sw["st"].data_ptr(), N * h * w,
-                            self.dims[si - 1])
-                f.linear(st["ds"], st["ds"].desc(N, h, w), sw["ln"].data_ptr(), sw["x"].data_ptr())
-                h, w = h // 2, w // 2
-                x = sw["x"]
-            rows = N * h * w
+        for st, sw in zip(self.stages, ws["stages"]):
+            if "ds" in st:
+                x = self._downsample_fwd(f, st, sw, x)
             for blk, b in zip(st["blocks"], sw["blocks"]):
-                b["in"] = x
-                hip.check(lib.icamd_dwconv7_fwd(x.data_ptr(), self.shadow.data_ptr() + 2 * blk["dw_w"].offset,
-                                                self._pf(blk["dw_b"]), b["d"].data_ptr(), N, h, w, dim, s), blk["name"] + " dw")
-                f.layernorm(b["d"].data_ptr(), blk["nw"], blk["nb"], b["h"].data_ptr(), b["st"].data_ptr(), rows, dim)
-                # z1 = pwconv1(h), a = gelu(z1): one kernel
-                f.linear_gelu(blk["fc1"], blk["fc1"].desc(N, h, w), b["h"].data_ptr(), b["z1"].data_ptr(), b["a"].data_ptr())
-                keep = None
-                if self.training and blk["rate"] > 0.0:
-                    if self.injected_keep is not None:
-                        keep = self.injected_keep[bi].to(self.device, dtype=torch.float32)
-                    else:
-                        keep = drop_rows[bi]
-                b["keep"] = keep
-                if self.grn:
-                    c2 = blk["fc2"]
-                    hip.check(lib.icamd_grn_fwd(b["a"].data_ptr(), self._pf(blk["grn_w"]), self._pf(blk["grn_b"]), b["g"].data_ptr(),
-                                                b["gx"].data_ptr(), N, h * w, 4 * dim, GRN_EPS, ws["grn_ws"].data_ptr(),
-                                                ws["grn_bytes"], s), blk["name"] + " grn")
-                    if keep is None:     # out = x + fc2(g) in fc2's store pass
-                        f.linear(c2, c2.desc(N, h, w), b["g"].data_ptr(), b["out"].data_ptr(), x.data_ptr())
-                    else:                # out = x + keep * fc2(g)
-                        f.linear(c2, c2.desc(N, h, w), b["g"].data_ptr(), b["z2"].data_ptr())
-                        hip.check(lib.icamd_layerscale_fwd(b["z2"].data_ptr(), x.data_ptr(), self.ones.data_ptr(), keep.data_ptr(),
-                                                           b["out"].data_ptr(), rows, dim, h * w, s), "drop path")
-                elif self.fused_ls:
-                    # out = x + a W2'^T + b2' in fc2's store pass; the dropped samples: out = x, and their rows of `a` are cleared
-                    # so that they vanish from fc2's weight gradient (which then runs on the unmasked output gradient)
-                    c2 = blk["fc2"]
-                    hip.check(lib.icamd_conv2d_fwd(ctypes.byref(c2.desc(N, h, w)), b["a"].data_ptr(), self._w(c2),
-                                                   b["out"].data_ptr(), self.fold_bias.data_ptr() + 4 * blk["fb_off"],
-                                                   x.data_ptr(), None, s), c2.name + " + layer scale + residual")
-                    if keep is not None:
-                        hip.check(lib.icamd_rows_fix(keep.data_ptr(), N, b["out"].data_ptr(), x.data_ptr(), h * w * dim * 2,
-                                                     None if logits_only else b["a"].data_ptr(), h * w * dim * 8, s), "drop path")
-                else:
-                    f.linear(blk["fc2"], blk["fc2"].desc(N, h, w), b["a"].data_ptr(), b["z2"].data_ptr())
-                    hip.check(lib.icamd_layerscale_fwd(b["z2"].data_ptr(), x.data_ptr(), self._pf(blk["gamma"]),
-                                                       None if keep is None else keep.data_ptr(), b["out"].data_ptr(), rows, dim,
-                                                       h * w, s), "layer scale")
-                x = b["out"]
-                bi += 1
-        dl = self.dims[-1]
-        hip.check(lib.icamd_avgpool_fwd(x.data_ptr(), ws["pool"].data_ptr(), N, h * w, dl, s), "avgpool")
+                x = self._block_fwd(f, blk, b, x, keeps[blk["index"]], *sw["hw"])
+        return self._head_fwd(f, x)
+
+    def _keeps(self, ws):
+        """Stochastic depth: this step's mask per block (float [N], 0 or 1 / keep_prob) -- the injected one or a row of one draw for
+        all blocks; None for a block whose rate is 0, and for every block in eval."""
+        if not self.training:
+            return [None] * len(self.blocks)
+        if self.injected_keep is not None:
+            return [k.to(self.device, dtype=torch.float32) if blk["rate"] > 0.0 else None
+                    for blk, k in zip(self.blocks, self.injected_keep)]
+        rows = self._draw_keep(ws, [blk["rate"] for blk in self.blocks], ws["N"])
+        return [rows[blk["index"]] if blk["rate"] > 0.0 else None for blk in self.blocks]
+
+    def _downsample_fwd(self, f, st, sw, x):
+        N, (h, w) = f.ws["N"], sw["in_hw"]
+        sw["in"] = x
+        f.layernorm(x.data_ptr(), st["ds_nw"], st["ds_nb"], sw["ln"].data_ptr(), sw["st"].data_ptr(), N * h * w, st["ds"].cin)
+        f.linear(st["ds"], st["ds"].desc(N, h, w), sw["ln"].data_ptr(), sw["x"].data_ptr())
+        return sw["x"]
+
+    def _block_fwd(self, f, blk, b, x, keep, h, w):
+        """dw -> LN -> fc1 + GELU (z1, a) -> tail; returns the block's output b["out"]"""
+        N, dim = f.ws["N"], blk["dim"]
+        b["in"], b["keep"] = x, keep
+        hip.check(self.lib.icamd_dwconv7_fwd(x.data_ptr(), self.shadow.data_ptr() + 2 * blk["dw_w"].offset, self._pf(blk["dw_b"]),
+                                             b["d"].data_ptr(), N, h, w, dim, f.s), blk["name"] + " dw")
+        f.layernorm(b["d"].data_ptr(), blk["nw"], blk["nb"], b["h"].data_ptr(), b["st"].data_ptr(), N * h * w, dim)
+        f.linear_gelu(blk["fc1"], blk["fc1"].desc(N, h, w), b["h"].data_ptr(), b["z1"].data_ptr(), b["a"].data_ptr())
+        self._tail_fwd(f, blk, b, x, keep, h, w)
+        return b["out"]
+
+    def _v2_fwd(self, f, blk, b, x, keep, h, w):
+        """g = GRN(a); out = x + keep * fc2(g) -- not dropped: the residual in fc2's store pass"""
+        N, dim, c2, ws = f.ws["N"], blk["dim"], blk["fc2"], f.ws
+        hip.check(self.lib.icamd_grn_fwd(b["a"].data_ptr(), self._pf(blk["grn_w"]), self._pf(blk["grn_b"]), b["g"].data_ptr(),
+                                         b["gx"].data_ptr(), N, h * w, 4 * dim, GRN_EPS, ws["grn_ws"].data_ptr(), ws["grn_bytes"],
+                                         f.s), blk["name"] + " grn")
+        f.residual(c2, c2.desc(N, h, w), b["g"].data_ptr(), x.data_ptr(), b["out"].data_ptr(), keep, b["z2"].data_ptr(), N * h * w,
+                   dim, h * w)
+
+    def _folded_fwd(self, f, blk, b, x, keep, h, w):
+        """out = x + a W2'^T + b2' in fc2's store pass; the dropped samples: out = x, and their rows of `a` are cleared so that
+        they vanish from fc2's weight gradient (which then runs on the unmasked output gradient)"""
+        N, dim, c2 = f.ws["N"], blk["dim"], blk["fc2"]
+        hip.check(self.lib.icamd_conv2d_fwd(ctypes.byref(c2.desc(N, h, w)), b["a"].data_ptr(), self._w(c2), b["out"].data_ptr(),
+                                            self.fold_bias.data_ptr() + 4 * blk["fb_off"], x.data_ptr(), None, f.s),
+                  c2.name + " + layer scale + residual")
+        if keep is not None:
+            hip.check(self.lib.icamd_rows_fix(keep.data_ptr(), N, b["out"].data_ptr(), x.data_ptr(), h * w * dim * 2,
+                                              None if f.logits_only else b["a"].data_ptr(), h * w * dim * 8, f.s), "drop path")
+
+    def _unfolded_fwd(self, f, blk, b, x, keep, h, w):
+        """z2 = fc2(a); out = x + keep * gamma * z2"""
+        N, dim = f.ws["N"], blk["dim"]
+        f.linear(blk["fc2"], blk["fc2"].desc(N, h, w), b["a"].data_ptr(), b["z2"].data_ptr())
+        hip.check(self.lib.icamd_layerscale_fwd(b["z2"].data_ptr(), x.data_ptr(), self._pf(blk["gamma"]),
+                                                None if keep is None else keep.data_ptr(), b["out"].data_ptr(), N * h * w, dim,
+                                                h * w, f.s), "layer scale")
+
+    def _head_fwd(self, f, x):
+        ws, dl = f.ws, self.dims[-1]
+        N, (h, w) = ws["N"], ws["final_hw"]
+        hip.check(self.lib.icamd_avgpool_fwd(x.data_ptr(), ws["pool"].data_ptr(), N, h * w, dl, f.s), "avgpool")
         f.layernorm(ws["pool"].data_ptr(), self.head_nw, self.head_nb, ws["pn"].data_ptr(), ws["st_head"].data_ptr(), N, dl)
         f.linear(self.head, self.head.desc(N, 1, 1), ws["pn"].data_ptr(), ws["logits"].data_ptr())
         return ws["logits"]
@@ -379,104 +372,32 @@ class ConvNeXt(ArenaModel):
     def backward_packed(self, ws, accumulate=False, dfeat=None):
         """Backward from ws['dlogits'].  `dfeat` (bf16 NHWC tensor shaped like the last stage's output): start from that
         gradient instead and skip the classification head -- the entry the reference-vector parity test uses, since the
-        reference tree's ConvNeXt is the headless backbone."""
+        reference tree's ConvNeXt is the headless backbone.  G: the scratch pointers -- the gradient of a block's output and of its
+        input alternate between G[0] and G[3] (`dout`, `other`); within a block G[4] = d z1, G[1] = d h, G[2] = d (dwconv out)."""
         lane = side_lane(self, "ICAMD_WGRAD_STREAM", True)
         bw = Backward(self, ws, lane, accumulate)
-        lib, s, acc, W = self.lib, bw.s, bw.acc, bw.writes
-        N = ws["N"]
         hook = self.grad_ready_hook
-        wsp, wsb = bw.wg
-        dwp, dwb = ws["dwg_ws"].data_ptr(), ws["dwg_bytes"]
-        csp, csb = ws["cs_ws"].data_ptr(), ws["cs_bytes"]
         G = [g.data_ptr() for g in self._scratch(ws)]
-        dl = self.dims[-1]
-        h, w = ws["final_hw"]
-        dout = G[0]
+        dout, other = G[0], G[3]
         if dfeat is None:
-            bw.gemm(self.head, self.head.desc(N, 1, 1), ws["pn"].data_ptr(), ws["dlogits"].data_ptr(), G[1])
-            bw.layernorm(G[1], ws["pool"].data_ptr(), ws["st_head"].data_ptr(), self.head_nw, self.head_nb, None, G[2], N, dl)
-            hip.check(lib.icamd_avgpool_bwd(G[2], W(dout), N, h * w, dl, s), "avgpool bwd")
+            self._head_bwd(bw, G, dout)
         else:
-            assert dfeat.dtype == torch.bfloat16 and dfeat.numel() == N * h * w * dl
+            assert dfeat.dtype == torch.bfloat16 and dfeat.numel() == ws["stages"][-1]["blocks"][-1]["out"].numel()
             self._scratch(ws)[0][: dfeat.numel()].copy_(dfeat.reshape(-1))
         if hook:
             hook(self.head_nw.offset, self.n_params, lane.events())
-        other = G[3]
-        nblocks, bj = sum(self.depths), 0     # bj: blocks done, counted from the last one
-        for si in range(len(self.stages) - 1, -1, -1):
-            st, sw = self.stages[si], ws["stages"][si]
-            dim = st["dim"]
-            rows = N * h * w
+        for st, sw in zip(reversed(self.stages), reversed(ws["stages"])):
             for blk, b in zip(reversed(st["blocks"]), reversed(sw["blocks"])):
-                keep = None if b["keep"] is None else b["keep"].data_ptr()
-                if self.grn:
-                    d2 = dout     # gradient of fc2's output: the block's output gradient, masked where the branch was dropped
-                    if keep is not None:
-                        d2 = ws["d2"].data_ptr()
-                        hip.check(lib.icamd_layerscale_bwd(dout, dout, self.ones.data_ptr(), keep, W(d2), ws["ls_dg"].data_ptr(),
-                                                           rows, dim, h * w, 0, csp, csb, s), "drop path bwd")
-                    bw.gemm(blk["fc2"], blk["fc2"].desc(N, h, w), b["g"].data_ptr(), d2, G[5])                        # G5 = d g
-                    hip.check(lib.icamd_grn_bwd(G[5], b["a"].data_ptr(), b["gx"].data_ptr(), self._pf(blk["grn_w"]),
-                                                b["z1"].data_ptr(), W(G[4]), self._gf(blk["grn_w"]), self._gf(blk["grn_b"]), acc, N,
-                                                h * w, 4 * dim, GRN_EPS, ws["grn_ws"].data_ptr(), ws["grn_bytes"], s),
-                              blk["name"] + " grn bwd + gelu bwd")                                                  # G4 = d z1
-                elif self.fused_ls:
-                    # fc2 with the layer scale folded in: its data gradient reads the block's output gradient itself (the folded,
-                    # transposed filter carries cb * gamma); the side lane forms G = dout^T a and the column sums of dout over the
-                    # kept samples, and from them the gradients of W2, b2 and gamma (icamd_layerscale_param_grads)
-                    c2, gam = blk["fc2"], blk["gamma"]
-                    d2 = c2.desc(N, h, w)
-                    cb = self._ls_cbs[nblocks - 1 - bj]
-                    lsG, lsS, lsD = ws["ls_G"].data_ptr(), ws["ls_S"].data_ptr(), ws["ls_drop"].data_ptr()
-
-                    def side(st_, d2=d2, c2=c2, gam=gam, cb=cb, keep=keep, a_ptr=b["a"].data_ptr(), dout=dout, hw=h * w, dim=dim):
-                        if keep is not None:
-                            hip.check(lib.icamd_dropped_colsum(dout, keep, N, hw, dim, lsD, st_), "dropped column sums")
-                        hip.check(lib.icamd_conv2d_wgrad_bias(ctypes.byref(d2), a_ptr, dout, lsG, lsS, 0, wsp, wsb, st_),
-                                  c2.name + " wgrad+bias (folded)")
-                        hip.check(lib.icamd_layerscale_param_grads(lsG, self._pf(c2.w), self._pf(c2.b), self._pf(gam), lsS,
-                                                                   None if keep is None else lsD, N, cb, c2.cout, c2.cin,
-                                                                   self._gf(c2.w), self._gf(c2.b), self._gf(gam), acc, st_),
-                                  "layer scale parameter gradients")
-                    lane.launch(side, reads=(dout,))
-                    hip.check(lib.icamd_conv2d_dgrad_gelu(ctypes.byref(d2), dout, self._wt(c2), b["z1"].data_ptr(), W(G[4]), s),
-                              c2.name + " dgrad + gelu bwd (folded)")
-                    if keep is not None:
-                        hip.check(lib.icamd_rows_fix(keep, N, G[4], None, h * w * dim * 8, None, 0, s), "drop path bwd")
-                    bj += 1
-                else:
-                    hip.check(lib.icamd_layerscale_bwd(dout, b["z2"].data_ptr(), self._pf(blk["gamma"]), keep, W(G[1]),
-                                                       self._gf(blk["gamma"]), rows, dim, h * w, acc, csp, csb, s), "layer scale bwd")
-                    bw.gemm(blk["fc2"], blk["fc2"].desc(N, h, w), b["a"].data_ptr(), G[1], G[4], gelu_z=b["z1"].data_ptr())   # G4 = d z1
-                bw.gemm(blk["fc1"], blk["fc1"].desc(N, h, w), b["h"].data_ptr(), G[4], G[1])                         # G1 = d h
-                # G2 = d (dwconv out)
-                bw.layernorm(G[1], b["d"].data_ptr(), b["st"].data_ptr(), blk["nw"], blk["nb"], None, G[2], rows, dim)
-                bin_ptr, g2, hh, ww_, dd = b["in"].data_ptr(), G[2], h, w, dim
-                dwg = self._gf(blk["dw_w"])
-                if lib.icamd_dwconv7_wgrad_bias_supported(N, hh, ww_, dd):   # filter and bias gradient out of one pass over dy
-                    dbg = self._gf(blk["dw_b"])
-                    lane.launch(lambda st_, bin_ptr=bin_ptr, g2=g2, hh=hh, ww_=ww_, dd=dd, dwg=dwg, dbg=dbg, nm=blk["name"]: hip.check(
-                        lib.icamd_dwconv7_wgrad_bias(bin_ptr, g2, dwg, dbg, acc, dwp, dwb, N, hh, ww_, dd, st_), nm + " dw wgrad+bias"),
-                        reads=(G[2],))
-                else:
-                    lane.launch(lambda st_, bin_ptr=bin_ptr, g2=g2, hh=hh, ww_=ww_, dd=dd, dwg=dwg, nm=blk["name"]: hip.check(
-                        lib.icamd_dwconv7_wgrad(bin_ptr, g2, dwg, acc, dwp, dwb, N, hh, ww_, dd, st_), nm + " dw wgrad"),
-                        reads=(G[2],))
-                    hip.check(lib.icamd_colsum_rows(G[2], rows, dim, dim, self._gf(blk["dw_b"]), acc, csp, csb, s), "dw bias grad")
-                hip.check(lib.icamd_dwconv7_dgrad(G[2], self.shadow.data_ptr() + 2 * blk["dw_w"].offset, dout, W(other), N, h, w,
-                                                  dim, s), blk["name"] + " dw dgrad")        # + residual gradient
+                self._block_bwd(bw, blk, b, G, dout, other, *sw["hw"])
                 dout, other = other, dout
                 if hook:
                     hook(blk["dw_w"].offset, None, lane.events())
-            if si > 0:
-                prev = self.dims[si - 1]
-                bw.gemm(st["ds"], st["ds"].desc(N, 2 * h, 2 * w), sw["ln"].data_ptr(), dout, G[1])
-                h, w = 2 * h, 2 * w
-                bw.layernorm(G[1], sw["in"].data_ptr(), sw["st"].data_ptr(), st["ds_nw"], st["ds_nb"], None, other, N * h * w,
-                             prev)
+            if "ds" in st:
+                self._downsample_bwd(bw, st, sw, G, dout, other)
                 dout, other = other, dout
                 if hook:
                     hook(st["ds_nw"].offset, None, lane.events())
+        N, (h, w) = ws["N"], ws["stages"][0]["hw"]
         bw.layernorm(dout, ws["s"].data_ptr(), ws["st_stem"].data_ptr(), self.stem_nw, self.stem_nb, None, G[1], N * h * w,
                      self.dims[0])
         bw.gemm(self.stem, self.stem.desc(N, ws["H"], ws["W"]), ws["x8"].data_ptr(), G[1], None)
@@ -484,3 +405,81 @@ class ConvNeXt(ArenaModel):
         if hook:
             hook(0, None)
 
+    def _head_bwd(self, bw, G, dout):
+        ws, dl = bw.ws, self.dims[-1]
+        N, (h, w) = ws["N"], ws["final_hw"]
+        bw.gemm(self.head, self.head.desc(N, 1, 1), ws["pn"].data_ptr(), ws["dlogits"].data_ptr(), G[1])
+        bw.layernorm(G[1], ws["pool"].data_ptr(), ws["st_head"].data_ptr(), self.head_nw, self.head_nb, None, G[2], N, dl)
+        hip.check(self.lib.icamd_avgpool_bwd(G[2], bw.writes(dout), N, h * w, dl, bw.s), "avgpool bwd")
+
+    def _downsample_bwd(self, bw, st, sw, G, dout, dx):
+        N, (h, w) = bw.ws["N"], sw["in_hw"]
+        bw.gemm(st["ds"], st["ds"].desc(N, h, w), sw["ln"].data_ptr(), dout, G[1])
+        bw.layernorm(G[1], sw["in"].data_ptr(), sw["st"].data_ptr(), st["ds_nw"], st["ds_nb"], None, dx, N * h * w, st["ds"].cin)
+
+    def _block_bwd(self, bw, blk, b, G, dout, dx, h, w):
+        """dout: the gradient of the block's output; dx receives that of its input (pointers)"""
+        N, dim = bw.ws["N"], blk["dim"]
+        self._tail_bwd(bw, blk, b, dout, b["keep"], G, h, w)                                                 # G4 = d z1
+        bw.gemm(blk["fc1"], blk["fc1"].desc(N, h, w), b["h"].data_ptr(), G[4], G[1])                         # G1 = d h
+        bw.layernorm(G[1], b["d"].data_ptr(), b["st"].data_ptr(), blk["nw"], blk["nb"], None, G[2], N * h * w, dim)
+        self._dw_bwd(bw, blk, b, G[2], dout, dx, h, w)
+
+    def _v2_bwd(self, bw, blk, b, dout, keep, G, h, w):
+        """fc2 from the block's output gradient (masked into a buffer of its own where the branch was dropped), then GRN's backward,
+        which also applies gelu'(z1)"""
+        N, dim, ws = bw.ws["N"], blk["dim"], bw.ws
+        d2 = dout if keep is None else bw.drop_path(dout, keep, ws["d2"].data_ptr(), N * h * w, dim, h * w)
+        bw.gemm(blk["fc2"], blk["fc2"].desc(N, h, w), b["g"].data_ptr(), d2, G[5])                           # G5 = d g
+        hip.check(self.lib.icamd_grn_bwd(G[5], b["a"].data_ptr(), b["gx"].data_ptr(), self._pf(blk["grn_w"]), b["z1"].data_ptr(),
+                                         bw.writes(G[4]), self._gf(blk["grn_w"]), self._gf(blk["grn_b"]), bw.acc, N, h * w, 4 * dim,
+                                         GRN_EPS, ws["grn_ws"].data_ptr(), ws["grn_bytes"], bw.s), blk["name"] + " grn bwd + gelu bwd")
+
+    def _folded_bwd(self, bw, blk, b, dout, keep, G, h, w):
+        """fc2 with the layer scale folded in: its data gradient reads the block's output gradient itself (the folded, transposed
+        filter carries cb * gamma); the side lane forms G = dout^T a and the column sums of dout over the kept samples, and from
+        them the gradients of W2, b2 and gamma (icamd_layerscale_param_grads)"""
+        lib, ws, N, dim, c2, gam = self.lib, bw.ws, bw.ws["N"], blk["dim"], blk["fc2"], blk["gamma"]
+        d2, cb, keep = ctypes.byref(c2.desc(N, h, w)), self._ls_cbs[blk["index"]], None if keep is None else keep.data_ptr()
+        lsG, lsS, lsD = ws["ls_G"].data_ptr(), ws["ls_S"].data_ptr(), ws["ls_drop"].data_ptr()
+
+        def side(st):
+            if keep is not None:
+                hip.check(lib.icamd_dropped_colsum(dout, keep, N, h * w, dim, lsD, st), "dropped column sums")
+            hip.check(lib.icamd_conv2d_wgrad_bias(d2, b["a"].data_ptr(), dout, lsG, lsS, 0, *bw.wg, st), c2.name + " wgrad+bias (folded)")
+            hip.check(lib.icamd_layerscale_param_grads(lsG, self._pf(c2.w), self._pf(c2.b), self._pf(gam), lsS,
+                                                       None if keep is None else lsD, N, cb, c2.cout, c2.cin, self._gf(c2.w),
+                                                       self._gf(c2.b), self._gf(gam), bw.acc, st), "layer scale parameter gradients")
+        bw.lane.launch(side, reads=(dout,))
+        hip.check(lib.icamd_conv2d_dgrad_gelu(d2, dout, self._wt(c2), b["z1"].data_ptr(), bw.writes(G[4]), bw.s),
+                  c2.name + " dgrad + gelu bwd (folded)")
+        if keep is not None:
+            hip.check(lib.icamd_rows_fix(keep, N, G[4], None, h * w * dim * 8, None, 0, bw.s), "drop path bwd")
+
+    def _unfolded_bwd(self, bw, blk, b, dout, keep, G, h, w):
+        """G1 = d z2 = keep * gamma * dout (and gamma's gradient), then fc2 with the GELU backward in its data gradient"""
+        N, dim, ws = bw.ws["N"], blk["dim"], bw.ws
+        hip.check(self.lib.icamd_layerscale_bwd(dout, b["z2"].data_ptr(), self._pf(blk["gamma"]), None if keep is None else keep.data_ptr(),
+                                                bw.writes(G[1]), self._gf(blk["gamma"]), N * h * w, dim, h * w, bw.acc,
+                                                ws["cs_ws"].data_ptr(), ws["cs_bytes"], bw.s), "layer scale bwd")
+        bw.gemm(blk["fc2"], blk["fc2"].desc(N, h, w), b["a"].data_ptr(), G[1], G[4], gelu_z=b["z1"].data_ptr())
+
+    def _dw_bwd(self, bw, blk, b, dy, dout, dx, h, w):
+        """The depthwise convolution from dy = d (its output): filter and bias gradient on the side lane -- out of one pass over dy
+        where the shape has that kernel, else the filter there and the bias as column sums on the main stream --, then
+        dx = dgrad(dy) + dout, the residual's gradient"""
+        lib, ws, N, dim, acc = self.lib, bw.ws, bw.ws["N"], blk["dim"], bw.acc
+        x_ptr, dw, db = b["in"].data_ptr(), self._gf(blk["dw_w"]), self._gf(blk["dw_b"])
+        wsp, wsb = ws["dwg_ws"].data_ptr(), ws["dwg_bytes"]
+        one_pass = lib.icamd_dwconv7_wgrad_bias_supported(N, h, w, dim)
+
+        def side(st):
+            if one_pass:
+                hip.check(lib.icamd_dwconv7_wgrad_bias(x_ptr, dy, dw, db, acc, wsp, wsb, N, h, w, dim, st), blk["name"] + " dw wgrad+bias")
+            else:
+                hip.check(lib.icamd_dwconv7_wgrad(x_ptr, dy, dw, acc, wsp, wsb, N, h, w, dim, st), blk["name"] + " dw wgrad")
+        bw.lane.launch(side, reads=(dy,))
+        if not one_pass:
+            hip.check(lib.icamd_colsum_rows(dy, N * h * w, dim, dim, db, acc, ws["cs_ws"].data_ptr(), ws["cs_bytes"], bw.s), "dw bias grad")
+        hip.check(lib.icamd_dwconv7_dgrad(dy, self.shadow.data_ptr() + 2 * blk["dw_w"].offset, dout, bw.writes(dx), N, h, w, dim,
+                                          bw.s), blk["name"] + " dw dgrad")

@@ -6,15 +6,16 @@ To see what moved when the test fails, write the records themselves at both comm
     python tests/golden/make_call_traces.py --dump DIR
 
 The models run on the CPU under make_arena_layouts.install_stubs plus three more replacements (`install_recorders`): the library
-records (entry, arguments) and returns 0 (a ResNet case carries a table of other answers for the queries, `Case.answers`),
+records (entry, arguments) and returns 0 (a ResNet or routed ConvNeXt case carries a table of other answers for the queries, `Case.answers`),
 torch.cuda.current_stream is a stand-in whose stream is 0, and streams.SideLane is a
 lane of the same interface that runs a launch with stream 1 when it is enabled (0 otherwise) and leaves a record for every
 before_write that meets a pending read and for every join.  grad_ready_hook records (lo, hi, events).  A case is: construct at
 seed 0, train(), pack, forward_packed, backward_packed, backward_packed(accumulate=True), eval(), forward_packed(logits_only=True)
-(a ResNet case: twice, the second one with the BatchNorm fold already done), load_state_dict(state_dict()).  PHASES keeps where each
+(a ResNet case: twice, the second one with the BatchNorm fold already done), load_state_dict(state_dict()); a case with `dfeat`
+(the ConvNeXt ones added with the block walk) also runs backward_packed(dfeat=zeros) after the accumulating backward.  PHASES keeps where each
 phase starts in TRACE.
 
-Arguments are written by their type in hip._SIGNATURES: a descriptor as its key(), a float as its repr, the last pointer as the
+Arguments are written by their type in hip._SIGNATURES / _SIGNATURES_ADDED: a descriptor as its key(), a float as its repr, the last pointer as the
 stream id, any other pointer as [number of its buffer in order of first use, byte offset, bytes of the buffer] -- looked up
 among all tensors reachable from the model (collected after every phase and kept alive, so that an address is never used twice),
 "input" for the image batch, None for NULL; a byref(BnBwdFuse) as the list of its fields, pointers in the same form.  No attribute or dictionary name enters the record; a pointer into no buffer is an
@@ -51,6 +52,7 @@ MODELS = {
     "swin_test": ("swin", "SwinTransformer", {"arch": "swin_test", "img_size": 56}, 56),
     "swin_test_w12": ("swin", "SwinTransformer", {"arch": "swin_test_w12", "img_size": 96}, 96),
     "convnext_test": ("convnext", "ConvNeXt", {"arch": "convnext_test"}, 64),
+    "convnextv2_test": ("convnext", "ConvNeXt", {"arch": "convnextv2_test"}, 64),
 }
 RESNETS = ("resnet50", "resnet18", "resnext50_32x4d", "seresnet50", "resnet50d", "resnet18d", "seresnext26d_32x4d")
 MODELS.update({arch: ("nets", "ResNet", {"arch": arch}, 64) for arch in RESNETS})
@@ -58,11 +60,13 @@ MODELS.update({arch: ("nets", "ResNet", {"arch": arch}, 64) for arch in RESNETS}
 STATE_MODELS = ("vit_tiny_test", "swin_test", "swin_test_w12", "convnext_test", "resnet50", "seresnext26d_32x4d")
 
 # One case.  more: further constructor arguments; masks: drop-path masks per block (None: none injected); env: environment
-# (None: unset).  A ResNet case also has answers = (what a *_supported query returns, {entry: another answer}) -- with a table
-# every *_rows query returns 4 and every *_bytes query 256, so that the statistics and workspace buffers are real tensors; None:
-# every entry returns 0 --, switches: the import-time switches of nets.py, attrs: attributes set on the model, hw: the input's
-# height and width where it is not the model's square size.
-Case = collections.namedtuple("Case", "model more masks env answers switches attrs hw", defaults=({}, None, {}, None, {}, {}, None))
+# (None: unset).  A ResNet or routed ConvNeXt case also has answers = (what a *_supported query returns, {entry: another answer})
+# -- with a table every *_stats_rows query returns 4 and every *_bytes query 256, so that the statistics and workspace buffers are
+# real tensors; None: every entry returns 0 --, switches: import-time switches of the module `switch_module` (read when the model is
+# constructed or run), attrs: attributes set on the model, hw: the input's height and width where it is not the model's square
+# size, dfeat: one more phase after the accumulating backward, a backward from a gradient of the last stage's output.
+Case = collections.namedtuple("Case", "model more masks env answers switches attrs hw switch_module dfeat",
+                              defaults=({}, None, {}, None, {}, {}, None, "nets", False))
 RESNET_ENV = {"ICAMD_WGRAD_STREAM": None, "ICAMD_EVAL_FOLD": None}
 
 
@@ -75,6 +79,15 @@ def _resnet(arch, supported=1, by_entry=None, switches=None, **kw):
     return Case(arch, env=RESNET_ENV, answers=(supported, by_entry or {}), switches={**SWITCHES, **(switches or {})}, **kw)
 
 
+# every ConvNeXt case sets convnext.py's one switch, for the same reason; the model reads it when it is constructed
+def _convnext(model, drop, lane, supported=None, fused_ls=True):
+    """supported: what icamd_dwconv7_wgrad_bias_supported answers (None: the two cases recorded first, without an answers table
+    and without the dfeat phase)"""
+    return Case(model, {"drop_path_rate": drop}, 1 if drop > 0.0 else None, {CNX_ENV: None if lane else "0"},
+                answers=None if supported is None else (supported, {}), dfeat=supported is not None,
+                switches={"_FUSED_LS": fused_ls}, switch_module="convnext")
+
+
 CASES = {
     "vit_tiny_test/lane_off": Case("vit_tiny_test", env={VIT_ENV: None}),
     "vit_tiny_test/lane_on": Case("vit_tiny_test", env={VIT_ENV: "1"}),
@@ -82,8 +95,14 @@ CASES = {
     "swin_test/drop": Case("swin_test", {"drop_path_rate": DROP_PATH}, 2),
     "swin_test_w12/no_drop": Case("swin_test_w12", {"drop_path_rate": 0.0}),
     "swin_test_w12/drop": Case("swin_test_w12", {"drop_path_rate": DROP_PATH}, 2),
-    "convnext_test/lane_on": Case("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: None}),
-    "convnext_test/lane_off": Case("convnext_test", {"drop_path_rate": DROP_PATH}, 1, {CNX_ENV: "0"}),
+    "convnext_test/lane_on": _convnext("convnext_test", DROP_PATH, True),
+    "convnext_test/lane_off": _convnext("convnext_test", DROP_PATH, False),
+    "convnext_test/routed": _convnext("convnext_test", DROP_PATH, True, 1),
+    "convnext_test/routed_no_drop": _convnext("convnext_test", 0.0, True, 1),
+    "convnext_test/unfolded": _convnext("convnext_test", DROP_PATH, True, 0, fused_ls=False),
+    "convnext_test/unfolded_lane_off": _convnext("convnext_test", DROP_PATH, False, 0, fused_ls=False),
+    "convnextv2_test/drop": _convnext("convnextv2_test", DROP_PATH, True, 1),
+    "convnextv2_test/no_drop_lane_off": _convnext("convnextv2_test", 0.0, False, 0),
     "resnet50/routed": _resnet("resnet50"),
     "resnet50/plain_odd_width": _resnet("resnet50", 0, hw=(64, 63)),
     "resnet50/gy_partials": _resnet("resnet50", 0, {"icamd_conv2d_dgrad_bnred_supported": 1}),
@@ -113,13 +132,13 @@ class FuseFields(list):
 
 
 class RecordingLib:
-    """Stands in for libicamd.so: every entry of hip._SIGNATURES records its call and returns 0 -- or, for a query, what the
+    """Stands in for libicamd.so: every entry of hip._SIGNATURES and hip._SIGNATURES_ADDED records its call and returns 0 -- or, for a query, what the
     running case's `answers` say (Case); any other name is an error."""
     answers = None
 
     def __getattr__(self, name):
         from imageclassification_amd import hip
-        argtypes = hip._SIGNATURES[name][1]
+        argtypes = (hip._SIGNATURES.get(name) or hip._SIGNATURES_ADDED[name])[1]
 
         def by_value(a):      # byref(ConvDesc) -> the descriptor's fields, byref(BnBwdFuse) -> its fields, taken now
             d = getattr(a, "_obj", None)
@@ -134,7 +153,7 @@ class RecordingLib:
                 return 0
             if name.endswith("_supported"):
                 return self.answers[1].get(name, self.answers[0])
-            return 4 if name.endswith("_rows") else 256 if name.endswith("_bytes") else 0
+            return 4 if name.endswith("_stats_rows") else 256 if name.endswith("_bytes") else 0
         return entry
 
 
@@ -300,7 +319,7 @@ def canonical(trace, held, x):
 
 def run_case(case_id, setenv=None, dump=None, setattr_fn=None):
     """-> {"sha256", "calls", "stream_queries"} of one case, under install_recorders; dump: a file for the records, one per line.
-    setenv(name, value or None) changes the environment and setattr_fn(nets, switch, value) a switch of nets.py (a test passes
+    setenv(name, value or None) changes the environment and setattr_fn(module, switch, value) a switch of the case's module (a test passes
     functions that undo themselves); by default os.environ and setattr, restored at the end."""
     from imageclassification_amd import hip
     case = CASES[case_id]
@@ -314,7 +333,7 @@ def run_case(case_id, setenv=None, dump=None, setattr_fn=None):
         (setenv or default_setenv)(k, v)
     try:
         if case.switches:
-            nets = importlib.import_module("imageclassification_amd.nets")
+            nets = importlib.import_module("imageclassification_amd." + case.switch_module)
             for k, v in case.switches.items():
                 saved_switches[k] = getattr(nets, k)
                 (setattr_fn or setattr)(nets, k, v)
@@ -346,6 +365,9 @@ def run_case(case_id, setenv=None, dump=None, setattr_fn=None):
         phase("forward", lambda: model.forward_packed(ws))
         phase("backward", lambda: model.backward_packed(ws))
         phase("backward_accumulate", lambda: model.backward_packed(ws, accumulate=True))
+        if case.dfeat:
+            dfeat = torch.zeros(BATCH, *ws["final_hw"], model.dims[-1], dtype=torch.bfloat16)
+            phase("backward_dfeat", lambda: model.backward_packed(ws, dfeat=dfeat))
         phase("eval", model.eval)
         phase("eval_forward", lambda: model.forward_packed(ws, logits_only=True))
         if MODELS[case.model][0] == "nets":

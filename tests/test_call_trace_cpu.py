@@ -1,4 +1,4 @@
-"""The library calls of a ViT, Swin, ConvNeXt and ResNet (nets.py) training step, without a GPU: every launch of construct / pack / forward / backward /
+"""The library calls of a ViT, Swin, ConvNeXt (V1 folded and unfolded, V2) and ResNet (nets.py) training step, without a GPU: every launch of construct / pack / forward / backward /
 accumulating backward / eval forward (ResNet: twice) / reload -- entry, arguments, buffers, stream, order, side-lane waits and gradient-hook calls --
 is the recorded one (tests/golden/call_traces.json, written by tests/golden/make_call_traces.py, whose docstring states what a
 record holds), and a seed still gives the weights it gave.
@@ -129,6 +129,86 @@ def test_the_resnet_cases_call_every_entry_nets_names(resnet_calls):
         named = {n for n in re.findall(r"\bicamd_\w+", f.read()) if n in hip._SIGNATURES}
     called = set().union(*(c for c, _, _ in resnet_calls.values()))
     assert len(named) > 50 and sorted(named - called) == []
+
+
+FOLDED = ["icamd_layerscale_fold", "icamd_layerscale_param_grads", "icamd_conv2d_dgrad_gelu"]
+UNFOLDED = ["icamd_layerscale_fwd", "icamd_layerscale_bwd", "icamd_dwconv7_wgrad", "icamd_colsum_rows", "icamd_conv2d_dgrad_gelu"]
+V2 = ["icamd_grn_fwd", "icamd_grn_bwd", "icamd_conv2d_dgrad"]
+NOT_V2 = ["icamd_layerscale_fold", "icamd_layerscale_param_grads", "icamd_rows_fix", "icamd_dropped_colsum", "icamd_conv2d_dgrad_gelu"]
+# ConvNeXt case -> (entries it must call, entries it must not call)
+CONVNEXT_PATHS = {
+    "convnext_test/lane_on": (FOLDED + ["icamd_dwconv7_wgrad", "icamd_colsum_rows", "icamd_rows_fix", "icamd_dropped_colsum"],
+                              ["icamd_dwconv7_wgrad_bias", "icamd_layerscale_fwd", "icamd_layerscale_bwd", "icamd_grn_fwd"]),
+    "convnext_test/lane_off": (FOLDED + ["icamd_dwconv7_wgrad", "icamd_colsum_rows"], ["icamd_dwconv7_wgrad_bias", "lane.before_write"]),
+    "convnext_test/routed": (FOLDED + ["icamd_dwconv7_wgrad_bias", "icamd_dropped_colsum", "icamd_rows_fix", "lane.before_write"],
+                             ["icamd_dwconv7_wgrad", "icamd_colsum_rows", "icamd_layerscale_fwd", "icamd_layerscale_bwd", "icamd_grn_fwd"]),
+    "convnext_test/routed_no_drop": (FOLDED + ["icamd_dwconv7_wgrad_bias"],
+                                     ["icamd_rows_fix", "icamd_dropped_colsum", "icamd_dwconv7_wgrad", "icamd_colsum_rows"]),
+    "convnext_test/unfolded": (UNFOLDED + ["lane.before_write"],
+                               ["icamd_dwconv7_wgrad_bias", "icamd_layerscale_fold", "icamd_layerscale_param_grads", "icamd_rows_fix",
+                                "icamd_dropped_colsum"]),
+    "convnext_test/unfolded_lane_off": (UNFOLDED, ["icamd_dwconv7_wgrad_bias", "icamd_layerscale_fold", "lane.before_write"]),
+    "convnextv2_test/drop": (V2 + ["icamd_dwconv7_wgrad_bias", "icamd_layerscale_fwd", "icamd_layerscale_bwd", "lane.before_write"],
+                             NOT_V2 + ["icamd_dwconv7_wgrad", "icamd_colsum_rows"]),
+    "convnextv2_test/no_drop_lane_off": (V2 + ["icamd_dwconv7_wgrad", "icamd_colsum_rows"],
+                                         NOT_V2 + ["icamd_dwconv7_wgrad_bias", "icamd_layerscale_fwd", "icamd_layerscale_bwd",
+                                                   "lane.before_write"]),
+}
+HEAD_DESC = (G.BATCH, 1, 1, 192, 1, 1, 64, 1, 1, 1, 0)     # head.fc of both test models: 192 features, 10 classes padded to 64
+
+
+@pytest.fixture(scope="module")
+def convnext_calls(recorders):
+    """ConvNeXt case -> (the entries it calls, the streams of its launches, {phase: its records})"""
+    out = {}
+    for case_id in CONVNEXT_PATHS:
+        _run(recorders, case_id)
+        streams = {r[2][-1] for r in G.TRACE if r[0].startswith("icamd_") and not r[0].endswith(("_bytes", "_supported"))}
+        phases = {n: G.phase_records(n) for n, _ in G.PHASES if n.startswith("backward")}
+        out[case_id] = ({r[0] for r in G.TRACE}, streams, phases)
+    return out
+
+
+def test_convnext_cases_are_the_listed_ones():
+    assert set(CONVNEXT_PATHS) == {c for c in G.CASES if G.MODELS[G.CASES[c].model][0] == "convnext"}
+
+
+@pytest.mark.parametrize("case_id", list(CONVNEXT_PATHS))
+def test_the_convnext_cases_take_the_paths_they_are_there_for(convnext_calls, case_id):
+    called, streams, _ = convnext_calls[case_id]
+    must, must_not = CONVNEXT_PATHS[case_id]
+    assert [n for n in must if n not in called] == [] and [n for n in must_not if n in called] == []
+    assert streams == ({0} if case_id.endswith("lane_off") else {0, 1})
+
+
+def test_the_convnext_cases_call_every_entry_convnext_names(convnext_calls):
+    from imageclassification_amd import convnext, hip
+    with open(convnext.__file__) as f:
+        named = {n for n in re.findall(r"\bicamd_\w+", f.read()) if n in hip._SIGNATURES or n in hip._SIGNATURES_ADDED}
+    called = set().union(*(c for c, _, _ in convnext_calls.values()))
+    assert len(named) >= 20 and sorted(named - called) == []
+
+
+@pytest.mark.parametrize("case_id", [c for c in CONVNEXT_PATHS if G.CASES[c].dfeat])
+def test_a_backward_from_dfeat_skips_the_head_only(convnext_calls, case_id):
+    """No pooling backward and no weight gradient of head.fc; every block's depthwise data gradient, as in the backward from the
+    logits."""
+    _, _, phases = convnext_calls[case_id]
+    full, dfeat = phases["backward"], phases["backward_dfeat"]
+
+    def names(records):
+        return [r[0] for r in records]
+
+    def wgrad_descs(records):
+        return [r[2][0] for r in records if r[0] == "icamd_conv2d_wgrad_bias"]
+
+    assert "icamd_avgpool_bwd" in names(full) and "icamd_avgpool_bwd" not in names(dfeat)
+    assert wgrad_descs(full)[0] == HEAD_DESC and HEAD_DESC not in wgrad_descs(dfeat)
+    assert wgrad_descs(dfeat) == wgrad_descs(full)[1:]
+    dw = [r[2][4:8] for r in dfeat if r[0] == "icamd_dwconv7_dgrad"]          # (N, h, w, dim) of each, last block first
+    assert dw == [(G.BATCH, 2, 2, 192), (G.BATCH, 4, 4, 128), (G.BATCH, 4, 4, 128), (G.BATCH, 8, 8, 64), (G.BATCH, 16, 16, 32)]
+    assert dw == [r[2][4:8] for r in full if r[0] == "icamd_dwconv7_dgrad"]
+    assert names(dfeat)[-1] == "hook" and names(dfeat).count("lane.join") == 1
 
 
 @pytest.mark.parametrize("model_id", list(G.STATE_MODELS))

@@ -159,7 +159,6 @@ def test_library_calls_of_a_v2_step(monkeypatch):
     z1, fc1 and the rest as in V1.  Every pointer of every call lies in a tensor of the model."""
     from imageclassification_amd import hip
     T.install_recorders(monkeypatch.setattr)
-    monkeypatch.setattr(hip, "_SIGNATURES", {**hip._SIGNATURES, **hip._SIGNATURES_ADDED})     # the recorder reads argument types here
     monkeypatch.delenv("ICAMD_WGRAD_STREAM", raising=False)
     net = _build("convnextv2_test", drop_path_rate=0.2)
     hooks = []
