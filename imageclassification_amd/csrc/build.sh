@@ -14,7 +14,7 @@ REUSED=""
 for f in $UNITS; do
   # An object is reused only together with the device assembly it was built with: the ISA lint below reads that file, and an
   # object whose .s is missing (a build directory of an older tree, a deleted file) would otherwise be linked unlinted.
-  if [ ! -f build/$f.o ] || [ ! -f "$(asm_of $f)" ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ icamd_internal.h -nt build/$f.o ] || [ capi_common.h -nt build/$f.o ] || [ attention_common.h -nt build/$f.o ] || [ ../../include/icamd.h -nt build/$f.o ]; then
+  if [ ! -f build/$f.o ] || [ ! -f "$(asm_of $f)" ] || [ $f.hip -nt build/$f.o ] || [ common.h -nt build/$f.o ] || [ icamd_internal.h -nt build/$f.o ] || [ capi_common.h -nt build/$f.o ] || [ attention_common.h -nt build/$f.o ] || [ workspace.h -nt build/$f.o ] || [ ../../include/icamd.h -nt build/$f.o ]; then
     mkdir -p build
     rm -f build/$f.o "$(asm_of $f)"   # a failed compile must not leave a stale object (or its assembly) for the link step
     # -save-temps=obj leaves build/$f-hip-amdgcn-amd-amdhsa-gfx950.s next to the object: the device assembly tools/isa_lint.py reads

@@ -313,7 +313,7 @@ size_t icamd_conv2d_wgrad_workspace_bytes(const icamd_conv_desc* d) {
     icamd_wgrad_halo_plan((int)M, d->Cin, d->Cout, &S2, &rows);
     if (S2 > S) S = S2;
   }
-  return (size_t)S * d->Cout * ((size_t)Ktot + 1) * sizeof(float);   // filter slabs + one bias row per split
+  return wgrad_ws(nullptr, S, d->Cout, Ktot).bytes;   // filter slabs + one bias row per split
 }
 
 static int wgrad_impl(const icamd_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias, int accumulate,
@@ -351,7 +351,7 @@ static int wgrad_impl(const icamd_conv_desc* d, const void* x, const void* dy, f
     rc = icamd_wgrad_halo_launch(p, (hipStream_t)stream);
   } else {
     icamd_wgrad_plan(p.M, p.Cout, p.Ktot, &p.S, &p.rows_per_split);
-    if (dbias != nullptr) p.bias_slab = p.slab + (size_t)p.S * p.Cout * p.Ktot;
+    if (dbias != nullptr) p.bias_slab = wgrad_ws(workspace, p.S, p.Cout, p.Ktot).bias_slab;
     rc = icamd_wgrad_launch(p, (hipStream_t)stream);
   }
   if (rc) return rc;

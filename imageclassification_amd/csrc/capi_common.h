@@ -1,9 +1,10 @@
 // What the C-ABI units (capi.hip, capi_conv_special.hip, capi_norm.hip, capi_tokens.hip, capi_step.hip) share: the in-process
-// kernel timing scope, the convolution-descriptor check and the workspace-carving helpers.  Host code only.
+// kernel timing scope, the convolution-descriptor check and the workspace layouts (workspace.h).  Host code only.
 #pragma once
 #include "../../include/icamd.h"
 #include "common.h"
 #include "icamd_internal.h"
+#include "workspace.h"
 #include <cstdlib>
 #include <string.h>
 #include <vector>
@@ -54,8 +55,8 @@ static bool conv_desc_ok(const icamd_conv_desc* d) {
   return true;
 }
 
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// BN workspace: [64 chunks][2][C] doubles + ceil(C/64) arrival counters (uint32, must be zero before first use; self-resetting)
-// in the first 256 B.  The LayerNorm, column-sum and layer-scale reductions carve the same block.
-static size_t bn_chunk_bytes(int C) { return 256 + align_up((size_t)64 * 2 * C * sizeof(double), 256); }
+// partial rows of the BatchNorm backward's reduce pass: one per block of the plan
+static long long bn_bwd_blocks(long long rows, int C) {
+  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
+  return (rows + rpb - 1) / rpb;
+}

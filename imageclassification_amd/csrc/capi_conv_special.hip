@@ -305,25 +305,19 @@ int icamd_conv1x1_bn_bwd_fused(const icamd_conv_desc* d, const float* partials, 
   if (bn_workspace_bytes < (partials ? icamd_bn_bwd_apply_workspace_bytes(C) : icamd_bn_bwd_workspace_bytes(M, C)) ||
       wgrad_workspace_bytes < icamd_conv1x1_bn_bwd_fused_workspace_bytes(d))
     return ICAMD_ERR_WORKSPACE;
-  char* ws = (char*)bn_workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(C);
+  // the workspace of icamd_bn_bwd_from_gy_partials, or (no sums yet) of icamd_bn_bwd
+  const ReduceWs w = reduce_ws(bn_workspace, C, partials ? 0 : bn_bwd_blocks(M, C), 2);
+  float* c1c2 = w.scratch;
   int rc;
-  float* c1c2;
   if (partials != nullptr) {
     // (sum g, sum g * y) rows left by icamd_conv2d_dgrad_bnred
-    c1c2 = (float*)ws;
-    rc = icamd_bn_bwd_finalize_launch(partials, nrows, mean, invstd, dgamma, dbeta, M, C, accumulate, chunks, c1c2, (hipStream_t)stream, 1);
+    rc = icamd_bn_bwd_finalize_launch(partials, nrows, mean, invstd, dgamma, dbeta, M, C, accumulate, w.chunks, c1c2, (hipStream_t)stream, 1);
   } else {
-    // no sums yet: the reduce pass of icamd_bn_bwd over the (already masked) g and y first; workspace laid out as icamd_bn_bwd's
-    const int rpb = icamd_bn_bwd_rows_per_block(M, C);
-    const long long nblk = (M + rpb - 1) / rpb;
-    float* part = (float*)ws;
-    c1c2 = (float*)(ws + align_up((size_t)nblk * 2 * C * sizeof(float), 256));
+    // the reduce pass of icamd_bn_bwd over the (already masked) g and y first
     int nb = 0;
-    rc = icamd_bn_bwd_reduce_launch((const bf16_t*)g, (const bf16_t*)y, mean, invstd, part, M, C, &nb, (hipStream_t)stream);
+    rc = icamd_bn_bwd_reduce_launch((const bf16_t*)g, (const bf16_t*)y, mean, invstd, w.part, M, C, &nb, (hipStream_t)stream);
     if (rc) return rc;
-    rc = icamd_bn_bwd_finalize_launch(part, nb, mean, invstd, dgamma, dbeta, M, C, accumulate, chunks, c1c2, (hipStream_t)stream, 0);
+    rc = icamd_bn_bwd_finalize_launch(w.part, nb, mean, invstd, dgamma, dbeta, M, C, accumulate, w.chunks, c1c2, (hipStream_t)stream, 0);
   }
   if (rc) return rc;
   FusedBwdParams p;

@@ -3,7 +3,7 @@
 
 extern "C" {
 
-size_t icamd_bn_workspace_bytes(int C) { return C > 0 ? bn_chunk_bytes(C) : 0; }
+size_t icamd_bn_workspace_bytes(int C) { return C > 0 ? reduce_ws(nullptr, C, 0, 0).bytes : 0; }
 
 int icamd_bn_train_finalize(const float* partials, int nrows, int C, double count, const float* gamma,
                             const float* beta, float* running_mean, float* running_var, float momentum, float eps,
@@ -14,7 +14,7 @@ int icamd_bn_train_finalize(const float* partials, int nrows, int C, double coun
       mean == nullptr || invstd == nullptr || scale == nullptr || shift == nullptr || workspace == nullptr || C > 4096)
     return ICAMD_ERR_BAD_ARG;
   return icamd_bn_finalize_launch(partials, nrows, C, count, gamma, beta, running_mean, running_var, momentum, eps, mean,
-                                  invstd, scale, shift, (double*)((char*)workspace + 256), (hipStream_t)stream);
+                                  invstd, scale, shift, reduce_ws(workspace, C, 0, 0).chunks, (hipStream_t)stream);
 }
 
 int icamd_bn_eval_coeffs(int C, const float* gamma, const float* beta, const float* running_mean,
@@ -112,12 +112,23 @@ int icamd_se_bn_bwd(const void* dout, const uint8_t* maskbits, const void* y, co
                                 (hipStream_t)stream);
 }
 
-// bwd workspace: partial rows [nblk][2][C] floats | chunks [64][2][C] doubles | c1,c2 [2][C] floats
+// bwd workspace (reduce_ws): counters | chunks [64][2][C] doubles | partial rows [nblk][2][C] floats | c1,c2 [2][C] floats
 size_t icamd_bn_bwd_workspace_bytes(long long rows, int C) {
   if (rows <= 0 || C <= 0) return 0;
-  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
-  const long long nblk = (rows + rpb - 1) / rpb;
-  return align_up((size_t)nblk * 2 * C * sizeof(float), 256) + bn_chunk_bytes(C) + align_up((size_t)2 * C * sizeof(float), 256);
+  return reduce_ws(nullptr, C, bn_bwd_blocks(rows, C), 2).bytes;
+}
+
+// what icamd_bn_bwd and icamd_bn_bwd_maxpool3x3s2 share behind their argument checks
+static int bn_bwd_impl(const void* dout, const void* act, const void* y, const float* mean, const float* invstd, const float* scale,
+                       const float* shift, float* dgamma, float* dbeta, void* dy, void* gout, const uint8_t* maskbits,
+                       long long rows, int C, int relu, int accumulate, void* workspace, size_t workspace_bytes, void* stream,
+                       const uint8_t* pool_idx = nullptr, int IH = 0, int IW = 0) {
+  if (workspace_bytes < icamd_bn_bwd_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  const ReduceWs w = reduce_ws(workspace, C, bn_bwd_blocks(rows, C), 2);
+  return icamd_bn_bwd_launch((const bf16_t*)dout, (const bf16_t*)act, (const bf16_t*)y, mean, invstd, scale, shift, dgamma,
+                             dbeta, (bf16_t*)dy, (bf16_t*)gout, maskbits, rows, C, relu, accumulate, w.part, w.chunks, w.scratch,
+                             (hipStream_t)stream, pool_idx, IH, IW);
 }
 
 int icamd_bn_bwd(const void* dout, const void* act, const void* y, const float* mean, const float* invstd,
@@ -129,20 +140,8 @@ int icamd_bn_bwd(const void* dout, const void* act, const void* y, const float* 
   if (dout == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || scale == nullptr || shift == nullptr ||
       dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 || C <= 0)
     return ICAMD_ERR_BAD_ARG;
-  const size_t need = icamd_bn_bwd_workspace_bytes(rows, C);
-  if (workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
-  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
-  const long long nblk = (rows + rpb - 1) / rpb;
-  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);     // arrival counters live in the first 256 B
-  ws += bn_chunk_bytes(C);
-  float* part = (float*)ws;
-  ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
-  float* c1c2 = (float*)ws;
-  return icamd_bn_bwd_launch((const bf16_t*)dout, (const bf16_t*)act, (const bf16_t*)y, mean, invstd, scale, shift, dgamma,
-                             dbeta, (bf16_t*)dy, (bf16_t*)gout, maskbits, rows, C, relu, accumulate, part, chunks, c1c2,
-                             (hipStream_t)stream);
+  return bn_bwd_impl(dout, act, y, mean, invstd, scale, shift, dgamma, dbeta, dy, gout, maskbits, rows, C, relu, accumulate,
+                     workspace, workspace_bytes, stream);
 }
 
 int icamd_bn_bwd_maxpool3x3s2(const void* dout_pooled, const uint8_t* idx, const void* y, const float* mean,
@@ -155,21 +154,8 @@ int icamd_bn_bwd_maxpool3x3s2(const void* dout_pooled, const uint8_t* idx, const
       shift == nullptr || dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || N <= 0 || IH <= 0 ||
       IW <= 0 || C <= 0 || C % 8 != 0)
     return ICAMD_ERR_BAD_ARG;
-  const long long rows = (long long)N * IH * IW;
-  const size_t need = icamd_bn_bwd_workspace_bytes(rows, C);
-  if (workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
-  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
-  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
-  const long long nblk = (rows + rpb - 1) / rpb;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(C);
-  float* part = (float*)ws;
-  ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
-  float* c1c2 = (float*)ws;
-  return icamd_bn_bwd_launch((const bf16_t*)dout_pooled, nullptr, (const bf16_t*)y, mean, invstd, scale, shift, dgamma, dbeta,
-                             (bf16_t*)dy, nullptr, nullptr, rows, C, /*relu=*/1, accumulate, part, chunks, c1c2,
-                             (hipStream_t)stream, idx, IH, IW);
+  return bn_bwd_impl(dout_pooled, nullptr, y, mean, invstd, scale, shift, dgamma, dbeta, dy, nullptr, nullptr,
+                     (long long)N * IH * IW, C, /*relu=*/1, accumulate, workspace, workspace_bytes, stream, idx, IH, IW);
 }
 
 int icamd_bn_bwd_dual(const void* dout, const uint8_t* maskbits, const void* yA, const float* meanA, const float* invstdA,
@@ -185,26 +171,26 @@ int icamd_bn_bwd_dual(const void* dout, const uint8_t* maskbits, const void* yA,
     return ICAMD_ERR_BAD_ARG;
   if (workspace_bytes < icamd_bn_bwd_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
   if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
-  const int rpb = icamd_bn_bwd_rows_per_block(rows, C);
-  const long long nblk = (rows + rpb - 1) / rpb;
-  float* part[2]; double* chunks[2]; float* cc[2];
-  void* wsv[2] = {workspaceA, workspaceB};
-  for (int i = 0; i < 2; ++i) {
-    char* ws = (char*)wsv[i];
-    chunks[i] = (double*)(ws + 256);
-    ws += bn_chunk_bytes(C);
-    part[i] = (float*)ws;
-    ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
-    cc[i] = (float*)ws;
-  }
+  const long long nblk = bn_bwd_blocks(rows, C);
+  const ReduceWs a = reduce_ws(workspaceA, C, nblk, 2), b = reduce_ws(workspaceB, C, nblk, 2);
   return icamd_bn_bwd_dual_launch((const bf16_t*)dout, maskbits, (const bf16_t*)yA, meanA, invstdA, scaleA, dgammaA, dbetaA,
                                   (bf16_t*)dyA, (const bf16_t*)yB, meanB, invstdB, scaleB, dgammaB, dbetaB, (bf16_t*)dyB, rows,
-                                  C, accumulate, part[0], chunks[0], cc[0], part[1], chunks[1], cc[1], (hipStream_t)stream);
+                                  C, accumulate, a.part, a.chunks, a.scratch, b.part, b.chunks, b.scratch, (hipStream_t)stream);
 }
 
-// workspace: chunks [64][2][C] doubles | c1,c2 [2][C] floats
-size_t icamd_bn_bwd_apply_workspace_bytes(int C) {
-  return C > 0 ? bn_chunk_bytes(C) + align_up((size_t)2 * C * sizeof(float), 256) : 0;
+// workspace (reduce_ws without partial rows): counters | chunks [64][2][C] doubles | c1,c2 [2][C] floats
+size_t icamd_bn_bwd_apply_workspace_bytes(int C) { return C > 0 ? reduce_ws(nullptr, C, 0, 2).bytes : 0; }
+
+// what icamd_bn_bwd_from_partials and icamd_bn_bwd_from_gy_partials share behind their argument checks
+static int bn_bwd_from_partials_impl(const float* partials, int nrows, const void* g, const void* y, const float* mean,
+                                     const float* invstd, const float* scale, float* dgamma, float* dbeta, void* dy,
+                                     long long rows, int C, int accumulate, void* workspace, size_t workspace_bytes,
+                                     void* stream, int sums_are_gy) {
+  if (workspace_bytes < icamd_bn_bwd_apply_workspace_bytes(C)) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  const ReduceWs w = reduce_ws(workspace, C, 0, 2);
+  return icamd_bn_bwd_apply_launch(partials, nrows, (const bf16_t*)g, (const bf16_t*)y, mean, invstd, scale, dgamma, dbeta,
+                                   (bf16_t*)dy, rows, C, accumulate, w.chunks, w.scratch, (hipStream_t)stream, sums_are_gy);
 }
 
 int icamd_bn_bwd_from_partials(const float* partials, int nrows, const void* g, const void* y, const float* mean,
@@ -217,13 +203,8 @@ int icamd_bn_bwd_from_partials(const float* partials, int nrows, const void* g, 
       scale == nullptr || dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 ||
       C <= 0 || C % 8 != 0)
     return ICAMD_ERR_BAD_ARG;
-  if (workspace_bytes < icamd_bn_bwd_apply_workspace_bytes(C)) return ICAMD_ERR_WORKSPACE;
-  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(C);
-  return icamd_bn_bwd_apply_launch(partials, nrows, (const bf16_t*)g, (const bf16_t*)y, mean, invstd, scale, dgamma, dbeta,
-                                   (bf16_t*)dy, rows, C, accumulate, chunks, (float*)ws, (hipStream_t)stream);
+  return bn_bwd_from_partials_impl(partials, nrows, g, y, mean, invstd, scale, dgamma, dbeta, dy, rows, C, accumulate, workspace,
+                                   workspace_bytes, stream, 0);
 }
 
 int icamd_bn_bwd_from_gy_partials(const float* partials, int nrows, const void* g, const void* y, const float* mean,
@@ -236,13 +217,8 @@ int icamd_bn_bwd_from_gy_partials(const float* partials, int nrows, const void* 
       scale == nullptr || dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 ||
       C <= 0 || C % 8 != 0)
     return ICAMD_ERR_BAD_ARG;
-  if (workspace_bytes < icamd_bn_bwd_apply_workspace_bytes(C)) return ICAMD_ERR_WORKSPACE;
-  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(C);
-  return icamd_bn_bwd_apply_launch(partials, nrows, (const bf16_t*)g, (const bf16_t*)y, mean, invstd, scale, dgamma, dbeta,
-                                   (bf16_t*)dy, rows, C, accumulate, chunks, (float*)ws, (hipStream_t)stream, 1);
+  return bn_bwd_from_partials_impl(partials, nrows, g, y, mean, invstd, scale, dgamma, dbeta, dy, rows, C, accumulate, workspace,
+                                   workspace_bytes, stream, 1);
 }
 
 int icamd_maxpool3x3s2_fwd(const void* x, void* out, uint8_t* argmax, int N, int IH, int IW, int C, void* stream) {

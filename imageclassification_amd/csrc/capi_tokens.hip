@@ -15,11 +15,10 @@ int icamd_layernorm_fwd(const void* x, const float* gamma, const float* beta, vo
   return icamd_layernorm_fwd_launch((const bf16_t*)x, gamma, beta, (bf16_t*)y, mean, rstd, rows, C, eps, (hipStream_t)stream);
 }
 
-// workspace: [counters|chunks] | partial rows [blocks][2][C] | scratch [2][C]
+// workspace (reduce_ws): [counters|chunks] | partial rows [blocks][2][C] | scratch [2][C]
 size_t icamd_layernorm_bwd_workspace_bytes(long long rows, int C) {
   if (rows <= 0 || C <= 0) return 0;
-  return bn_chunk_bytes(C) + align_up((size_t)icamd_layernorm_bwd_blocks(rows) * 2 * C * sizeof(float), 256) +
-         align_up((size_t)2 * C * sizeof(float), 256);
+  return reduce_ws(nullptr, C, icamd_layernorm_bwd_blocks(rows), 2).bytes;
 }
 
 int icamd_layernorm_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
@@ -31,16 +30,12 @@ int icamd_layernorm_bwd(const void* dy, const void* x, const float* mean, const 
       dgamma == nullptr || dbeta == nullptr || workspace == nullptr || rows <= 0 || C <= 0 || C > 4096)
     return ICAMD_ERR_BAD_ARG;
   if (workspace_bytes < icamd_layernorm_bwd_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(C);
-  float* part = (float*)ws;
   const int nblk = icamd_layernorm_bwd_blocks(rows);
-  ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
+  const ReduceWs w = reduce_ws(workspace, C, nblk, 2);
   int rc = icamd_layernorm_bwd_launch((const bf16_t*)dy, (const bf16_t*)x, mean, rstd, gamma, (const bf16_t*)addend,
-                                      (bf16_t*)dx, part, rows, C, (hipStream_t)stream);
+                                      (bf16_t*)dx, w.part, rows, C, (hipStream_t)stream);
   if (rc) return rc;
-  return icamd_sum_partials_launch(part, nblk, C, dbeta, dgamma, accumulate, chunks, (float*)ws, (hipStream_t)stream);
+  return icamd_sum_partials_launch(w.part, nblk, C, dbeta, dgamma, accumulate, w.chunks, w.scratch, (hipStream_t)stream);
 }
 
 int icamd_gelu_fwd(const void* z, void* a, long long numel, void* stream) {
@@ -59,8 +54,7 @@ int icamd_gelu_bwd(const void* da, const void* z, void* dz, long long numel, voi
 
 size_t icamd_colsum_rows_workspace_bytes(long long rows, int cols) {
   if (rows <= 0 || cols <= 0) return 0;
-  return bn_chunk_bytes(cols) + align_up((size_t)icamd_colsum_blocks(rows) * 2 * cols * sizeof(float), 256) +
-         align_up((size_t)3 * cols * sizeof(float), 256);
+  return reduce_ws(nullptr, cols, icamd_colsum_blocks(rows), 3).bytes;
 }
 
 // out[c] = (accumulate ? out[c] : 0) + sum_r x[r][c], two-level, fixed order (bias gradients of long token matrices)
@@ -71,16 +65,12 @@ int icamd_colsum_rows(const void* x, long long rows, int ld, int cols, float* ou
   if (x == nullptr || out == nullptr || workspace == nullptr || rows <= 0 || cols <= 0 || cols > 4096 || ld < cols)
     return ICAMD_ERR_BAD_ARG;
   if (workspace_bytes < icamd_colsum_rows_workspace_bytes(rows, cols)) return ICAMD_ERR_WORKSPACE;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(cols);
-  float* part = (float*)ws;
   const int nblk = icamd_colsum_blocks(rows);
-  ws += align_up((size_t)nblk * 2 * cols * sizeof(float), 256);
-  float* scratch = (float*)ws;   // [3][cols]: discarded second sum + c1/c2
-  int rc = icamd_colsum_partial_launch((const bf16_t*)x, part, rows, ld, cols, (hipStream_t)stream);
+  const ReduceWs w = reduce_ws(workspace, cols, nblk, 3);   // scratch [3][cols]: discarded second sum + c1/c2
+  int rc = icamd_colsum_partial_launch((const bf16_t*)x, w.part, rows, ld, cols, (hipStream_t)stream);
   if (rc) return rc;
-  return icamd_sum_partials_launch(part, nblk, cols, out, scratch, accumulate, chunks, scratch + cols, (hipStream_t)stream);
+  return icamd_sum_partials_launch(w.part, nblk, cols, out, w.scratch, accumulate, w.chunks, w.scratch + cols,
+                                   (hipStream_t)stream);
 }
 
 int icamd_vit_tokens_fwd(const void* patches, const float* cls_token, const float* pos_embed, void* tokens, int B, int T, int C,
@@ -166,8 +156,7 @@ int icamd_layerscale_fwd(const void* z, const void* inp, const float* gamma, con
 
 size_t icamd_layerscale_bwd_workspace_bytes(long long rows, int C) {
   if (rows <= 0 || C <= 0) return 0;
-  return bn_chunk_bytes(C) + align_up((size_t)icamd_layerscale_bwd_blocks(rows) * 2 * C * sizeof(float), 256) +
-         align_up((size_t)3 * C * sizeof(float), 256);
+  return reduce_ws(nullptr, C, icamd_layerscale_bwd_blocks(rows), 3).bytes;
 }
 
 int icamd_layerscale_bwd(const void* dout, const void* z, const float* gamma, const float* keep, void* dz, float* dgamma,
@@ -179,17 +168,12 @@ int icamd_layerscale_bwd(const void* dout, const void* z, const float* gamma, co
       rows <= 0 || C <= 0 || C > 4096 || rows_per_image <= 0)
     return ICAMD_ERR_BAD_ARG;
   if (workspace_bytes < icamd_layerscale_bwd_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
-  char* ws = (char*)workspace;
-  double* chunks = (double*)(ws + 256);
-  ws += bn_chunk_bytes(C);
-  float* part = (float*)ws;
   const int nblk = icamd_layerscale_bwd_blocks(rows);
-  ws += align_up((size_t)nblk * 2 * C * sizeof(float), 256);
-  float* scratch = (float*)ws;
-  int rc = icamd_layerscale_bwd_launch((const bf16_t*)dout, (const bf16_t*)z, gamma, keep, (bf16_t*)dz, part, rows, C,
+  const ReduceWs w = reduce_ws(workspace, C, nblk, 3);
+  int rc = icamd_layerscale_bwd_launch((const bf16_t*)dout, (const bf16_t*)z, gamma, keep, (bf16_t*)dz, w.part, rows, C,
                                        rows_per_image, (hipStream_t)stream);
   if (rc) return rc;
-  return icamd_sum_partials_launch(part, nblk, C, dgamma, scratch, accumulate, chunks, scratch + C, (hipStream_t)stream);
+  return icamd_sum_partials_launch(w.part, nblk, C, dgamma, w.scratch, accumulate, w.chunks, w.scratch + C, (hipStream_t)stream);
 }
 
 // Layer scale folded into the Mlp's second Linear layer (round 5): see include/icamd.h
@@ -302,7 +286,7 @@ int icamd_window_attention_fwd(const void* qkv, const float* bias, void* out, fl
 size_t icamd_window_attention_bwd_workspace_bytes(int B, int Hs, int Ws, int H, int ws) {
   if (B <= 0 || H <= 0 || !icamd_window_attention_ok(Hs, Ws, ws, 32)) return 0;
   const long long nwin = (long long)B * (Hs / ws) * (Ws / ws);
-  return align_up((size_t)icamd_window_attention_bwd_chunks(nwin, H, ws) * H * ws * ws * ws * ws * sizeof(float), 256);
+  return ws_round256((size_t)icamd_window_attention_bwd_chunks(nwin, H, ws) * H * ws * ws * ws * ws * sizeof(float));
 }
 
 int icamd_window_attention_bwd(const void* qkv, const float* bias, const void* out, const void* dout, const float* lse,
@@ -349,7 +333,7 @@ int icamd_patch_merge_ln_fwd(const void* x, const float* gamma, const float* bet
 
 size_t icamd_patch_merge_ln_bwd_workspace_bytes(int N, int H, int W, int C) {
   if (!icamd_patch_merge_ln_ok(N, H, W, C)) return 0;
-  return align_up((size_t)icamd_patch_merge_ln_bwd_blocks((long long)N * (H / 2) * (W / 2)) * 8 * C * sizeof(float), 256);
+  return ws_round256((size_t)icamd_patch_merge_ln_bwd_blocks((long long)N * (H / 2) * (W / 2)) * 8 * C * sizeof(float));
 }
 
 int icamd_patch_merge_ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma, void* dx,

@@ -737,7 +737,7 @@ int pick_side(int n) {
   if (n <= 64) return 64;
   if (n <= 128) return 128;
   if (n % 256 == 0 || n >= 1024) return 256;
-  return ((n + 255) / 256 * 256 - n) * 4 <= n ? 256 : 128;     // at most 25 % padding for the 256 side
+  return (256 - n % 256) * 4 <= n ? 256 : 128;     // at most 25 % padding for the 256 side (n is no multiple of 256 here)
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 // No float atomics anywhere: two launches on the same inputs give the same bits.  The backward's finishing launch sums the
 // per-sample rows P Nx and Q over n in a fixed order into dgamma / dbeta (fp32, accumulate flag).
 #include "icamd_internal.h"
+#include "workspace.h"
 
 namespace {
 
@@ -307,19 +308,18 @@ void icamd_grn_plan(int N, int HW, int C, int* S, int* rps, int* B, int* rpb) {
   *B = cdiv(HW, *rpb);
 }
 
-// workspace: partial rows [N][S][2][C] | per-sample rows of the parameter gradients [N][2][C]
+// workspace (grn_ws): partial rows [N][S][2][C] | per-sample rows of the parameter gradients [N][2][C]
 size_t icamd_grn_bytes(int N, int HW, int C) {
   int S, rps, B, rpb;
   icamd_grn_plan(N, HW, C, &S, &rps, &B, &rpb);
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  return up((size_t)N * S * 2 * C * sizeof(float)) + up((size_t)N * 2 * C * sizeof(float));
+  return grn_ws(nullptr, N, S, C).bytes;
 }
 
 int icamd_grn_fwd_launch(const bf16_t* a, const float* gamma, const float* beta, bf16_t* g, float* gx_out, int N, int HW, int C,
                          float eps, void* workspace, hipStream_t s) {
   int S, rps, B, rpb;
   icamd_grn_plan(N, HW, C, &S, &rps, &B, &rpb);
-  float* part = (float*)workspace;
+  float* part = grn_ws(workspace, N, S, C).part;
   const int cpr = C / 8, tcols = reduce_tcols(cpr);
   hipLaunchKernelGGL(grn_reduce_kernel<1>, dim3(cpr / tcols, S, N), dim3(GRN_THREADS), 0, s, a, nullptr, part, HW, C, tcols, rps, S);
   hipLaunchKernelGGL(grn_fwd_apply_kernel, dim3(B, N), dim3(GRN_THREADS), 2 * C * sizeof(float), s, a, gamma, beta, g, gx_out, part,
@@ -332,8 +332,8 @@ int icamd_grn_bwd_launch(const bf16_t* dg, const bf16_t* a, const float* gx, con
                          hipStream_t s) {
   int S, rps, B, rpb;
   icamd_grn_plan(N, HW, C, &S, &rps, &B, &rpb);
-  float* part = (float*)workspace;
-  float* fin = (float*)((char*)workspace + ((size_t)N * S * 2 * C * sizeof(float) + 255) / 256 * 256);
+  const GrnWs w = grn_ws(workspace, N, S, C);
+  float *part = w.part, *fin = w.fin;
   const int cpr = C / 8, tcols = reduce_tcols(cpr);
   hipLaunchKernelGGL(grn_reduce_kernel<2>, dim3(cpr / tcols, S, N), dim3(GRN_THREADS), 0, s, a, dg, part, HW, C, tcols, rps, S);
   if (z != nullptr)

@@ -19,6 +19,7 @@
 // descriptors, so parity tests inject them.  Bit-exact against Pillow for steps 1-4 (tests/test_image_gpu.py).
 #include "../../include/icamd.h"
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
@@ -411,10 +412,7 @@ static long long tab_words(int out_h, int out_w, int kmax) { return (long long)(
 
 size_t icamd_image_pipeline_workspace_bytes(int B, int max_crop_h, int out_h, int out_w, int kmax) {
   if (B <= 0 || max_crop_h <= 0 || out_h <= 0 || out_w <= 0 || kmax <= 0) return 0;
-  const size_t tabs = (size_t)B * tab_words(out_h, out_w, kmax) * 4;
-  const size_t tmp = (size_t)B * max_crop_h * out_w * 3;
-  const size_t img = (size_t)B * out_h * out_w * 3;
-  return ((tabs + 255) / 256 + (tmp + 255) / 256 + (img + 255) / 256) * 256;
+  return image_ws(nullptr, B, tab_words(out_h, out_w, kmax), max_crop_h, out_h, out_w).bytes;
 }
 
 int icamd_image_pipeline(const uint8_t* src, const icamd_image_desc* descs, int B, int max_crop_h, int out_h, int out_w,
@@ -427,12 +425,10 @@ int icamd_image_pipeline(const uint8_t* src, const icamd_image_desc* descs, int 
   if (need == 0 || workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const long long per_image = tab_words(out_h, out_w, kmax);
-  int* tabs = (int*)workspace;
-  const size_t tabs_b = ((size_t)B * per_image * 4 + 255) / 256 * 256;
-  unsigned char* tmp = (unsigned char*)workspace + tabs_b;
   const long long tmp_per_image = (long long)max_crop_h * out_w * 3;
-  const size_t tmp_b = ((size_t)B * tmp_per_image + 255) / 256 * 256;
-  unsigned char* img = tmp + tmp_b;
+  const ImageWs w = image_ws(workspace, B, per_image, max_crop_h, out_h, out_w);
+  int* tabs = w.tabs;
+  unsigned char *tmp = w.tmp, *img = w.img;
   const int omax = out_h > out_w ? out_h : out_w;
   hipLaunchKernelGGL(resample_coeffs_kernel, dim3((unsigned)((omax + 63) / 64), 2, (unsigned)B), dim3(64), 0, s, descs, out_h,
                      out_w, filter, kmax, tabs, per_image);
@@ -447,11 +443,8 @@ int icamd_image_pipeline(const uint8_t* src, const icamd_image_desc* descs, int 
 }
 
 size_t icamd_image_pipeline_aug_workspace_bytes(int B, int max_crop_h, int out_h, int out_w, int kmax) {
-  const size_t base = icamd_image_pipeline_workspace_bytes(B, max_crop_h, out_h, out_w, kmax);
-  if (base == 0) return 0;
-  const size_t img = (size_t)B * out_h * out_w * 3;
-  const size_t aux = (size_t)B * AUG_AUX_BYTES;
-  return base + ((img + 255) / 256 + (aux + 255) / 256) * 256;
+  if (icamd_image_pipeline_workspace_bytes(B, max_crop_h, out_h, out_w, kmax) == 0) return 0;
+  return image_aug_ws(nullptr, B, tab_words(out_h, out_w, kmax), max_crop_h, out_h, out_w, AUG_AUX_BYTES).bytes;
 }
 
 int icamd_image_pipeline_aug(const uint8_t* src, const icamd_image_desc* descs, const icamd_aug_op* ops, int ops_per_image,
@@ -467,15 +460,10 @@ int icamd_image_pipeline_aug(const uint8_t* src, const icamd_image_desc* descs, 
   // icamd_image_pipeline's layout [tabs][tmp][img], then [img2][aux]: the final image must land in img (icamd_image_pipeline_u8),
   // so the resize writes to img2 when the number of ping-pong passes is odd
   const long long per_image = tab_words(out_h, out_w, kmax);
-  int* tabs = (int*)workspace;
-  const size_t tabs_b = ((size_t)B * per_image * 4 + 255) / 256 * 256;
-  unsigned char* tmp = (unsigned char*)workspace + tabs_b;
   const long long tmp_per_image = (long long)max_crop_h * out_w * 3;
-  const size_t tmp_b = ((size_t)B * tmp_per_image + 255) / 256 * 256;
-  unsigned char* img = tmp + tmp_b;
-  const size_t img_b = ((size_t)B * out_h * out_w * 3 + 255) / 256 * 256;
-  unsigned char* img2 = img + img_b;
-  unsigned char* aux = img2 + img_b;
+  const ImageAugWs w = image_aug_ws(workspace, B, per_image, max_crop_h, out_h, out_w, AUG_AUX_BYTES);
+  int* tabs = w.tabs;
+  unsigned char *tmp = w.tmp, *img = w.img, *img2 = w.img2, *aux = w.aux;
   unsigned char* cur = ops_per_image % 2 ? img2 : img;
   unsigned char* nxt = ops_per_image % 2 ? img : img2;
   const int omax = out_h > out_w ? out_h : out_w;
@@ -503,9 +491,7 @@ int icamd_image_pipeline_aug(const uint8_t* src, const icamd_image_desc* descs, 
 // the uint8 [B][H][W][3] image after resize / flips / jitter (what Pillow would hold before ToTensor): for parity tests
 int icamd_image_pipeline_u8(const void* workspace, int B, int max_crop_h, int out_h, int out_w, int kmax, const uint8_t** img) {
   if (workspace == nullptr || img == nullptr) return ICAMD_ERR_BAD_ARG;
-  const size_t tabs_b = ((size_t)B * tab_words(out_h, out_w, kmax) * 4 + 255) / 256 * 256;
-  const size_t tmp_b = ((size_t)B * max_crop_h * out_w * 3 + 255) / 256 * 256;
-  *img = (const uint8_t*)workspace + tabs_b + tmp_b;
+  *img = image_ws(const_cast<void*>(workspace), B, tab_words(out_h, out_w, kmax), max_crop_h, out_h, out_w).img;
   return ICAMD_OK;
 }
 

@@ -11,6 +11,7 @@
 // index order and every sum over samples is a serial loop in n: no float atomics, every output is bitwise repeatable.
 #include "common.h"
 #include "icamd_internal.h"
+#include "workspace.h"
 #include <stdlib.h>
 
 namespace {
@@ -390,7 +391,6 @@ __global__ __launch_bounds__(256) void se_bwd_apply_kernel(const bf16_t* __restr
 }
 
 inline int gcd_i(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
-inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
 // blocks per sample of the two elementwise passes: ~2048 workgroups in all, total threads per sample a multiple of C/8
 unsigned int blocks_per_sample(int N, int HW, int cpr) {
@@ -427,7 +427,7 @@ void icamd_se_plan(int N, int HW, int* S, int* rps) {
 size_t icamd_se_squeeze_bytes(int N, int HW, int C) {
   int S, rps;
   icamd_se_plan(N, HW, &S, &rps);
-  return align256((size_t)N * S * C * sizeof(float));
+  return ws_round256((size_t)N * S * C * sizeof(float));
 }
 
 int icamd_se_squeeze_launch(const bf16_t* y, float* ysum, int N, int HW, int C, float* part, hipStream_t s) {
@@ -461,13 +461,11 @@ int icamd_se_bn_apply_launch(const bf16_t* y, const float* scale, const float* s
   return icamd_launch_status();
 }
 
-// workspace: part [N*S][2][C] | AB [N][2][C] | dp2 [N][C] | ds [N][C] | k0 [N][C] | dh [N][256] | k2 [C]   (floats, 256 B aligned)
+// workspace: the seven regions of se_bwd_ws (workspace.h)
 size_t icamd_se_bn_bwd_bytes(int N, int HW, int C) {
   int S, rps;
   icamd_se_plan(N, HW, &S, &rps);
-  const size_t nc = align256((size_t)N * C * sizeof(float));
-  return align256((size_t)N * S * 2 * C * sizeof(float)) + 2 * nc + 3 * nc + align256((size_t)N * 256 * sizeof(float)) +
-         align256((size_t)C * sizeof(float));
+  return se_bwd_ws(nullptr, N, S, C).bytes;
 }
 
 int icamd_se_bn_bwd_launch(const bf16_t* dout, const unsigned char* maskbits, const bf16_t* y, const float* mean,
@@ -477,15 +475,8 @@ int icamd_se_bn_bwd_launch(const bf16_t* dout, const unsigned char* maskbits, co
                            int accumulate, void* workspace, hipStream_t s) {
   int S, rps;
   icamd_se_plan(N, HW, &S, &rps);
-  const size_t nc = align256((size_t)N * C * sizeof(float));
-  char* ws = (char*)workspace;
-  float* part = (float*)ws; ws += align256((size_t)N * S * 2 * C * sizeof(float));
-  float* AB = (float*)ws; ws += 2 * nc;
-  float* dp2 = (float*)ws; ws += nc;
-  float* ds = (float*)ws; ws += nc;
-  float* k0 = (float*)ws; ws += nc;
-  float* dh = (float*)ws; ws += align256((size_t)N * 256 * sizeof(float));
-  float* k2 = (float*)ws;
+  const SeBwdWs w = se_bwd_ws(workspace, N, S, C);
+  float *part = w.part, *AB = w.AB, *dp2 = w.dp2, *ds = w.ds, *k0 = w.k0, *dh = w.dh, *k2 = w.k2;
   hipLaunchKernelGGL(se_reduce_kernel<2>, dim3((unsigned)(N * S)), dim3(256), 0, s, y, dout, maskbits, mean, invstd, part, HW, C,
                      S, rps);
   int rc = icamd_launch_status();
