@@ -6,12 +6,18 @@ whole-network comparisons are calibrated against the oracle's own re-association
 wiring is proven with a teacher-forced run (both explained at the tests).
 """
 import ctypes
+import os
+import sys
 
 import pytest
 import torch
 
 from oracle import ops_ref as R
 from oracle.resnet_ref import ResNetRef
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _resnet_parity import assert_hip_within_yardstick, hip_rows, parity_batch, yardstick  # noqa: E402
+from _resnet_parity import timm_default_pair as _timm_default_pair, xent_backward as _xent_backward  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -31,18 +37,6 @@ def _pair(arch, num_classes, seed=0):
     return ref, net
 
 
-def _xent_backward(net, ws, targets, num_classes, smoothing=0.0):
-    from imageclassification_amd import hip
-    lib = net.lib
-    B = targets.shape[0]
-    hip.check(lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, num_classes, targets.data_ptr(), None, 1.0,
-                                     smoothing, 1.0 / B, ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(),
-                                     ws["dlogits"].data_ptr(), hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
-    return float(ws["loss_rows"].mean())
-
-
 def _nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
 
@@ -53,42 +47,15 @@ def test_resnet18_forward_backward_within_asserted_reassociation_noise():
     test used random BatchNorm weights on every layer at batch 4-8 / 64x64, where the ORACLE's own gradient noise is 0.15-1.0
     -- ReLU-mask flips cost sqrt(fraction flipped) in relative L2 -- and so accepted anything; that configuration is now
     only used teacher-forced, where the masks are pinned.)"""
-    import copy
     C, B, HW = 10, 16, 96
     ref, net = _timm_default_pair("resnet18", C)
-    ref64 = copy.deepcopy(ref).double()
-    g = torch.Generator().manual_seed(5)
-    x = torch.randn(B, 3, HW, HW, generator=g)
-    y = torch.randint(0, C, (B,), generator=g)
-    ref.train(); ref64.train()
-    out = ref(x)
-    loss = torch.nn.functional.cross_entropy(out, y, label_smoothing=0.1)
-    loss.backward()
-    out64 = ref64(x.double())
-    torch.nn.functional.cross_entropy(out64, y, label_smoothing=0.1).backward()
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    hip_loss = _xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
-    got = logits[:, :C].float().cpu()
-    noise_logits = R.rel_l2(out64.detach().float(), out.detach())
-    p64 = dict(ref64.named_parameters())
-    rows = []
-    for name, p in ref.named_parameters():
-        if float(p.grad.abs().max()) == 0.0:
-            assert float(net.grad_of(name).abs().max()) == 0.0, name
-            continue
-        rows.append((name, R.rel_l2(net.grad_of(name), p.grad), R.rel_l2(p64[name].grad.float(), p.grad)))
-    mean_e = sum(r[1] for r in rows) / len(rows)
-    mean_n = sum(r[2] for r in rows) / len(rows)
-    print(f"resnet18: logits err {R.rel_l2(got, out.detach()):.2e} (self-noise {noise_logits:.2e}); mean grad err "
-          f"{mean_e:.2e} (self-noise {mean_n:.2e}) over {len(rows)} tensors")
-    assert noise_logits <= 5e-3 and mean_n <= 2e-2, (noise_logits, mean_n)
-    assert R.rel_l2(got, out.detach()) <= 2.0 * max(noise_logits, 1e-3)
-    assert abs(hip_loss - float(loss)) <= 1e-3 * abs(float(loss))
-    assert mean_e <= 2.0 * max(mean_n, 1e-3)
-    for name, e, n in rows:
-        assert e <= 3.0 * max(n, 5e-3), (name, e, n)
+    x, y = parity_batch(C, B, HW)
+    yard = yardstick(ref, x, y, 0.1)
+    got = hip_rows(net, x, y, C, 0.1, yard)
+    print(f"resnet18: logits err {got.err_logits:.2e} (self-noise {yard.noise_logits:.2e}); mean grad err "
+          f"{got.mean_err:.2e} (self-noise {yard.mean_noise:.2e}) over {len(got.rows)} tensors")
+    assert yard.noise_logits <= 5e-3 and yard.mean_noise <= 2e-2, (yard.noise_logits, yard.mean_noise)
+    assert_hip_within_yardstick(yard, got)
 
 
 def test_resnet18_odd_input_size_matches_oracle():
@@ -117,17 +84,6 @@ def test_resnet18_odd_input_size_matches_oracle():
     with torch.no_grad():
         eo = ref(x)
     assert R.rel_l2(net(x.cuda()).float().cpu(), eo) <= 1e-2
-
-
-def _timm_default_pair(arch, num_classes, seed=0):
-    """The configuration the reference really trains from: timm's ResNet init (Kaiming fan-out filters, BatchNorm weight 1 /
-    bias 0, ZERO-initialised last BatchNorm weight of every residual block; /root/reference/train.py:194 create_model)."""
-    from imageclassification_amd.nets import ResNet
-    torch.manual_seed(seed)
-    ref = ResNetRef(arch, num_classes, bf16_points=True, zero_init_last=True)
-    net = ResNet(arch, num_classes)
-    net.load_state_dict(ref.state_dict())
-    return ref, net
 
 
 class _As64(torch.nn.Module):
@@ -161,47 +117,15 @@ def test_resnet50_whole_network_parity_well_conditioned(gamma_last):
     that cannot tell a wrong gradient from a right one.  At 0.02 the branches do not amplify, the gradient only crosses their
     two inner ReLU masks: yardstick mean 8.7e-2, worst 1.5e-1 (a BatchNorm bias in layer4: a sum with cancellation), asserted
     <= 0.13 / 0.22; a dropped term, tap or stride class in any branch kernel scores >= 0.5 on its tensor."""
-    import copy
     C, B, HW = 100, 32, 128
-    ref, net = _timm_default_pair("resnet50", C)
-    if gamma_last:
-        for n, m in ref.named_modules():
-            if n.endswith("bn3"):
-                m.weight.data.fill_(gamma_last)
-        net.load_state_dict(ref.state_dict())
-    ref64 = copy.deepcopy(ref).double()
-    g = torch.Generator().manual_seed(5)
-    x = torch.randn(B, 3, HW, HW, generator=g)
-    y = torch.randint(0, C, (B,), generator=g)
-    ref.train(); ref64.train()
-    out = ref(x)
-    loss = torch.nn.functional.cross_entropy(out, y, label_smoothing=0.1)
-    loss.backward()
-    out64 = ref64(x.double())
-    loss64 = torch.nn.functional.cross_entropy(out64, y, label_smoothing=0.1)
-    loss64.backward()
-
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    hip_loss = _xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
-    got = logits[:, :C].float().cpu()
-    noise_logits = R.rel_l2(out64.detach().float(), out.detach())
-    err_logits = R.rel_l2(got, out.detach())
-    p64 = dict(ref64.named_parameters())
-    rows, zero_branch = [], 0
-    for name, p in ref.named_parameters():
-        if float(p.grad.abs().max()) == 0.0:
-            assert float(net.grad_of(name).abs().max()) == 0.0, name     # zero-gamma branches: exactly zero on both sides
-            zero_branch += 1
-            continue
-        rows.append((name, R.rel_l2(net.grad_of(name), p.grad), R.rel_l2(p64[name].grad.float(), p.grad)))
-    mean_e = sum(r[1] for r in rows) / len(rows)
-    mean_n = sum(r[2] for r in rows) / len(rows)
-    worst = max(rows, key=lambda r: r[1])
-    print(f"resnet50 B={B} {HW}x{HW} gamma_last={gamma_last}: logits err {err_logits:.2e} (self-noise {noise_logits:.2e}); "
-          f"loss {hip_loss:.6f} vs {float(loss):.6f}; {len(rows)} gradient tensors: mean err {mean_e:.2e} (self-noise "
-          f"{mean_n:.2e}), worst {worst[0]} {worst[1]:.2e} (its self-noise {worst[2]:.2e}); {zero_branch} zero-gradient "
+    ref, net = _timm_default_pair("resnet50", C, gamma_last=gamma_last)
+    x, y = parity_batch(C, B, HW)
+    yard = yardstick(ref, x, y, 0.1)
+    got = hip_rows(net, x, y, C, 0.1, yard)
+    rows, zero_branch, worst = got.rows, got.zero_branch, got.worst
+    print(f"resnet50 B={B} {HW}x{HW} gamma_last={gamma_last}: logits err {got.err_logits:.2e} (self-noise {yard.noise_logits:.2e}); "
+          f"loss {got.loss:.6f} vs {yard.loss:.6f}; {len(rows)} gradient tensors: mean err {got.mean_err:.2e} (self-noise "
+          f"{yard.mean_noise:.2e}), worst {worst[0]} {worst[1]:.2e} (its self-noise {worst[2]:.2e}); {zero_branch} zero-gradient "
           f"branch tensors exact")
     if gamma_last:
         for kind in ("conv1.weight", "conv2.weight", "conv3.weight", "bn1.weight", "bn2.weight", "bn3.weight"):
@@ -210,18 +134,15 @@ def test_resnet50_whole_network_parity_well_conditioned(gamma_last):
                   f"{max(r[1] for r in sel):.2e} | yardstick mean {sum(r[2] for r in sel) / len(sel):.2e} worst "
                   f"{max(r[2] for r in sel):.2e}")
     # the yardstick itself
+    noise = (yard.noise_logits, yard.mean_noise)
     if gamma_last:
         assert zero_branch == 0 and len(rows) == 161            # every parameter tensor has a non-zero gradient
-        assert noise_logits <= 8e-3 and mean_n <= 0.13 and max(r[2] for r in rows) <= 0.22, (noise_logits, mean_n)
+        assert yard.noise_logits <= 8e-3 and yard.mean_noise <= 0.13 and yard.worst_noise[1] <= 0.22, noise
     else:
-        assert noise_logits <= 5e-3 and mean_n <= 4e-2 and max(r[2] for r in rows) <= 6e-2, (noise_logits, mean_n)
+        assert yard.noise_logits <= 5e-3 and yard.mean_noise <= 4e-2 and yard.worst_noise[1] <= 6e-2, noise
         assert zero_branch >= 48 * 2 and len(rows) >= 40
     # the HIP path against it
-    assert err_logits <= 2.0 * max(noise_logits, 1e-3)
-    assert abs(hip_loss - float(loss)) <= 1e-3 * abs(float(loss))
-    assert mean_e <= 2.0 * max(mean_n, 1e-3)
-    for name, e, n in rows:
-        assert e <= 3.0 * max(n, 5e-3), (name, e, n)
+    assert_hip_within_yardstick(yard, got)
 
 
 @pytest.mark.parametrize("arch,B,HW,tol", [("resnet18", 8, 64, 3e-2), ("resnet50", 4, 96, 8e-2)])

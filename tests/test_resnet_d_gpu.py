@@ -1,5 +1,5 @@
-"""The ResNet-D variants on the GPU: whole-network parity of resnet50d, resnet18d and seresnext26d_32x4d against the tests-side
-reference (tests/_resnetd_ref.py) by the protocol of tests/test_resnet_family_gpu.py; the deep stem and the pooled shortcut
+"""The ResNet-D variants on the GPU: whole-network parity of resnet50d, resnet18d and seresnext26d_32x4d against the oracle
+(oracle/resnet_ref.py) by the protocol of tests/test_resnet_family_gpu.py; the deep stem and the pooled shortcut
 checked op by op on the HIP path's own tensors; the ICAMD_STEM_THIN routes against each other; one finite step of the two
 largest members; eval, state_dict, engine, command line and reproducibility for resnet50d."""
 import copy
@@ -14,31 +14,14 @@ import torch.nn.functional as F
 from oracle import ops_ref as R
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from _resnetd_ref import ResNetDRef  # noqa: E402
-from oracle.resnet_ref import _Block  # noqa: E402
+from _resnet_parity import (assert_hip_within_yardstick, hip_rows, parity_batch, perturbed_bn_pair, set_last_gamma,  # noqa: E402
+                            timm_default_pair, xent_backward, yardstick)
+from oracle.resnet_ref import ResNetRef  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = torch.device("cuda")
 F64 = torch.float64
-
-
-def _xent_backward(net, ws, targets, num_classes, smoothing=0.0):
-    from imageclassification_amd import hip
-    lib = net.lib
-    B = targets.shape[0]
-    hip.check(lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, num_classes, targets.data_ptr(), None, 1.0,
-                                     smoothing, 1.0 / B, ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(),
-                                     ws["dlogits"].data_ptr(), hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
-    return float(ws["loss_rows"].mean())
-
-
-def _set_last_gamma(ref, value):
-    for m in ref.modules():
-        if isinstance(m, _Block):
-            m.last_bn.weight.data.fill_(value)
 
 
 # arch, tensors with a gradient
@@ -49,58 +32,29 @@ PARITY = [("resnet50d", 167), ("resnet18d", 68), ("seresnext26d_32x4d", 127)]
 def test_whole_network_parity_well_conditioned(arch, ntensors):
     """Batch 32 at 128 x 128, 100 classes, label smoothing 0.1, timm-default init, the last BatchNorm weight of every block at
     0.02 (every tensor compared).  The yardstick -- the reference against its own fp64 copy -- is asserted first under the caps
-    of tests/test_resnet_family_gpu.py (8e-3, 0.13, 0.22; measured on a CPU: resnet50d logits 5.1e-3 / mean 0.116 / worst 0.189,
-    resnet18d 4.7e-3 / 0.074 / 0.160, seresnext26d_32x4d 4.9e-3 / 0.101 / 0.180).  Then the HIP path: logits <= 2 max(noise,
+    of tests/test_resnet_family_gpu.py (8e-3, 0.13, 0.22; measured on a CPU: resnet50d logits 5.3e-3 / mean 0.111 / worst 0.182,
+    resnet18d 4.4e-3 / 0.072 / 0.174, seresnext26d_32x4d 4.9e-3 / 0.085 / 0.161).  Then the HIP path: logits <= 2 max(noise,
     1e-3), loss to 1e-3, mean gradient error <= 2 max(mean noise, 1e-3), per tensor <= 3 max(its noise, 5e-3)."""
-    from imageclassification_amd.nets import ResNet
     C, B, HW = 100, 32, 128
-    torch.manual_seed(0)
-    ref = ResNetDRef(arch, C, bf16_points=True, zero_init_last=True)
-    _set_last_gamma(ref, 0.02)
-    net = ResNet(arch, C)
-    net.load_state_dict(ref.state_dict())
-    ref64 = copy.deepcopy(ref).double()
-    g = torch.Generator().manual_seed(5)
-    x = torch.randn(B, 3, HW, HW, generator=g)
-    y = torch.randint(0, C, (B,), generator=g)
-    ref.train(); ref64.train()
-    out = ref(x)
-    loss = F.cross_entropy(out, y, label_smoothing=0.1)
-    loss.backward()
-    out64 = ref64(x.double())
-    loss64 = F.cross_entropy(out64, y, label_smoothing=0.1)
-    loss64.backward()
-
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    hip_loss = _xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
-    got = logits[:, :C].float().cpu()
-    noise_logits = R.rel_l2(out64.detach().float(), out.detach())
-    err_logits = R.rel_l2(got, out.detach())
-    p64 = dict(ref64.named_parameters())
-    rows = []
-    for name, p in ref.named_parameters():
-        assert float(p.grad.abs().max()) > 0.0, name
-        rows.append((name, R.rel_l2(net.grad_of(name), p.grad), R.rel_l2(p64[name].grad.float(), p.grad)))
-    mean_e = sum(r[1] for r in rows) / len(rows)
-    mean_n = sum(r[2] for r in rows) / len(rows)
-    worst = max(rows, key=lambda r: r[1])
-    print(f"{arch} B={B} {HW}x{HW}: logits err {err_logits:.2e} (self-noise {noise_logits:.2e}); loss {hip_loss:.6f} vs "
-          f"{float(loss):.6f}; {len(rows)} gradient tensors: mean err {mean_e:.2e} (self-noise {mean_n:.2e}), worst {worst[0]} "
-          f"{worst[1]:.2e} (its self-noise {worst[2]:.2e}), yardstick worst {max(r[2] for r in rows):.2e}")
+    ref, net = timm_default_pair(arch, C, gamma_last=0.02)
+    x, y = parity_batch(C, B, HW)
+    yard = yardstick(ref, x, y, 0.1)
+    for name, grad in yard.grads.items():
+        assert float(grad.abs().max()) > 0.0, name
+    got = hip_rows(net, x, y, C, 0.1, yard)
+    rows, worst = got.rows, got.worst
+    print(f"{arch} B={B} {HW}x{HW}: logits err {got.err_logits:.2e} (self-noise {yard.noise_logits:.2e}); loss {got.loss:.6f} vs "
+          f"{yard.loss:.6f}; {len(rows)} gradient tensors: mean err {got.mean_err:.2e} (self-noise {yard.mean_noise:.2e}), worst "
+          f"{worst[0]} {worst[1]:.2e} (its self-noise {worst[2]:.2e}), yardstick worst {yard.worst_noise[1]:.2e}")
     for name, e, n in rows:
         if name.startswith(("conv1.", "bn1.")) or "downsample" in name:
             print(f"    {name:32s} HIP {e:.2e} yardstick {n:.2e}")
     # the yardstick itself
-    assert noise_logits <= 8e-3 and mean_n <= 0.13 and max(r[2] for r in rows) <= 0.22, (noise_logits, mean_n)
+    assert yard.noise_logits <= 8e-3 and yard.mean_noise <= 0.13 and yard.worst_noise[1] <= 0.22, \
+        (yard.noise_logits, yard.mean_noise)
     assert len(rows) == ntensors
     # the HIP path against it
-    assert err_logits <= 2.0 * max(noise_logits, 1e-3)
-    assert abs(hip_loss - float(loss)) <= 1e-3 * abs(float(loss))
-    assert mean_e <= 2.0 * max(mean_n, 1e-3)
-    for name, e, n in rows:
-        assert e <= 3.0 * max(n, 5e-3), (name, e, n)
+    assert_hip_within_yardstick(yard, got)
 
 
 # ------------------------------------------------------------------------------------------------ teacher-forced stem and shortcut
@@ -148,7 +102,7 @@ def test_stem_and_pooled_shortcut_op_by_op(HW):
             seen[bi] = (gb[2].clone(), gb[3].clone(), other.clone())
 
     net.grad_ready_hook = hook
-    _xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
+    xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
     net.grad_ready_hook = None
 
     def stats_of(bn):
@@ -246,7 +200,7 @@ for _ in range(%(repeat)d):
     net.train()
     ws = net.pack(x.cuda())
     logits = net.forward_packed(ws)
-    loss = T._xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
+    loss = T.xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
     runs.append((logits[:, :C].float().cpu().clone(), net.grad_arena.cpu().clone()))
 assert all(torch.equal(r[0], runs[0][0]) and torch.equal(r[1], runs[0][1]) for r in runs), "not bitwise repeatable"
 grads = {name: net.grad_of(name) for name in net.params}
@@ -300,7 +254,7 @@ def test_largest_members_take_one_finite_step(arch):
     net.train()
     ws = net.pack(x.cuda())
     logits = net.forward_packed(ws)
-    loss = _xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
+    loss = xent_backward(net, ws, y.cuda(), C, smoothing=0.1)
     assert torch.isfinite(logits[:, :C].float()).all() and loss == loss and abs(loss) < 1e3
     assert torch.isfinite(net.grad_arena).all()
     for name in ("conv1.0.weight", "conv1.3.weight", "conv1.6.weight", "layer2.0.downsample.1.weight", "layer3.20.conv2.weight",
@@ -308,43 +262,29 @@ def test_largest_members_take_one_finite_step(arch):
         assert float(net.grad_of(name).abs().max()) > 0.0, name
 
 
-def _is_bn_key(k):
-    return "bn" in k or "downsample.2" in k or k.startswith(("conv1.1.", "conv1.4."))
-
-
-def _resnet50d_pair(C, seed):
-    from imageclassification_amd.nets import ResNet
-    torch.manual_seed(seed)
-    ref = ResNetDRef("resnet50d", C, bf16_points=True, zero_init_last=False)
-    g = torch.Generator().manual_seed(seed + 1)
-    sd = ref.state_dict()
-    for k, v in sd.items():
-        if k.endswith("running_mean"):
-            sd[k] = torch.randn(v.shape, generator=g) * 0.2
-        elif k.endswith("running_var"):
-            sd[k] = torch.rand(v.shape, generator=g) + 0.5
-        elif _is_bn_key(k) and k.endswith(".weight"):
-            sd[k] = torch.rand(v.shape, generator=g) + 0.5
-        elif _is_bn_key(k) and k.endswith(".bias"):
-            sd[k] = torch.randn(v.shape, generator=g) * 0.1
-    ref.load_state_dict(sd)
-    net = ResNet("resnet50d", C)
-    net.load_state_dict(sd)
-    return ref, net, sd
-
-
 @pytest.mark.parametrize("HW", [64, 72])
 def test_resnet50d_eval_folded_and_state_dict_round_trip(HW):
+    """Folded and unfolded eval logits against the reference's fp32 arithmetic, <= 1e-2 each.  At batch 4 the bf16-points
+    reference's own distance d from its fp32 arithmetic swings with the weight draw between 4e-3 and 1.0e-2 (measured on a CPU,
+    seeds 4 .. 12).  The HIP paths round at other points or in another order, so their distance is a second sample of the same
+    noise, up to sqrt(2) d for two independent errors of size d: the bound holds only where d <= 1e-2 / 1.5, asserted first as
+    <= 6.5e-3 (as tests/test_seresnet_gpu.py).  Seed 10 (4.9e-3 at 64 x 64, 4.3e-3 at 72 x 72) is the first seed from 4 up that
+    meets it at both sizes; seed 4 stopped meeting it (1.01e-2 at 64 x 64, the unfolded HIP path at 1.14e-2) when the oracle
+    stopped constructing layers it threw away, which moved the seeded draw of every member but resnet18/34/50."""
     from imageclassification_amd.nets import ResNet
     C = 10
-    ref, net, sd = _resnet50d_pair(C, seed=4)
+    ref, net, sd = perturbed_bn_pair("resnet50d", C, seed=10)
     x = torch.randn(4, 3, HW, HW, generator=torch.Generator().manual_seed(10))
-    exact = ResNetDRef("resnet50d", C, bf16_points=False, zero_init_last=False)   # the reference's fp32 arithmetic
+    exact = ResNetRef("resnet50d", C, bf16_points=False, zero_init_last=False)   # the reference's fp32 arithmetic
     exact.load_state_dict(sd)
     exact.eval()
     net.eval()
+    ref.eval()
     with torch.no_grad():
         want = exact(x)
+        rounded = ref(x)
+    print(f"resnet50d {HW}x{HW} eval: the bf16-points reference vs its fp32 arithmetic {R.rel_l2(rounded, want):.2e}")
+    assert R.rel_l2(rounded, want) <= 6.5e-3          # the condition under which the bound below can be held
     assert net.fold_eval
     folded = net(x.cuda()).float().cpu()
     net.fold_eval = False
@@ -372,10 +312,10 @@ def test_resnet50d_eval_unfolded_by_environment(tmp_path):
             "import torch\n"
             "import test_resnet_d_gpu as T\n"
             "from oracle import ops_ref as R\n"
-            "ref, net, sd = T._resnet50d_pair(10, seed=4)\n"
+            "ref, net, sd = T.perturbed_bn_pair('resnet50d', 10, seed=4)\n"
             "assert not net.fold_eval\n"
             "x = torch.randn(4, 3, 72, 72, generator=torch.Generator().manual_seed(10))\n"
-            "exact = T.ResNetDRef('resnet50d', 10, bf16_points=False, zero_init_last=False)\n"
+            "exact = T.ResNetRef('resnet50d', 10, bf16_points=False, zero_init_last=False)\n"
             "exact.load_state_dict(sd); exact.eval(); net.eval()\n"
             "with torch.no_grad():\n"
             "    want = exact(x)\n"
@@ -400,8 +340,8 @@ def test_resnet50d_engine_step_evaluate_and_bitwise_repeat():
     from oracle import engine_ref as E
     C, B = 10, 8
     torch.manual_seed(0)
-    ref = ResNetDRef("resnet50d", C, bf16_points=True, zero_init_last=False)
-    _set_last_gamma(ref, 0.02)
+    ref = ResNetRef("resnet50d", C, bf16_points=True, zero_init_last=False)
+    set_last_gamma(ref, 0.02)
     net = ResNet("resnet50d", C)
     net.load_state_dict(ref.state_dict())
     start = copy.deepcopy(ref.state_dict())
@@ -412,7 +352,7 @@ def test_resnet50d_engine_step_evaluate_and_bitwise_repeat():
     for _ in range(2):
         ws = net.pack(data[0][0].cuda())
         net.forward_packed(ws)
-        loss = _xent_backward(net, ws, data[0][1].cuda(), C, smoothing=0.1)
+        loss = xent_backward(net, ws, data[0][1].cuda(), C, smoothing=0.1)
         runs.append((loss, net.grad_arena.clone(), ws["logits"].clone()))
         net.load_state_dict(ref.state_dict())      # running statistics back to the start
     assert runs[0][0] == runs[1][0]

@@ -1,5 +1,5 @@
 """The ResNet family beyond ResNet-18/34/50 (resnet101/152, wide_resnet50_2/101_2, resnext50/101_32x4d), the parts that need no GPU:
-the tests-side reference has the published parameter counts and torchvision / timm names, the product's ARCHS rows describe
+the oracle has the published parameter counts and torchvision / timm names, the product's ARCHS rows describe
 the same graph, the three existing names are unchanged, and the host-only entries of the grouped-convolution ABI answer."""
 import ctypes
 import os
@@ -10,8 +10,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _resnext_ref import FAMILY, ResNetFamilyRef  # noqa: E402
-from oracle.resnet_ref import ResNetRef  # noqa: E402
+from _resnet_parity import named_shapes  # noqa: E402
+from oracle.resnet_ref import ARCHS, ResNetRef  # noqa: E402
 
 PUBLISHED = {
     "resnet101": 44549160,
@@ -25,13 +25,9 @@ PUBLISHED = {
 RESNEXT50_CONV2 = [(128, 56, 1), (256, 56, 2), (256, 28, 1), (512, 28, 2), (512, 14, 1), (1024, 14, 2), (1024, 7, 1)]
 
 
-def _named_shapes(model):
-    return [(n, tuple(p.shape)) for n, p in model.named_parameters()]
-
-
 @pytest.mark.parametrize("arch", sorted(PUBLISHED))
 def test_reference_parameter_counts_and_names(arch):
-    ref = ResNetFamilyRef(arch, 1000)
+    ref = ResNetRef(arch, 1000)
     assert sum(p.numel() for p in ref.parameters()) == PUBLISHED[arch]
     sd = ref.state_dict()
     assert tuple(sd["conv1.weight"].shape) == (64, 3, 7, 7)
@@ -51,10 +47,10 @@ def test_reference_parameter_counts_and_names(arch):
 def test_product_archs_describe_the_same_graph(arch):
     from imageclassification_amd import nets
     assert arch in nets.ARCHS
-    assert nets.param_shapes(arch, 1000) == _named_shapes(ResNetFamilyRef(arch, 1000))
+    assert nets.param_shapes(arch, 1000) == named_shapes(ResNetRef(arch, 1000))
     assert nets.param_shapes(arch, 10)[-2:] == [("fc.weight", (10, 2048)), ("fc.bias", (10,))]
     groups = {c[0]: c[6] for blk in nets.block_specs(arch) for c in blk["convs"]}
-    want = FAMILY[arch][2]
+    want = ARCHS[arch][2]
     assert all(g == (want if n.endswith(".conv2") else 1) for n, g in groups.items())
 
 
@@ -62,8 +58,8 @@ def test_product_archs_describe_the_same_graph(arch):
 def test_existing_names_unchanged(arch):
     from imageclassification_amd import nets
     ref = ResNetRef(arch, 1000)
-    assert nets.param_shapes(arch, 1000) == _named_shapes(ref)
-    assert _named_shapes(ResNetFamilyRef(arch, 1000)) == _named_shapes(ref)
+    assert nets.param_shapes(arch, 1000) == named_shapes(ref)
+    assert tuple(nets.ARCHS[arch][:4]) == tuple(ARCHS[arch][:4])
     assert all(c[6] == 1 for blk in nets.block_specs(arch) for c in blk["convs"])
 
 

@@ -1,4 +1,4 @@
-"""SE-ResNet / SE-ResNeXt (seresnet50/101/152, seresnext50/101_32x4d), the parts that need no GPU: the tests-side reference has the
+"""SE-ResNet / SE-ResNeXt (seresnet50/101/152, seresnext50/101_32x4d), the parts that need no GPU: the oracle has the
 published parameter counts and timm's key order, the product's ARCHS rows describe the same graph, the nine older names are
 unchanged, the host-only entries of the SE ABI answer, and the backward-in-sums identity the kernels implement agrees with
 autograd in fp64."""
@@ -10,8 +10,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _resnext_ref import FAMILY, ResNetFamilyRef  # noqa: E402
-from _seresnet_ref import SE_FAMILY, SEResNetRef  # noqa: E402
+from _resnet_parity import named_shapes  # noqa: E402
+from oracle.resnet_ref import ARCHS, ResNetRef  # noqa: E402
 
 PUBLISHED = {
     "seresnet50": 28088024,
@@ -26,21 +26,17 @@ SE_SYMBOLS = ("icamd_se_squeeze_workspace_bytes", "icamd_se_squeeze", "icamd_se_
 TAILS = [(256, 3136), (512, 784), (1024, 196), (2048, 49)]
 
 
-def _named_shapes(model):
-    return [(n, tuple(p.shape)) for n, p in model.named_parameters()]
-
-
 @pytest.mark.parametrize("arch", sorted(PUBLISHED))
 def test_reference_parameter_counts(arch):
-    ref = SEResNetRef(arch, 1000)
+    ref = ResNetRef(arch, 1000)
     assert sum(p.numel() for p in ref.parameters()) == PUBLISHED[arch]
-    plain = ResNetFamilyRef(arch[2:], 1000)
-    extra = sum(2 * c * (c // 16) + c // 16 + c for c, n in zip([256, 512, 1024, 2048], SE_FAMILY[arch][1]) for _ in range(n))
+    plain = ResNetRef(arch[2:], 1000)
+    extra = sum(2 * c * (c // 16) + c // 16 + c for c, n in zip([256, 512, 1024, 2048], ARCHS[arch][1]) for _ in range(n))
     assert PUBLISHED[arch] == sum(p.numel() for p in plain.parameters()) + extra
 
 
 def test_reference_key_names_and_order():
-    sd = SEResNetRef("seresnet50", 10).state_dict()
+    sd = ResNetRef("seresnet50", 10).state_dict()
     keys = list(sd)
     i = keys.index("layer1.0.bn3.num_batches_tracked")
     assert keys[i + 1:i + 6] == ["layer1.0.se.fc1.weight", "layer1.0.se.fc1.bias", "layer1.0.se.fc2.weight", "layer1.0.se.fc2.bias",
@@ -52,7 +48,7 @@ def test_reference_key_names_and_order():
     assert tuple(sd["layer4.2.se.fc2.weight"].shape) == (2048, 128, 1, 1) and tuple(sd["layer4.2.se.fc2.bias"].shape) == (2048,)
     # timm's init: Kaiming-normal (fan_out) on both SE weights, nn.Conv2d's default U(+-1/sqrt(fan_in)) on the biases
     torch.manual_seed(0)
-    ref = SEResNetRef("seresnet50", 10)
+    ref = ResNetRef("seresnet50", 10)
     w = ref.layer3[0].se.fc2.weight
     assert abs(float(w.detach().std()) / (2.0 / 1024) ** 0.5 - 1.0) <= 0.05
     b = ref.layer3[0].se.fc1.bias
@@ -63,21 +59,21 @@ def test_reference_key_names_and_order():
 def test_product_archs_describe_the_same_graph(arch):
     from imageclassification_amd import nets
     assert arch in nets.ARCHS and nets.has_se(arch)
-    assert nets.param_shapes(arch, 1000) == _named_shapes(SEResNetRef(arch, 1000))
+    assert nets.param_shapes(arch, 1000) == named_shapes(ResNetRef(arch, 1000))
     assert sum(torch.Size(s).numel() for _, s in nets.param_shapes(arch, 1000)) == PUBLISHED[arch]
     specs = nets.block_specs(arch)
     assert all(blk["se"] == (blk["name"] + ".se", blk["convs"][-1][2], blk["convs"][-1][2] // 16) for blk in specs)
     groups = {c[0]: c[6] for blk in specs for c in blk["convs"]}
-    assert all(g == (SE_FAMILY[arch][2] if n.endswith(".conv2") else 1) for n, g in groups.items())
+    assert all(g == (ARCHS[arch][2] if n.endswith(".conv2") else 1) for n, g in groups.items())
 
 
-@pytest.mark.parametrize("arch", sorted(FAMILY))
+@pytest.mark.parametrize("arch", sorted(a for a, row in ARCHS.items() if not row[4] and not row[5]))
 def test_existing_names_unchanged(arch):
     from imageclassification_amd import nets
     assert not nets.has_se(arch)
-    assert nets.param_shapes(arch, 1000) == _named_shapes(ResNetFamilyRef(arch, 1000))
+    assert nets.param_shapes(arch, 1000) == named_shapes(ResNetRef(arch, 1000))
     assert all(blk["se"] is None for blk in nets.block_specs(arch))
-    assert tuple(nets.ARCHS[arch][:4]) == tuple(FAMILY[arch])
+    assert tuple(nets.ARCHS[arch][:4]) == tuple(ARCHS[arch][:4])
 
 
 def test_train_cli_lists_the_new_names():
