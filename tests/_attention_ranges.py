@@ -20,6 +20,7 @@ of dQ is scale * sum_j dS_ij = 0 in exact arithmetic (rows of dS sum to zero).  
 columns and over the others separately, and holds dQ's D0 column absolutely (dq_d0_excess)."""
 import torch
 
+from _harness import rnd_bf16
 from oracle import ops_ref as R
 
 D = 64
@@ -56,11 +57,6 @@ def head_offset(pair):
 
 def shift_constants(T, offset=0):
     return torch.tensor([CYCLE[(i + offset) % len(CYCLE)] for i in range(T)])
-
-
-def rnd_bf16(*shape, seed):
-    g = torch.Generator().manual_seed(seed)
-    return R.bf16_round(torch.randn(*shape, generator=g))
 
 
 def operands(regime, B, T, H):

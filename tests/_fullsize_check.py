@@ -50,6 +50,12 @@ def block_rel_l2(got, ref, row_ids=None, block=BLOCK):
     return rel, present
 
 
+def worst_block(got, ref):
+    """largest rel L2 error over the 64 x 64 blocks of an output (for the tests' printed figures)"""
+    rel, present = block_rel_l2(got.reshape(ref.shape[0], -1), ref.reshape(ref.shape[0], -1))
+    return float(rel[present].max())
+
+
 def _blocks(got, ref, row_ids, bound):
     rel, present = block_rel_l2(got, ref, row_ids)
     bad = ~(rel <= bound) & present[:, None]

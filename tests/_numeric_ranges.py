@@ -21,14 +21,10 @@ import math
 
 import torch
 
+from _harness import rnd_bf16
 from oracle import ops_ref as R
 
 F64 = torch.float64
-
-
-def rnd_bf16(*shape, scale=1.0, seed):
-    g = torch.Generator().manual_seed(seed)
-    return R.bf16_round(torch.randn(*shape, generator=g) * scale)
 
 
 def on_bf16_grid(t):

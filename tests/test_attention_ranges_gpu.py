@@ -1,8 +1,7 @@
 """The four attention kernel families outside the logit band `randn` operands keep them in: rows shifted by -160 ... +128 (lse from
 about -157 to +134 inside one 16-row block), peaked and flat softmax, large and small v and dO.  Operands, references and bounds are
 those of tests/_attention_ranges.py (checked on the CPU by tests/test_attention_ranges_cpu.py); the launches go through the
-guarded-buffer run() helpers of tests/test_attention_long_gpu.py and tests/test_window_attention_gpu.py, so the guard bands are held
-too.
+guarded-buffer run() helpers of tests/_attention_long.py and tests/_window_attention.py, so the guard bands are held too.
 
   resident (csrc/attention.hip)           <4>: T = 17, 50, 64 (64 has no pad keys); <13>: T = 100, 197, 208; and one case with more
                                           (image, head) pairs than the grid cap, so every persistent workgroup hands over to a second head
@@ -19,32 +18,20 @@ e_round being the rounding-point ORACLE against the exact one.
 What this file found when it was written: both dQ kernels of the dense routes (attn_bwd_dq_kernel, attn_long_bwd_dq_kernel) formed
 p = exp(0 - lse) for the zero-filled key rows past T without a mask; for a query with lse below about -88.7 that is +inf, dS = inf
 * (0 - delta), and the K^T dS product spread 0 * inf = NaN over the whole dq row."""
-import os
-import sys
-
 import pytest
 import torch
 
+import _attention_long as AL
+import _attention_ranges as AR
+import _window_attention as WA
+from _harness import lib  # noqa: F401
+from _swin_ref import window_attention_ref
 from oracle import ops_ref as R
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-import _attention_ranges as AR  # noqa: E402
-import test_attention_long_gpu as AL  # noqa: E402
-import test_window_attention_gpu as WA  # noqa: E402
-from _swin_ref import window_attention_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 D, SCALE = AR.D, AR.SCALE
 assert (AL.D, AL.SCALE) == (D, SCALE)
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
 
 
 def case_id(c):

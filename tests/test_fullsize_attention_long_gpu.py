@@ -2,12 +2,12 @@
 768 (image, head) pairs x 5 blocks of 128 rows = 3840 workgroups per kernel, several rounds of every CU, in the XCD-grouped order
 of csrc/attention_long.hip), default routing.  A subset of the images is compared with oracle/ops_ref.py accumulated in fp64 on
 the GPU, under the bounds tests/test_fullsize_layers_gpu.py applies to the same entries at T = 197 (vit_attention there)."""
-import os
-
 import pytest
 import torch
 
 from _fullsize_check import check_bf16, check_close, require
+from _harness import default_routing_lib as lib  # noqa: F401
+from _harness import rnd_dev as rnd
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -15,21 +15,6 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 F64 = torch.float64
 B, T, H, D = 64, 577, 12, 64
-
-
-@pytest.fixture(scope="module")
-def lib():
-    routed = sorted(k for k in os.environ if k.startswith("ICAMD_"))
-    # a routing switch in the environment would test some other route than the default: a failure, not a skip
-    assert not routed, f"this module checks the default routing; unset {routed}"
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def rnd(shape, seed):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    return torch.randn(shape, generator=g, device=DEV).to(torch.bfloat16)
 
 
 def test_vit_b16_384_attention_768_pairs(lib):

@@ -8,6 +8,9 @@ import pytest
 import torch
 
 from _fullsize_check import check_bf16, check_fp32, check_stats, require, sample_rows
+from _harness import free_after_each  # noqa: F401
+from _harness import lib  # noqa: F401
+from _harness import rnd_dev as rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -17,28 +20,6 @@ N = 256
 GROUPS = 32
 # (C, input grid, stride): layer1.*, layer2.0, layer2.1-3, layer3.0, layer3.1-5, layer4.0, layer4.1-2
 SHAPES = [(128, 56, 1), (256, 56, 2), (256, 28, 1), (512, 28, 2), (512, 14, 1), (1024, 14, 2), (1024, 7, 1)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-@pytest.fixture(autouse=True)
-def _free():
-    yield
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-
-def rnd(shape, seed, scale=1.0, relu=False):
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    t = torch.randn(shape, generator=g, device=DEV) * scale
-    if relu:
-        t = t.clamp_min(0)
-    return t.to(torch.bfloat16)
 
 
 def _taps(xp, r, s, st, OH, OW):

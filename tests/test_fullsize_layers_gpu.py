@@ -10,12 +10,16 @@ rounding points as the kernel -- accumulated in fp64 on the GPU.  Bounds are tho
 same entry, plus rel L2 <= 2e-3 in every 64 x 64 block (tests/_fullsize_check.py), which one wrong tile cannot pass.
 """
 import ctypes
-import os
 
 import pytest
 import torch
 
+import _harness
 from _fullsize_check import check_bf16, check_close, check_fp32, check_stats, require
+from _harness import default_routing_lib as lib  # noqa: F401
+from _harness import free_after_each  # noqa: F401
+from _harness import rnd_dev as rnd
+from _harness import sync
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -38,44 +42,9 @@ CNX_N = 256
 CNX_STAGES = [(96, 56), (192, 28), (384, 14), (768, 7)]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    routed = sorted(k for k in os.environ if k.startswith("ICAMD_"))
-    # a routing switch in the environment would test some other route than the benchmark's: a failure, not a skip
-    assert not routed, f"this module checks the default routing; unset {routed}"
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-@pytest.fixture(autouse=True)
-def _free():
-    yield
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def rnd(shape, seed, scale=1.0, relu=False, shift=0.0):
-    """Seeded normal values on the GPU, rounded to bf16 (post-ReLU inputs: clamped at zero, so mask bits are non-trivial)."""
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    t = torch.randn(shape, generator=g, device=DEV) * scale + shift
-    if relu:
-        t = t.clamp_min(0)
-    return t.to(torch.bfloat16)
-
-
 def urand(n, seed, lo, hi):
     g = torch.Generator(device=DEV).manual_seed(seed)
     return torch.rand(n, generator=g, device=DEV) * (hi - lo) + lo
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 def ok(rc, what):
@@ -105,7 +74,7 @@ def _conv_id(c):
 def resnet_conv_fwd_bn(lib, c, seed):
     """icamd_conv2d_fwd with statistics, then the BatchNorm that follows it: icamd_bn_train_finalize (multi-chunk reduce
     wherever M > 65 536), icamd_bn_apply (+ residual on the expansion convs, mask bits), icamd_bn_bwd."""
-    hip = _hip()
+    hip = _harness.hip()
     cin, cout, k, st, h = c
     pad = k // 2
     N = TRAIN_N
@@ -163,7 +132,7 @@ def resnet_conv_fwd_bn(lib, c, seed):
 
 def resnet_conv_dgrad(lib, c, seed):
     """icamd_conv2d_dgrad plain, with a bf16 addend, and (1x1 stride-1 layers) with the mask-bit addend."""
-    hip = _hip()
+    hip = _harness.hip()
     cin, cout, k, st, h = c
     pad = k // 2
     N = TRAIN_N
@@ -194,7 +163,7 @@ def resnet_conv_dgrad(lib, c, seed):
 
 def resnet_conv_wgrad(lib, c, seed):
     """icamd_conv2d_wgrad (planner-chosen kernel, split and workgroup order at the real grid) and its bias form."""
-    hip = _hip()
+    hip = _harness.hip()
     cin, cout, k, st, h = c
     pad = k // 2
     N = TRAIN_N
@@ -220,7 +189,7 @@ def resnet_conv_wgrad(lib, c, seed):
 
 def resnet_stem(lib, seed):
     """The 7x7 / stride-2 stem on the rgb4 layout: forward with statistics, and the weight gradient."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, Cout = TRAIN_N, 224, 64
     x = rnd((N, 3, H, H), seed).float()
     w = rnd((Cout, 7, 7, 3), seed + 1, scale=(1.0 / 147) ** 0.5).float()
@@ -256,7 +225,7 @@ def resnet_stem(lib, seed):
 def resnet_bn_apply_conv1x1_fused(lib, c, seed, res_bn):
     """icamd_bn_apply_conv1x1_fused at a layer1 / layer2 shape: out = relu(bn3(y3) + shortcut) with mask bits, y1 = conv1(out)
     of the next block with its statistics."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, K, Nout = c
     d = hip.conv_desc(N, h, h, K, Nout, 1, 1, 1, 0)
     assert lib.icamd_bn_apply_conv1x1_fused_supported(ctypes.byref(d)) == 1
@@ -305,7 +274,7 @@ def _bn_coeffs(y, C, gamma):
 
 def resnet_conv1x1_bn_bwd_fused(lib, c, seed):
     """icamd_conv1x1_bn_bwd_fused (conv3 + bn3 backward of a bottleneck) at a layer1 / layer2 shape."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, Cin, Cout = c
     d = hip.conv_desc(N, h, h, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d)) == 1
@@ -346,7 +315,7 @@ def resnet_conv1x1_bn_bwd_fused(lib, c, seed):
 def resnet_dgrad_bnred(lib, c, seed):
     """icamd_conv2d_dgrad_bnred (conv1 residual data gradient + the sums of the previous block's last BatchNorm backward),
     then icamd_bn_bwd_from_gy_partials on those sums."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, Cin, Cout = c
     d = hip.conv_desc(N, h, h, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d)) == 1
@@ -395,7 +364,7 @@ def resnet_stem_bn_pool(lib, seed):
     """The stem's tail: icamd_bn_relu_maxpool3x3s2_fwd on the 256 x 112 x 112 x 64 conv output, then the backward through
     the pool and the BatchNorm, both as nets.py runs them (icamd_maxpool3x3s2_bwd + icamd_bn_bwd) and folded
     (icamd_bn_bwd_maxpool3x3s2)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, C = TRAIN_N, 112, 64
     OH = 56
     y = rnd((N, H, H, C), seed, scale=1.5)
@@ -444,7 +413,7 @@ def resnet_stem_bn_pool(lib, seed):
 
 def resnet_bn_apply_res_bn(lib, c, seed):
     """icamd_bn_apply_res_bn: the block output of a projection block, relu(bn3(y3) + bn_d(y_d)), with its mask bits."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, C = c
     y, yd = rnd((N, h, h, C), seed, scale=1.3), rnd((N, h, h, C), seed + 1, scale=1.3)
     sc, sh = urand(C, seed + 2, 0.5, 1.5), urand(C, seed + 3, -0.3, 0.3)
@@ -462,7 +431,7 @@ def resnet_bn_apply_res_bn(lib, c, seed):
 
 def resnet_bn_bwd_dual(lib, c, seed):
     """icamd_bn_bwd_dual: the block-output BatchNorm and the shortcut BatchNorm backward of a projection block, one mask."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, C = c
     M = N * h * h
     gen = torch.Generator(device=DEV).manual_seed(seed)
@@ -490,7 +459,7 @@ def resnet_bn_bwd_dual(lib, c, seed):
 def resnet_dgrad_sub2(lib, c, seed):
     """icamd_conv2d_dgrad_sub2 (first block of stages 2-4, nets.py default): conv1's data gradient plus the 1x1 / stride-2
     shortcut's gradient, which lives on the even pixels only ([N][H/2][W/2][Cin] addend)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, Cin, Cout = c
     d = hip.conv_desc(N, h, h, Cin, Cout, 1, 1, 1, 0)
     dy = rnd((N, h, h, Cout), seed)
@@ -509,7 +478,7 @@ def resnet_dgrad_sub2(lib, c, seed):
 def resnet_dgrad_bnred_even(lib, c, seed):
     """icamd_conv2d_dgrad_bnred in its even-grid addend form (mode 1: the 1x1 / stride-2 shortcut's gradient of the next
     stage's first block, nets.py default where the pair is supported)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, Cin, Cout = c
     d = hip.conv_desc(N, h, h, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d)) == 1
@@ -535,7 +504,7 @@ def resnet_dgrad_bnred_even(lib, c, seed):
 
 def resnet_avgpool(lib, N, seed):
     """icamd_avgpool_fwd / _bwd over the 7 x 7 x 2048 features."""
-    hip = _hip()
+    hip = _harness.hip()
     HW, C = 49, 2048
     x = rnd((N, 7, 7, C), seed, relu=True)
     out = torch.empty(N, C, dtype=torch.bfloat16, device=DEV)
@@ -582,7 +551,7 @@ def test_resnet50_train(lib, case):
 # ============================================ ResNet-50, eval, batch 384 ============================================
 def resnet_eval_fold_act(lib, c, seed):
     """icamd_bn_fold_filters + icamd_conv2d_fwd_act (folded shift, optional residual and ReLU) at batch 384."""
-    hip = _hip()
+    hip = _harness.hip()
     cin, cout, k, st, h = c
     pad = k // 2
     N = EVAL_N
@@ -617,7 +586,7 @@ def resnet_eval_fold_act(lib, c, seed):
 
 def resnet_eval_stem_pool(lib, seed):
     """Eval stem at batch 384: icamd_stem7x7s2_fwd with the folded bias + ReLU in its epilogue, then icamd_maxpool3x3s2_fwd."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, Cout, OH = EVAL_N, 224, 64, 112
     x = rnd((N, 3, H, H), seed).float()
     w = rnd((Cout, 7, 7, 3), seed + 1, scale=(2.0 / 147) ** 0.5).float()
@@ -657,7 +626,7 @@ def linear_layer(lib, rows, cin, cout, seed, gelu_fwd=False, gelu_bwd=False, add
     """One Linear layer as the model runs it (a 1x1 convolution over `rows` pixels): forward (+bias, + residual addend, or
     GELU in the store pass), data gradient (GELU' in the store pass where the layer's input is a GELU output), weight
     gradient with the bias gradient."""
-    hip = _hip()
+    hip = _harness.hip()
     d = hip.conv_desc(rows, 1, 1, cin, cout, 1, 1, 1, 0)
     x = rnd((rows, 1, 1, cin), seed)
     if gelu_bwd:     # the layer's input is a GELU output
@@ -709,7 +678,7 @@ def linear_layer(lib, rows, cin, cout, seed, gelu_fwd=False, gelu_bwd=False, add
 def patch_conv(lib, N, H, cin_true, cout, k, seed, relu=False):
     """A k x k / stride-k patchifying convolution on the 8-channel packed input (ViT patch embedding, ConvNeXt stem) or on a
     feature map (ConvNeXt downsample): forward + bias, data gradient (feature-map inputs), weight gradient + bias."""
-    hip = _hip()
+    hip = _harness.hip()
     cin = 8 if cin_true == 3 else cin_true
     d = hip.conv_desc(N, H, H, cin, cout, k, k, k, 0)
     x = rnd((N, H, H, cin), seed, relu=relu)
@@ -749,7 +718,7 @@ def patch_conv(lib, N, H, cin_true, cout, k, seed, relu=False):
 
 
 def layernorm(lib, rows, C, seed, eps):
-    hip = _hip()
+    hip = _harness.hip()
     x = rnd((rows, C), seed, scale=2.0, shift=0.5)
     gamma, beta = urand(C, seed + 1, 0.5, 1.5), urand(C, seed + 2, -0.2, 0.2)
     y = torch.empty(rows, C, dtype=torch.bfloat16, device=DEV)
@@ -779,7 +748,7 @@ def vit_attention(lib, seed):
     """icamd_attention_fwd / _bwd at B = 256 (3072 (image, head) pairs over one persistent workgroup per CU: pair p runs in
     round p // #CUs of workgroup p % #CUs).  The reference covers images 0, 21, 128 and 234-255: heads 0, 255, 256 and 3071,
     and every pair from 234 * 12 = 2808 on -- the last round of every workgroup on a 256-CU device (pairs 2816-3071)."""
-    hip = _hip()
+    hip = _harness.hip()
     B, T, H, D = VIT_B, VIT_T, VIT_H, VIT_D
     scale = D ** -0.5
     qkv = rnd((B * T, 3 * H * D), seed)
@@ -816,7 +785,7 @@ def cnx_layerscale_tail(lib, C, h, seed):
     fc2 on the folded filter with the residual addend, icamd_rows_fix (dropped samples: out = x, their fc2 input zeroed);
     backward icamd_dropped_colsum, the weight gradient + bias, icamd_layerscale_param_grads, and the data gradient on the
     folded filter with its dropped rows zeroed."""
-    hip = _hip()
+    hip = _harness.hip()
     N, HW, K = CNX_N, h * h, 4 * C
     M = N * HW
     gen = torch.Generator(device=DEV).manual_seed(seed)
@@ -885,7 +854,7 @@ def cnx_layerscale_tail(lib, C, h, seed):
 def vit_tokens(lib, seed):
     """Token plumbing at B = 256: icamd_vit_tokens_fwd (class token + position embedding), icamd_batch_sum (their
     gradients), icamd_strided_rows_copy (class-token gather / scatter, patch gradients)."""
-    hip = _hip()
+    hip = _harness.hip()
     B, T, D = VIT_B, VIT_T, VIT_DIM
     patches = rnd((B, T - 1, D), seed)
     cls, pos = urand(D, seed + 1, -1, 1), urand(T * D, seed + 2, -1, 1).reshape(T, D)
@@ -912,7 +881,7 @@ def vit_tokens(lib, seed):
 
 def head_bias_colsum(lib, N, seed):
     """icamd_colsum: the classifier's bias gradient from dlogits [N][1024] (1000 classes padded)."""
-    hip = _hip()
+    hip = _harness.hip()
     dl = rnd((N, 1024), seed)
     out = torch.full((1024,), float("nan"), device=DEV)
     ok(lib.icamd_colsum(dl.data_ptr(), N, 1024, 1024, out.data_ptr(), 0, hip.stream_ptr()), "colsum")
@@ -944,7 +913,7 @@ def test_vit_b16(lib, case):
 # ============================================ ConvNeXt-T, batch 256 ============================================
 def dwconv7(lib, C, h, seed):
     """icamd_dwconv7_fwd / _dgrad (+ residual addend) / _wgrad_bias (or _wgrad where the one-pass form is refused)."""
-    hip = _hip()
+    hip = _harness.hip()
     N = CNX_N
     x = rnd((N, h, h, C), seed)
     w = rnd((C, 7, 7), seed + 1, scale=0.15)
@@ -1009,7 +978,7 @@ def test_checkers_reject_a_corrupted_copy_of_real_outputs(lib):
     """One case per checker kind on a real kernel output at a benchmark shape (ResNet-50 64 -> 256 1x1 at 56 x 56): the
     kernel's own output passes, a copy with one wrong 64 x 64 block / ragged-tile row / in-tile row position does not.
     Only the copy is changed."""
-    hip = _hip()
+    hip = _harness.hip()
     N, h, cin, cout = TRAIN_N, 56, 64, 256
     d = hip.conv_desc(N, h, h, cin, cout, 1, 1, 1, 0)
     x = rnd((N, h, h, cin), 11, relu=True)

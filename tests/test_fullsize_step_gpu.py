@@ -24,14 +24,17 @@ Wall time on an MI355X: 4.6 - 5.0 s for the 91 cases (three runs), 0.7 s of it b
 layer module's 25 s.  The fp64 references of the 86.6 M-element arenas cost 0.03 s per ViT-B/16 optimizer case; the slowest
 cases are the first loss case (0.4 s, first use of the fp64 softmax) and the first optimizer and gradient-norm cases (0.2 s).
 """
-import os
 import re
 
 import pytest
 import torch
 
+import _harness
 from _fullsize_check import (check_arena, check_bf16, check_bits, check_close, check_counts, check_fold, check_pred,
                              check_transposed, lowest_argmax, require)
+from _harness import default_routing_lib as lib  # noqa: F401
+from _harness import free_after_each  # noqa: F401
+from _harness import sync
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -50,16 +53,6 @@ ZERO_GRAD, NO_SKIP_COUNT = 1, 2
 
 
 @pytest.fixture(scope="module")
-def lib():
-    routed = sorted(k for k in os.environ if k.startswith("ICAMD_"))
-    # a routing switch in the environment would test some other route than the benchmark's: a failure, not a skip
-    assert not routed, f"this module checks the default routing; unset {routed}"
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-@pytest.fixture(scope="module")
 def models(lib):
     """The three benchmark models, built once: their arena sizes and job tables are what the cases run on."""
     from imageclassification_amd.convnext import ConvNeXt
@@ -67,18 +60,6 @@ def models(lib):
     from imageclassification_amd.vit import VisionTransformer
     return {"resnet50": ResNet("resnet50", 1000), "vit_b16": VisionTransformer("vit_base_patch16_224", 1000),
             "convnext_t": ConvNeXt("convnext_tiny", 1000, drop_path_rate=0.05)}
-
-
-@pytest.fixture(autouse=True)
-def _free():
-    yield
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
 
 
 def randn(n, seed, scale=1.0):
@@ -102,10 +83,6 @@ def sliced(n, seed, lo_exp=-4.0, hi_exp=2.0, slices=16):
     scale = 10.0 ** torch.linspace(lo_exp, hi_exp, slices, device=DEV)
     idx = (torch.arange(n, device=DEV) * slices // n).clamp_max(slices - 1)
     return t * scale[idx]
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 def ok(rc, what):
@@ -161,7 +138,7 @@ class OptState:
 
 
 def opt_launch(lib, name, bufs, n, step, gscale, clip, fin, skipped, flags, lo=0, hi=None, lr=LRS[2], wd=WDS[2]):
-    hip = _hip()
+    hip = _harness.hip()
     hi = n if hi is None else hi
     p, g, m, v, ema, shadow = bufs
 
@@ -279,7 +256,7 @@ def test_bucketed_adamw_is_bit_identical_to_one_launch(lib, models):
 
 
 def test_grad_guard_on_a_full_arena(lib, models):
-    hip = _hip()
+    hip = _harness.hip()
     n = models["vit_b16"].n_params
     g = randn(n, 130)
     g[n - 1] = float("nan")
@@ -298,7 +275,7 @@ def test_grad_guard_on_a_full_arena(lib, models):
 # ======================================== 2. gradient norm ========================================
 @pytest.mark.parametrize("model,tail", [(m, 0) for m in MODELS] + [("convnext_t", 3)], ids=MODELS + ["convnext_t-minus3"])
 def test_grad_norm(lib, models, model, tail):
-    hip = _hip()
+    hip = _harness.hip()
     n = models[model].n_params - tail
     assert n // 4 > 512 * 256 * 2
     g = sliced(models[model].n_params, 140 + MODELS.index(model))[:n]
@@ -323,7 +300,7 @@ def test_grad_norm(lib, models, model, tail):
 # ======================================== 3. EMA buffers and casts ========================================
 @pytest.mark.parametrize("which", ["vit_b16-params", "resnet50-buffers"])
 def test_lerp(lib, models, which):
-    hip = _hip()
+    hip = _harness.hip()
     n = models["vit_b16"].n_params if which == "vit_b16-params" else models["resnet50"].buffer_arena.numel()
     assert n > 50000
     dst0, src = randn(n, 150), randn(n, 151)
@@ -356,7 +333,7 @@ def test_f32_to_bf16(lib, models, model):
     """Bit-equal to torch's cast on a whole parameter arena, with the edge patterns planted in the first, a later and the
     last trip of the grid-stride loop.  fp32 denormals (no parameter is ever that small) are reported, not asserted: the
     hardware conversion may flush them."""
-    hip = _hip()
+    hip = _harness.hip()
     n = models[model].n_params
     assert n > 524288 * 2
     src = sliced(n, 160 + MODELS.index(model), -3.0, 1.0)
@@ -442,7 +419,7 @@ SENTINEL = 0x7A5B      # bf16 bit pattern of the rows behind row B
 
 
 def run_xent(lib, x, ld, y1, y2, lam, smoothing, gscale, want_pred=True, want_dl=True):
-    hip = _hip()
+    hip = _harness.hip()
     B, C = x.shape
     lp = torch.zeros(B, ld, dtype=torch.bfloat16, device=DEV)
     lp[:, :C] = x
@@ -517,7 +494,7 @@ def metrics_inputs(B, C, seed):
 
 
 def metrics_call(lib, loss, pred, target, B, C, st, slot, respect_skip):
-    hip = _hip()
+    hip = _harness.hip()
     ok(lib.icamd_step_metrics(hip.ptr(loss), hip.ptr(pred), target.data_ptr(), B, C, st["loss_out"].data_ptr(),
                               st["fin"].data_ptr(), st["acc"].data_ptr(), st["counts"].data_ptr(), st["log"].data_ptr(), slot,
                               8, respect_skip, hip.stream_ptr()), "step_metrics")
@@ -615,7 +592,7 @@ def pack_check(got, ref, mode, what):
 
 @pytest.mark.parametrize("case", PACK_CASES, ids=[c[0] for c in PACK_CASES])
 def test_pack_input(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     _, B, W, mode, box = case
     H, lam = 224, 0.37
     x = randn((B, 3, H, W), 200 + B + mode)
@@ -634,7 +611,7 @@ def test_pack_input(lib, case):
 
 @pytest.mark.parametrize("case", PACK_CASES_RGB4, ids=[c[0] for c in PACK_CASES_RGB4])
 def test_pack_input_rgb4(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     _, B, W, mode, box = case
     H, lam = 224, 0.37
     We = W + (W & 1)

@@ -10,6 +10,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _harness
+from _harness import dev, rnd_bf16, sync
+from _harness import lib  # noqa: F401
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -42,34 +45,9 @@ CASES = [
 ]
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def rnd_bf16(*shape, scale=1.0, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return R.bf16_round(torch.randn(*shape, generator=g) * scale)
-
-
-def dev(t):
-    return t.to(torch.bfloat16).to(DEV).contiguous()
-
-
-def sync():
-    torch.cuda.synchronize()
-
-
 def inputs(case):
     N, H, W, C, groups, st = case
-    hip = _hip()
+    hip = _harness.hip()
     d = hip.conv_desc(N, H, W, C, C, 3, 3, st, 1)
     cg = C // groups
     x = rnd_bf16(N, H, W, C, seed=1)
@@ -90,7 +68,7 @@ def ref_all(case, x, w, dy):
 
 
 def run_fwd(lib, d, groups, xd, wd, stats=None):
-    hip = _hip()
+    hip = _harness.hip()
     y = torch.full((d.N, d.OH, d.OW, d.Cout), float("nan"), dtype=torch.bfloat16, device=DEV)
     rc = lib.icamd_gconv3x3_fwd(ctypes.byref(d), groups, hip.ptr(xd), hip.ptr(wd), hip.ptr(y), hip.ptr(stats), hip.stream_ptr())
     assert rc == 0
@@ -99,7 +77,7 @@ def run_fwd(lib, d, groups, xd, wd, stats=None):
 
 
 def run_dgrad(lib, d, groups, dyd, wd):
-    hip = _hip()
+    hip = _harness.hip()
     dx = torch.full((d.N, d.IH, d.IW, d.Cin), float("nan"), dtype=torch.bfloat16, device=DEV)
     rc = lib.icamd_gconv3x3_dgrad(ctypes.byref(d), groups, hip.ptr(dyd), hip.ptr(wd), hip.ptr(dx), hip.stream_ptr())
     assert rc == 0
@@ -108,7 +86,7 @@ def run_dgrad(lib, d, groups, dyd, wd):
 
 
 def run_wgrad(lib, d, groups, xd, dyd, dw=None, accumulate=0):
-    hip = _hip()
+    hip = _harness.hip()
     cg = d.Cin // groups
     if dw is None:
         dw = torch.full((d.Cin, 3, 3, cg), float("nan"), device=DEV)
@@ -124,7 +102,7 @@ def run_wgrad(lib, d, groups, xd, dyd, dw=None, accumulate=0):
 
 @pytest.mark.parametrize("case", CASES)
 def test_gconv_fwd_stats_and_act(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C, groups, st = case
     d, x, w, dy = inputs(case)
     assert lib.icamd_gconv3x3_supported(ctypes.byref(d), groups) == 1
@@ -185,7 +163,7 @@ def test_gconv_dgrad(lib, case):
 
 @pytest.mark.parametrize("case", CASES)
 def test_gconv_wgrad(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C, groups, st = case
     d, x, w, dy = inputs(case)
     _, _, dw64 = ref_all(case, x, w, dy)
@@ -251,7 +229,7 @@ def expand_block_diagonal(w, groups):
 @pytest.mark.parametrize("case", [(2, 12, 12, 256, 32, 2), (4, 28, 28, 256, 32, 1), (2, 7, 7, 1024, 32, 1), (2, 9, 7, 128, 32, 1),
                                   (2, 15, 15, 512, 32, 2)])
 def test_gconv_agrees_with_dense_emulation(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C, groups, st = case
     cg = C // groups
     d, x, w, dy = inputs(case)
@@ -278,7 +256,7 @@ def test_gconv_agrees_with_dense_emulation(lib, case):
 
 
 def test_gconv_refusals_touch_nothing(lib):
-    hip = _hip()
+    hip = _harness.hip()
     bad = [
         (hip.conv_desc(2, 8, 8, 256, 256, 3, 3, 1, 1), 4),      # Cg = 64
         (hip.conv_desc(2, 8, 8, 128, 128, 1, 1, 1, 0), 32),     # 1x1

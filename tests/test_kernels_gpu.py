@@ -9,36 +9,15 @@ import os
 import pytest
 import torch
 
+import _harness
+from _harness import dev as to_dev_bf16
+from _harness import lib  # noqa: F401
+from _harness import rnd_bf16, sync
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def rnd_bf16(*shape, scale=1.0, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return R.bf16_round(torch.randn(*shape, generator=g) * scale)
-
-
-def to_dev_bf16(t):
-    return t.to(torch.bfloat16).to(DEV).contiguous()
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 CONV_CASES = [
@@ -62,7 +41,7 @@ CONV_CASES = [
 
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_fwd_with_stats_bias_addend(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     x = rnd_bf16(N, H, W, Cin, seed=1)
@@ -117,7 +96,7 @@ DGRAD_CASES = [
 
 @pytest.mark.parametrize("case", DGRAD_CASES)
 def test_conv_dgrad(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     dy = rnd_bf16(N, d.OH, d.OW, Cout, seed=5)
@@ -192,7 +171,7 @@ def _memo(key, fn, *inputs):
 
 
 def _run_large_pointwise(lib, cases):
-    hip = _hip()
+    hip = _harness.hip()
     for (N, H, W, Cin, Cout) in cases:
         case = (N, H, W, Cin, Cout)
         d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
@@ -333,7 +312,7 @@ def test_pointwise_large_tile_gemm_forced_small_k(tn):
 def test_conv_fwd_act_and_bn_fold(lib, case):
     """Inference epilogue: y = relu(conv(x, w_folded) + shift + residual) with w_folded/shift from icamd_bn_fold_filters,
     against eval-mode BatchNorm applied to the fp32 convolution of the same bf16 inputs (oracle)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     g = torch.Generator().manual_seed(31)
@@ -388,7 +367,7 @@ def test_pointwise_gelu_epilogues(lib, case):
     """fc1 forward with GELU in the store pass and fc2 data gradient with the GELU backward in the store pass are
     bit-identical to the two-kernel sequences they replace (and those are oracle-checked elsewhere); both GEMM kernels
     (128x128 implicit GEMM and the 256-row tile kernel, picked by size) are covered."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout = case
     d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
     x = to_dev_bf16(rnd_bf16(N, H, W, Cin, seed=41))
@@ -440,7 +419,7 @@ def test_conv3x3_halo_fwd_and_dgrad(lib, case):
     """The halo-staged 3x3 kernel (forward with BatchNorm statistics, inference form with bias + ReLU, and the data gradient
     = mirrored taps on the transposed filter) against torch's convolution: image borders, tiles that straddle images and
     rows, ragged last tiles, channel counts that are not a multiple of the tile."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C, Cout = case
     d = hip.conv_desc(N, H, W, C, Cout, 3, 3, 1, 1)
     x = rnd_bf16(N, H, W, C, seed=21)
@@ -524,7 +503,7 @@ def test_conv_wgrad_every_ring_tile_shape():
 
 @pytest.mark.parametrize("case", WGRAD_CASES)
 def test_conv_wgrad(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     x = rnd_bf16(N, H, W, Cin, seed=8)
@@ -566,7 +545,7 @@ def test_conv_wgrad(lib, case):
 
 
 def test_filter_transpose(lib):
-    hip = _hip()
+    hip = _harness.hip()
     shapes = [(64, 9, 64), (256, 1, 64), (128, 9, 128), (72, 1, 2048)]
     src_parts, descs, jobs = [], [], []
     off = 0
@@ -612,7 +591,7 @@ def test_filter_transpose(lib):
 
 @pytest.mark.parametrize("shape", [(4, 6, 6, 64), (2, 5, 5, 2048), (8, 20, 20, 128), (3, 7, 7, 96)])
 def test_bn_train_apply_and_bwd(lib, shape):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     g = torch.Generator().manual_seed(11)
     # the conv forward produces the statistics partials: run a 1x1 identity-like conv to get y and partials
@@ -700,7 +679,7 @@ def test_bn_train_apply_and_bwd(lib, shape):
 def test_bn_bwd_dual_matches_two_calls(lib, shape):
     """Block-output BatchNorm + shortcut BatchNorm backward in one reduce and one apply pass == two icamd_bn_bwd calls with
     the same mask bits: data gradients bit-identical, dgamma / dbeta equal, with and without accumulation."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     rows = N * H * W
     g = torch.Generator().manual_seed(120)
@@ -743,7 +722,7 @@ def test_bn_bwd_dual_matches_two_calls(lib, shape):
 
 @pytest.mark.parametrize("shape", [(2, 12, 12, 64), (3, 9, 11, 64), (1, 16, 16, 128)])
 def test_maxpool(lib, shape):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     x = rnd_bf16(N, H, W, C, seed=30).clamp_min(0)   # post-ReLU input: many exact ties at zero
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -769,7 +748,7 @@ def test_maxpool(lib, shape):
 def test_bn_bwd_with_maxpool_backward_folded_in_is_bit_identical(lib, shape):
     """icamd_bn_bwd_maxpool3x3s2 == icamd_maxpool3x3s2_bwd followed by icamd_bn_bwd (relu = 1, mask recomputed from y):
     input gradient, dgamma and dbeta bit for bit (the ResNet stem's backward; odd sizes, windows cut by the border)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     g = torch.Generator().manual_seed(130)
     y = to_dev_bf16(rnd_bf16(N, H, W, C, seed=131))
@@ -813,7 +792,7 @@ def test_bn_bwd_with_maxpool_backward_folded_in_is_bit_identical(lib, shape):
 def test_bn_apply_with_shortcut_batchnorm_is_bit_identical(lib):
     """Residual given as the raw shortcut conv output + its BatchNorm coefficients == BatchNorm-apply on the shortcut
     followed by the residual BatchNorm-apply (output and ReLU mask bits)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = 3, 7, 9, 256
     g = torch.Generator().manual_seed(95)
     y = to_dev_bf16(rnd_bf16(N, H, W, C, seed=96)); yd = to_dev_bf16(rnd_bf16(N, H, W, C, seed=97))
@@ -834,7 +813,7 @@ def test_bn_apply_with_shortcut_batchnorm_is_bit_identical(lib):
 def test_bn_relu_maxpool_fused_is_bit_identical(lib, shape):
     """Stem fusion: BatchNorm-apply + ReLU + max-pool in one pass == icamd_bn_apply followed by icamd_maxpool3x3s2_fwd
     (values and recorded argmax), odd sizes included."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     g = torch.Generator().manual_seed(90)
     y = to_dev_bf16(rnd_bf16(N, H, W, C, seed=91))
@@ -854,7 +833,7 @@ def test_bn_relu_maxpool_fused_is_bit_identical(lib, shape):
 
 
 def test_avgpool(lib):
-    hip = _hip()
+    hip = _harness.hip()
     N, HW, C = 6, 49, 2048
     x = rnd_bf16(N, 7, 7, C, seed=32)
     out = torch.empty(N, C, dtype=torch.bfloat16, device=DEV)
@@ -873,7 +852,7 @@ def test_avgpool(lib):
 
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_pack_input_mixup_cutmix(lib, mode):
-    hip = _hip()
+    hip = _harness.hip()
     B, H, W = 4, 10, 12
     x = torch.randn(B, 3, H, W, generator=torch.Generator().manual_seed(40))
     out = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=DEV)
@@ -890,7 +869,7 @@ def test_pack_input_mixup_cutmix(lib, mode):
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_pack_input_rgb4_stem_layout(lib, mode):
     """[B][H][W+8][4]: RGB + zero channel, 3 zero columns left / 5 right; same fused mixup / cutmix as icamd_pack_input."""
-    hip = _hip()
+    hip = _harness.hip()
     B, H, W = 4, 10, 12
     x = torch.randn(B, 3, H, W, generator=torch.Generator().manual_seed(40))
     out = torch.full((B, H, W + 8, 4), float("nan"), dtype=torch.bfloat16, device=DEV)
@@ -922,7 +901,7 @@ def test_stem7x7s2_fwd_and_wgrad(lib, case):
     """ResNet stem (7x7 stride 2 pad 3, timm resnet conv1) on the rgb4 layout against torch's convolution of the same bf16
     values: output and BatchNorm statistics partials, fused bias + ReLU (eval form), and the weight gradient, whose padding
     entries (row 7, column 7, channel 3 of the [Cout][8][8][4] arena layout) must be exactly zero."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cout = case
     g = torch.Generator().manual_seed(77)
     x = R.bf16_round(torch.randn(N, 3, H, W, generator=g))
@@ -984,7 +963,7 @@ def test_stem7x7s2_fwd_and_wgrad(lib, case):
 @pytest.mark.parametrize("cfg", [(8, 1000, 1024, 0.0, 1.0), (8, 1000, 1024, 0.1, 1.0), (6, 1000, 1024, 0.1, 0.3),
                                  (4, 2, 8, 0.1, 0.8), (5, 10, 16, 0.0, 1.0)])
 def test_softmax_xent_and_metrics(lib, cfg):
-    hip = _hip()
+    hip = _harness.hip()
     B, C, ld, smoothing, lam = cfg
     g = torch.Generator().manual_seed(50)
     logits = rnd_bf16(B, C, scale=3.0, seed=51)
@@ -1043,7 +1022,7 @@ def test_softmax_xent_and_metrics(lib, cfg):
 
 
 def test_adamw_ema_gradnorm(lib):
-    hip = _hip()
+    hip = _harness.hip()
     n = 4096 + 64
     g = torch.Generator().manual_seed(60)
     p0 = torch.randn(n, generator=g)
@@ -1119,7 +1098,7 @@ def test_adamw_ema_gradnorm(lib):
 def test_other_fused_optimizers(lib, name, kind):
     """icamd_optim_ema against torch.optim.SGD / Adam and the restated timm Lion (oracle), 4 steps with the lr = 0 first
     step, per-step weight decay, gradient scale, EMA, shadow and zero_grad fused."""
-    hip = _hip()
+    hip = _harness.hip()
     n = 4096 + 64
     g = torch.Generator().manual_seed(61)
     p0 = torch.randn(n, generator=g)
@@ -1168,7 +1147,7 @@ def test_other_fused_optimizers(lib, name, kind):
 
 
 def test_colsum_lerp_cast(lib):
-    hip = _hip()
+    hip = _harness.hip()
     x = rnd_bf16(37, 24, seed=70)
     out = torch.ones(20, device=DEV)
     xd = to_dev_bf16(x)
@@ -1193,7 +1172,7 @@ def test_colsum_lerp_cast(lib):
 @pytest.mark.parametrize("mask_mode", ["from_y", "from_act", "none"])
 def test_conv_dgrad_with_fused_bn_backward(lib, case, mask_mode):
     """icamd_conv2d_dgrad_bnbwd + icamd_bn_bwd_from_partials == data gradient followed by the BatchNorm backward."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     g = torch.Generator().manual_seed(80)
@@ -1243,7 +1222,7 @@ def test_conv_dgrad_with_fused_bn_backward(lib, case, mask_mode):
 
 def test_conv_dgrad_addend_maskbits(lib):
     """dx = dgrad(dy) + addend * [bit]: the residual shortcut adds the masked output gradient without materialising it."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = 2, 10, 9, 128, 64, 1, 1, 0
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     dy = rnd_bf16(N, d.OH, d.OW, Cout, seed=90)
@@ -1271,7 +1250,7 @@ def test_bn_apply_conv1x1_fused(lib, case):
     BYTES icamd_bn_apply / icamd_bn_apply_res_bn store (same expression); y1 and the statistics are compared with the oracle
     (R.bn_apply + R.conv2d_fwd) and with icamd_conv2d_fwd on the same `out`; ragged last tile; the raw-shortcut (res_bn) form; twice for
     bit-reproducibility."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, K, Nout, res_bn = case
     d = hip.conv_desc(N, H, W, K, Nout, 1, 1, 1, 0)
     assert lib.icamd_bn_apply_conv1x1_fused_supported(ctypes.byref(d)) == 1
@@ -1340,7 +1319,7 @@ def test_conv1x1_bn_bwd_fused(lib, case):
     oracle's three steps (R.bn_bwd, R.conv2d_dgrad, R.conv2d_wgrad), against the three-launch device path it replaces
     (icamd_bn_bwd_from_gy_partials + icamd_conv2d_dgrad + icamd_conv2d_wgrad: same dy bit for bit, so dx may differ by the fp32
     accumulation order only), twice for bit-reproducibility, with accumulate, and with a ragged last tile (M % 32 != 0)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout = case
     d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d)) == 1
@@ -1452,7 +1431,7 @@ def test_conv_dgrad_bnred(lib, case):
     sums of g and g*y that replace the first pass of that block's last BatchNorm backward -- against the oracle's two steps;
     then icamd_bn_bwd_from_gy_partials against the oracle's BatchNorm backward on the same g.  Shapes = the three routed
     (K, N) pairs; ragged last tile; also the kernel must refuse shapes it does not have."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout = case
     d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d)) == 1
@@ -1534,7 +1513,7 @@ def test_conv_dgrad_bnred(lib, case):
 def test_conv_dgrad_addend_on_even_grid(lib, case):
     """icamd_conv2d_dgrad_sub2 == icamd_conv2d_dgrad with the compact addend scattered into a zero tensor (bit for bit),
     and both match the oracle: the gradient a 1x1 stride-2 shortcut sends back exists on the even pixels only."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     dy = rnd_bf16(N, d.OH, d.OW, Cout, seed=94)
@@ -1578,7 +1557,7 @@ def test_conv_dgrad_addend_on_even_grid_large_tile_gemm():
 
 @pytest.mark.parametrize("rows,C", [(50, 768), (197 * 3, 768), (64, 96), (33, 384), (5, 1024)])
 def test_layernorm_fwd_bwd(lib, rows, C):
-    hip = _hip()
+    hip = _harness.hip()
     g = torch.Generator().manual_seed(100)
     x = rnd_bf16(rows, C, scale=2.0, seed=101) + 0.5
     x = R.bf16_round(x)
@@ -1611,7 +1590,7 @@ def test_layernorm_fwd_bwd(lib, rows, C):
 
 
 def test_gelu_and_colsum_rows(lib):
-    hip = _hip()
+    hip = _harness.hip()
     z = rnd_bf16(197 * 4, 3072, scale=2.0, seed=110)
     zd = to_dev_bf16(z)
     a = torch.empty_like(zd)
@@ -1662,7 +1641,7 @@ def test_gelu_and_colsum_rows(lib):
                                    # producer waves stage the next one while the consumers work
                                    (50, 197, 12)])
 def test_attention_fwd_bwd(lib, B, T, H):
-    hip = _hip()
+    hip = _harness.hip()
     D = 64
     scale = D ** -0.5
     qkv = rnd_bf16(B * T, 3 * H * D, scale=1.0, seed=120)
@@ -1719,7 +1698,7 @@ def test_layernorm_bwd_bits_do_not_depend_on_a_second_stream(lib):
     192-channel instance came out with one row's value missing or doubled -- hipcc had sunk the packed adds of the sums past the
     divergent store section of the row loop.  ConvNeXt-T stage 1 at batch 256: rows = 200 704, C = 192; the same call alone
     and next to a 192 -> 768 weight gradient must give bit-identical d gamma / d beta / dx."""
-    hip = _hip()
+    hip = _harness.hip()
     rows, C = 200704, 192
     g = torch.Generator(device="cuda").manual_seed(1)
     dy = (torch.randn(rows, C, device=DEV, generator=g) * 1e-4).bfloat16()
@@ -1769,7 +1748,7 @@ def test_partial_sum_kernels_bits_do_not_depend_on_a_second_stream(lib, which):
     """The other kernels that carry per-thread sums through a row loop with a divergent store section (the pattern behind
     test_layernorm_bwd_bits_do_not_depend_on_a_second_stream), at the sizes the models call them with: alone and next to a ring
     weight gradient on a second stream their outputs must be bit-identical."""
-    hip = _hip()
+    hip = _harness.hip()
     g = torch.Generator(device="cuda").manual_seed(7)
     main, side = torch.cuda.current_stream(), torch.cuda.Stream()
     d = hip.conv_desc(256, 28, 28, 192, 768, 1, 1, 1, 0)
@@ -1919,7 +1898,7 @@ def test_partial_sum_kernels_bits_do_not_depend_on_a_second_stream(lib, which):
                                    # rows split in two (H >= 28) with H odd, W not a multiple of 7, > 256 channel pairs per pixel
                                    (2, 29, 31, 96), (5, 9, 8, 384), (1, 1, 1, 64), (3, 33, 6, 160)])
 def test_dwconv7_fwd_dgrad_wgrad(lib, shape):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     g = torch.Generator().manual_seed(130)
     x = rnd_bf16(N, H, W, C, seed=131)
@@ -1985,7 +1964,7 @@ def test_folded_layerscale_block_tail(lib, use_keep):
     the folded filter) against the oracle's three steps fc2 -> layer scale -> drop path (R.layerscale_fwd / _bwd on the fp32
     Linear layer).  The folded path rounds the filter once (bf16(cb * gamma * W2)) where the three-step path rounds z2: bf16 noise,
     bound 4e-3 relative; the dropped samples must come out EXACTLY (out = x, zero gradient rows)."""
-    hip = _hip()
+    hip = _harness.hip()
     N, HW, C = 6, 49, 192
     K, M = 4 * C, N * HW
     g = torch.Generator().manual_seed(150)
@@ -2078,7 +2057,7 @@ def test_folded_layerscale_block_tail(lib, use_keep):
 
 @pytest.mark.parametrize("use_keep", [False, True])
 def test_layerscale_residual_droppath(lib, use_keep):
-    hip = _hip()
+    hip = _harness.hip()
     N, HW, C = 6, 49, 192
     g = torch.Generator().manual_seed(140)
     z = rnd_bf16(N, HW, C, seed=141)

@@ -8,7 +8,7 @@ Every case first shows that it IS multi-trip, from the library's own workspace /
 planner mirrors of tests/_multitrip.py otherwise (tests/test_multitrip_checks_cpu.py pins those mirrors to the trip counts below),
 so that a change of a cap cannot quietly turn it into a one-trip test.
 
-References are the ones of the kernels' own test modules (tests/_swin_ref.py, tests/test_se_kernels_gpu.py, oracle/ops_ref.py),
+References are the ones of the kernels' own tests (tests/_swin_ref.py, tests/_se_kernels.py, oracle/ops_ref.py),
 accumulated in fp64, on the GPU where the shape is large.  Bounds:
   * window attention: lse 1e-4 / 1e-4; out, dq, dk, dv, dbias global AND per 64 x 64 block under the bounds
     tests/test_fullsize_attention_long_gpu.py applies to icamd_attention_fwd / _bwd (3e-3 forward, 6e-3 backward, the
@@ -22,18 +22,19 @@ No bound here was set from a kernel's output.  Outputs are NaN-filled and carry 
 Like tests/test_fullsize_attention_long_gpu.py the module checks the default routing: an ICAMD_* variable in the environment is a
 failure, not a skip."""
 import ctypes
-import hashlib
-import os
 
 import pytest
 import torch
 
+import _harness
 import _multitrip as MT
-import test_patch_merge_gpu as PM
-import test_resnet_d_kernels_gpu as RD
-import test_se_kernels_gpu as SE
-import test_window_attention_gpu as WA
-from _fullsize_check import block_rel_l2, check_bf16, check_close, check_fp32, check_stats, require
+import _patch_merge as PM
+import _se_kernels as SE
+import _thin_conv as TC
+import _window_attention as WA
+from _fullsize_check import check_bf16, check_close, check_fp32, check_stats, require, worst_block
+from _harness import INT, UNSUPPORTED, dev, digest, guarded, intact
+from _harness import default_routing_lib as lib  # noqa: F401
 from _swin_ref import patch_merge_gather, patch_merge_ln_ref, window_attention_ref
 from oracle import ops_ref as R
 
@@ -41,54 +42,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 F64 = torch.float64
-UNSUPPORTED = 2
-BAND = 4096
-SENT = {1: 0x5A, 2: 0x5A5B, 4: 0x4B5A5B5C}
-INT = {1: torch.int8, 2: torch.int16, 4: torch.int32}
-
-
-@pytest.fixture(scope="module")
-def lib():
-    routed = sorted(k for k in os.environ if k.startswith("ICAMD_"))
-    assert not routed, f"this module checks the default routing; unset {routed}"
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def guarded(shape, dtype, fill):
-    """a `fill`-ed tensor with BAND sentinel elements behind it; returns (tensor, guard)"""
-    n = 1
-    for s in shape:
-        n *= s
-    es = torch.empty(0, dtype=dtype).element_size()
-    whole = torch.full((n + BAND,), SENT[es], dtype=INT[es], device=DEV)
-    view = whole[:n].view(dtype).view(*shape)
-    view.fill_(fill)
-    return view, (whole, n, SENT[es])
-
-
-def intact(guard):
-    whole, n, sentinel = guard
-    torch.cuda.synchronize()
-    return bool((whole[n:] == sentinel).all())
-
-
-def worst_block(got, ref):
-    rel, present = block_rel_l2(got.reshape(ref.shape[0], -1), ref.reshape(ref.shape[0], -1))
-    return float(rel[present].max())
-
-
-def digest(*tensors):
-    h = hashlib.sha256()
-    for t in tensors:
-        h.update(t.contiguous().view(torch.uint8).cpu().numpy().tobytes())
-    return h.hexdigest()
 
 
 # ---------------------------------------------------------------------------------------------------------------- window attention
@@ -191,11 +144,11 @@ _SE = {}
 
 
 def se_case(case):
-    """inputs of tests/test_se_kernels_gpu.py for the shape, moved to the GPU, with its two references computed there"""
+    """inputs of tests/_se_kernels.py for the shape, moved to the GPU, with its two references computed there"""
     if case not in _SE:
-        c = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in SE._inputs(*case).items()}
-        c["ref"] = SE._tail(c, torch.float32)
-        c["ref64"] = SE._tail(c, F64, c["ref"]["mask"])
+        c = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in SE.inputs(*case).items()}
+        c["ref"] = SE.tail(c, torch.float32)
+        c["ref64"] = SE.tail(c, F64, c["ref"]["mask"])
         c["ysum64"] = c["y"].double().sum(1)
         _SE[case] = c
     return _SE[case]
@@ -232,7 +185,7 @@ def se_assert_multitrip(lib, case):
 def test_se_forward_multitrip(lib, case):
     """icamd_se_squeeze, icamd_se_excite_fwd and icamd_se_bn_apply (plain residual and res_bn form) with the checks of
     tests/test_se_kernels_gpu.py test_squeeze_and_excite / test_gated_apply, plus the per-block term on out"""
-    hip = _hip()
+    hip = _harness.hip()
     N, HW, C, rd = case
     nb = se_assert_multitrip(lib, case)
     c = se_case(case)
@@ -266,7 +219,7 @@ def test_se_forward_multitrip(lib, case):
     assert lib.icamd_se_bn_apply(hip.ptr(yd), hip.ptr(sc), hip.ptr(sh), hip.ptr(eref), hip.ptr(resd), None, None, hip.ptr(out),
                                  hip.ptr(bits), N, HW, C, 1, sp) == 0
     assert intact(g_out) and intact(g_bits)
-    z, u = SE._apply_ref(c, c["res"])
+    z, u = SE.apply_ref(c, c["res"])
     want = R.bf16_round(torch.relu(u)).view(N * HW, C)
     oc = out.float()
     print(case, "out: max ulp", R.max_bf16_ulp(oc, want), "rel-L2", R.rel_l2(oc, want), "worst block", worst_block(oc, want))
@@ -324,7 +277,7 @@ def test_se_backward_multitrip(lib, case):
     dev.update(y=c["y"].to(torch.bfloat16), dout=c["dout"].to(torch.bfloat16), bits=pack_bits(ref["mask"]),
                ysum=c["y"].sum(1).contiguous(), s=ref["s"].contiguous(), h=ref["h"].contiguous(), e=ref["e"].contiguous())
     out, guards = se_bwd_buffers(case, 3.0)
-    assert SE._run_bwd(lib, c, dev, out) == 0
+    assert SE.run_bwd(lib, c, dev, out) == 0
     assert all(intact(g) for g in guards)
     errs = {k: R.rel_l2(out[k], ref[k]) for k in SE.GRADS}
     want_dy = R.bf16_round(ref["dy"]).view(N * HW, C)
@@ -337,11 +290,11 @@ def test_se_backward_multitrip(lib, case):
         assert errs[k] <= 1e-4, (k, errs[k])
     # two consecutive calls: bit-identical in every output
     out2, guards2 = se_bwd_buffers(case, -1.0)
-    assert SE._run_bwd(lib, c, dev, out2) == 0
+    assert SE.run_bwd(lib, c, dev, out2) == 0
     for k in out:
         assert torch.equal(out[k].view(INT[out[k].element_size()]), out2[k].view(INT[out[k].element_size()])), k
     # accumulate = 1 on top of the first call: twice one call's worth
-    assert SE._run_bwd(lib, c, dev, out2, accumulate=1) == 0
+    assert SE.run_bwd(lib, c, dev, out2, accumulate=1) == 0
     assert all(intact(g) for g in guards2)
     for k in SE.GRADS:
         assert R.rel_l2(out2[k], 2.0 * out[k]) <= 1e-6, k
@@ -349,7 +302,7 @@ def test_se_backward_multitrip(lib, case):
     # gamma = beta = 0: the four SE gradients are exact zeros
     out0, _ = se_bwd_buffers(case, 5.0)
     zero = torch.zeros(C, device=DEV)
-    assert SE._run_bwd(lib, c, dev, out0, gamma=zero, beta=zero) == 0
+    assert SE.run_bwd(lib, c, dev, out0, gamma=zero, beta=zero) == 0
     for k in ("dW1", "db1", "dW2", "db2"):
         assert float(out0[k].abs().max()) == 0.0, k
     assert float(out0["dy"].float().abs().max()) == 0.0 and float(out0["dbeta"].abs().max()) > 0.0
@@ -358,7 +311,7 @@ def test_se_backward_multitrip(lib, case):
 @pytest.mark.parametrize("C,rd", [(4104, 16), (4096, 257)])
 def test_se_refuses_what_is_past_the_contract_and_writes_nothing(lib, C, rd):
     """C = 4104 (a multiple of 8 past the 4096 limit) and rd = 257 (past 256)"""
-    hip = _hip()
+    hip = _harness.hip()
     N, HW = 2, 4
     sp = hip.stream_ptr()
     f = lambda *shape: torch.full(shape, 7.0, device=DEV)                      # noqa: E731
@@ -390,7 +343,7 @@ def test_se_refuses_what_is_past_the_contract_and_writes_nothing(lib, C, rd):
 # ---------------------------------------------------------------------------------------------------------------- thin 3x3
 def thin_assert_multitrip(lib, case):
     N, H, W, Cout = case
-    d = RD.thin_inputs(case)[0]
+    d = TC.thin_inputs(case)[0]
     sbf, ntiles, sbw, ntw, S_want, tps = MT.THIN_CASES[case]
     assert MT.thin_plan(N, H, W, Cout) == (sbf, sbf, ntiles, sbw, ntw, S_want, tps)
     cus = torch.cuda.get_device_properties(0).multi_processor_count
@@ -410,19 +363,19 @@ def thin_assert_multitrip(lib, case):
 def test_thin_forward_multitrip(lib, case):
     N, H, W, Cout = case
     d, rows = thin_assert_multitrip(lib, case)
-    _, x, w, dy, bias, ref = RD.thin_inputs(case)
-    xd, wd = RD.dev(x), RD.dev(w)
-    stats, gs = RD.guarded_f32((rows, 2, Cout))
-    y = RD.run_fwd(lib, d, xd, wd, stats=stats)
-    assert RD.intact(gs), "guard band behind the statistics written"
+    _, x, w, dy, bias, ref = TC.thin_inputs(case)
+    xd, wd = dev(x), dev(w)
+    stats, gs = guarded((rows, 2, Cout), torch.float32)
+    y = TC.run_fwd(lib, d, xd, wd, stats=stats)
+    assert intact(gs), "guard band behind the statistics written"
     got = y.float().cpu().reshape(-1, Cout)
     want = ref["y"].reshape(-1, Cout)
     print(case, "fwd rel_l2", R.rel_l2(got, want), "worst block", worst_block(got, want))
     assert R.rel_l2(got, want) <= 1e-3 and R.bf16_close(got, want)
     require(check_bf16(got, want, rel=1e-3), "thin fwd")                           # adds the per-block term
-    assert torch.equal(RD.run_fwd(lib, d, xd, wd).view(torch.int16), y.view(torch.int16))      # without statistics: the same bytes
-    stats_b, _ = RD.guarded_f32((rows, 2, Cout))
-    assert torch.equal(RD.run_fwd(lib, d, xd, wd, stats=stats_b).view(torch.int16), y.view(torch.int16))
+    assert torch.equal(TC.run_fwd(lib, d, xd, wd).view(torch.int16), y.view(torch.int16))      # without statistics: the same bytes
+    stats_b, _ = guarded((rows, 2, Cout), torch.float32)
+    assert torch.equal(TC.run_fwd(lib, d, xd, wd, stats=stats_b).view(torch.int16), y.view(torch.int16))
     assert torch.equal(stats.view(torch.int32), stats_b.view(torch.int32))         # run to run
     assert bool(torch.isfinite(stats).all())
     ssum = stats.cpu().double().sum(0)
@@ -437,7 +390,7 @@ def test_thin_forward_multitrip(lib, case):
     assert bool(((stats.cpu().double() - per_tile).abs() <= sb * 2.0 ** -24 * scale).all()), "a statistics row is not its tile's"
     bd = bias.to(DEV)
     for relu, key in ((0, "z"), (1, "zr")):
-        o = RD.run_fwd(lib, d, xd, wd, bias=bd, relu=relu).float().cpu().reshape(-1, Cout)
+        o = TC.run_fwd(lib, d, xd, wd, bias=bd, relu=relu).float().cpu().reshape(-1, Cout)
         assert R.rel_l2(o, ref[key].reshape(-1, Cout)) <= 1e-3 and R.bf16_close(o, ref[key])
         require(check_bf16(o, ref[key].reshape(-1, Cout), rel=1e-3), f"thin fwd with bias, relu {relu}")
 
@@ -445,14 +398,14 @@ def test_thin_forward_multitrip(lib, case):
 @pytest.mark.parametrize("case", list(MT.THIN_CASES))
 def test_thin_dgrad_multitrip(lib, case):
     d, _ = thin_assert_multitrip(lib, case)
-    _, x, w, dy, bias, ref = RD.thin_inputs(case)
-    dyd, wd = RD.dev(dy), RD.dev(w)
-    dx = RD.run_dgrad(lib, d, dyd, wd)
+    _, x, w, dy, bias, ref = TC.thin_inputs(case)
+    dyd, wd = dev(dy), dev(w)
+    dx = TC.run_dgrad(lib, d, dyd, wd)
     got, want = dx.float().cpu().reshape(-1, 32), ref["dx"].reshape(-1, 32)
     print(case, "dgrad rel_l2", R.rel_l2(got, want), "worst block", worst_block(got, want))
     assert R.rel_l2(got, want) <= 1e-3 and R.bf16_close(got, want)
     require(check_bf16(got, want, rel=1e-3), "thin dgrad")                         # adds the per-block term
-    assert torch.equal(dx.view(torch.int16), RD.run_dgrad(lib, d, dyd, wd).view(torch.int16))
+    assert torch.equal(dx.view(torch.int16), TC.run_dgrad(lib, d, dyd, wd).view(torch.int16))
 
 
 @pytest.mark.parametrize("case", list(MT.THIN_CASES))
@@ -460,14 +413,14 @@ def test_thin_wgrad_multitrip(lib, case):
     """through icamd_conv3x3_thin_wgrad itself: the models route this layer elsewhere by default, the entry is part of the ABI"""
     N, H, W, Cout = case
     d, _ = thin_assert_multitrip(lib, case)
-    _, x, w, dy, bias, ref = RD.thin_inputs(case)
-    xd, dyd = RD.dev(x), RD.dev(dy)
-    dw = RD.run_wgrad(lib, d, xd, dyd)
+    _, x, w, dy, bias, ref = TC.thin_inputs(case)
+    xd, dyd = dev(x), dev(dy)
+    dw = TC.run_wgrad(lib, d, xd, dyd)
     got, want = dw.cpu().double().reshape(Cout, -1), ref["dw"].reshape(Cout, -1)
     print(case, "wgrad rel_l2", R.rel_l2(got, want), "worst block", worst_block(got, want))
     assert R.rel_l2(got, want) <= 1e-4
     require(check_fp32(got, want, rel=1e-4), "thin wgrad")                         # adds the per-block term
-    assert torch.equal(dw.view(torch.int32), RD.run_wgrad(lib, d, xd, dyd).view(torch.int32))       # fixed-order reduction
+    assert torch.equal(dw.view(torch.int32), TC.run_wgrad(lib, d, xd, dyd).view(torch.int32))       # fixed-order reduction
     old = torch.randn(Cout, 3, 3, 32, generator=torch.Generator().manual_seed(6))
-    acc = RD.run_wgrad(lib, d, xd, dyd, prefill=old.to(DEV))
+    acc = TC.run_wgrad(lib, d, xd, dyd, prefill=old.to(DEV))
     assert R.rel_l2(acc.cpu().double(), old.double() + ref["dw"].double()) <= 1e-4

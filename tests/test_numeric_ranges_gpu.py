@@ -26,42 +26,19 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _harness
+import _numeric_ranges as NR
+import _se_kernels as SE
+from _convnextv2_ref import GRN_EPS, gelu_grad, grn_closed_form
+from _harness import dev as dev16
+from _harness import lib, sync  # noqa: F401
+from _swin_ref import patch_merge_ln_ref
 from oracle import ops_ref as R
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-import _numeric_ranges as NR  # noqa: E402
-from _convnextv2_ref import GRN_EPS, gelu_grad, grn_closed_form  # noqa: E402
-from _swin_ref import patch_merge_ln_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
 F64 = torch.float64
-
-
-@pytest.fixture(scope="module")
-def lib():
-    return _lib()
-
-
-def _lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def dev16(t):
-    return t.to(torch.bfloat16).to(DEV).contiguous()
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 def finite(**tensors):
@@ -103,7 +80,7 @@ def conv2d_fwd_route(case):
 
 def produce(lib, name, ops):
     """runs the statistics producer `name` on the operands: (y [N,OH,OW,C] bf16 on the device, partial rows [rows,2,C], rows)"""
-    hip = _hip()
+    hip = _harness.hip()
     case = {**NR.BN_PRODUCERS, **NR.BN_SPECIAL}[name]
     N, H, W, Cin, Cout, k, stride, pad, groups = case
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, stride, pad)
@@ -156,7 +133,7 @@ def produce(lib, name, ops):
 def run_bn_case(lib, name):
     """one producer: the regime, then finalize / apply / backward against the exact fp64 reference of the kernel's own y.
     Prints one line per offset class for the table in DESIGN.md; returns nothing, asserts everything."""
-    hip = _hip()
+    hip = _harness.hip()
     ops = NR.bn_operands(name)
     y, stats, rows = produce(lib, name, ops)
     C = y.shape[-1]
@@ -251,7 +228,8 @@ def test_bn_statistics_under_channel_offsets_forced_routes():
     here = os.path.dirname(os.path.abspath(__file__))
     code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
             "import test_numeric_ranges_gpu as T\n"
-            "lib = T._lib()\n"
+            "import _harness\n"
+            "lib = _harness.load_lib()\n"
             "for name in T.FORCED:\n"
             "    T.run_bn_case(lib, name)\n"
             "print('forced-ok')\n") % (here, os.path.dirname(here))
@@ -266,7 +244,7 @@ def test_bn_statistics_under_channel_offsets_forced_routes():
 def test_bn_bwd_from_gy_partials_under_channel_offsets(lib):
     """the backward's own raw-product form: icamd_conv2d_dgrad_bnred writes fp32 partial sums of g and g y, and
     icamd_bn_bwd_from_gy_partials turns them into sum g xhat = invstd (sum g y - mean sum g); y = randn + c_k, c_k up to +-64"""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout = NR.GY_CASE
     d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv2d_dgrad_bnred_supported(ctypes.byref(d)) == 1                    # the route
@@ -318,7 +296,7 @@ def test_conv_dgrad_bnbwd_under_channel_offsets(lib):
     """icamd_conv2d_dgrad_bnbwd + icamd_bn_bwd_from_partials with the BatchNorm input y = randn + c_k and the ReLU mask recomputed
     from y (y * scale + shift cancels to 1 part in 64 there): the masked gradient against the oracle's, the sums and dy against the
     fp64 BatchNorm backward of the g the kernel stored, under the bounds of test_conv_dgrad_with_fused_bn_backward"""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout, k, st, pad = 3, 9, 7, 64, 128, 3, 1, 1
     d = hip.conv_desc(N, H, W, Cin, Cout, k, k, st, pad)
     gen = torch.Generator().manual_seed(396)
@@ -368,7 +346,7 @@ def test_conv1x1_bn_bwd_fused_under_channel_offsets(lib):
     """icamd_conv1x1_bn_bwd_fused at its smallest routed shape with the BatchNorm input y = randn + c_k: from (sum g, sum g y) partial
     rows as icamd_conv2d_dgrad_bnred leaves them (fp32 sums per 128 rows), and with partials = NULL, where it forms sum g xhat itself;
     dgamma, dbeta, dx, dw against the fp64 chain BatchNorm backward -> data gradient / weight gradient, bounds of the sibling test"""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout = 3, 75, 75, 64, 256
     d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
     assert lib.icamd_conv1x1_bn_bwd_fused_supported(ctypes.byref(d)) == 1                  # the route
@@ -461,7 +439,7 @@ def check_ln_backward(ops, eps, run_bwd, variants=NR.LN_BWD_VARIANTS):
 @pytest.mark.parametrize("eps", NR.LN_EPS)
 @pytest.mark.parametrize("rows,C", NR.LN_SHAPES)
 def test_layernorm_ranges(lib, rows, C, eps):
-    hip = _hip()
+    hip = _harness.hip()
     ops = NR.ln_operands(rows, C)
     xd, gd, bd = dev16(ops["x"]), ops["gamma"].to(DEV), ops["beta"].to(DEV)
     y = torch.full((rows, C), float("nan"), dtype=torch.bfloat16, device=DEV)
@@ -489,7 +467,7 @@ def test_layernorm_ranges(lib, rows, C, eps):
 @pytest.mark.parametrize("eps", NR.LN_EPS)
 def test_patch_merge_layernorm_ranges(lib, eps):
     """the same rows through the 2x2 gather: x is the scatter of the merged matrix, so merged row r is of kind r % 9 (8 rows of 384)"""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = NR.PATCH_MERGE_SHAPE
     rows, C4 = N * (H // 2) * (W // 2), 4 * C
     ops = NR.ln_operands(rows, C4, seed=351)
@@ -527,7 +505,7 @@ def test_patch_merge_layernorm_ranges(lib, eps):
 @pytest.mark.parametrize("smoothing,lam", [(0.0, 1.0), (0.1, 1.0), (0.0, 0.3), (0.1, 0.3)])
 @pytest.mark.parametrize("B,C,ld", NR.XENT_SHAPES)
 def test_softmax_xent_ranges(lib, B, C, ld, smoothing, lam):
-    hip = _hip()
+    hip = _harness.hip()
     s = hip.stream_ptr()
     for start in NR.xent_batches(B):
         x, y1, y2, kinds = NR.xent_operands(B, C, start)
@@ -580,7 +558,7 @@ def test_softmax_xent_ranges(lib, B, C, ld, smoothing, lam):
 
 def test_step_metrics_folds_losses_of_0_001_and_400(lib):
     """icamd_step_metrics over the losses of such a batch: the fp64 fold sees 1e-3 and 4e2 together"""
-    hip = _hip()
+    hip = _harness.hip()
     B, C, ld = NR.XENT_SHAPES[0]
     x, y1, y2, kinds = NR.xent_operands(B, C, 0)
     i, j = kinds.index("peak_target"), kinds.index("peak_other")
@@ -621,7 +599,7 @@ def gelu_exact(z):
 def test_gelu_bwd_scaled_upstream_gradient(lib, da_scale):
     """dz = da gelu'(z) over every finite bf16 z with |z| <= 16 and da = +-da_scale: the bound of test_gelu_and_colsum_rows scaled
     by |da| (|err| <= |da| (2^-8 |gelu'| + 1e-6)), which is exact for a power of two"""
-    hip = _hip()
+    hip = _harness.hip()
     allz = torch.arange(-2 ** 15, 2 ** 15, dtype=torch.int32).to(torch.int16).view(torch.bfloat16).float()
     allz = allz[torch.isfinite(allz) & (allz.abs() <= 16.0)]
     allz = torch.cat([allz, torch.zeros((-allz.numel()) % 8)])
@@ -644,7 +622,7 @@ GELU_Z_CYCLE = (0.0, 12.0, -12.0, 0.0, 4.0, -4.0, 12.0, -12.0)
 def test_conv_gelu_epilogue_with_shifted_preactivations(lib):
     """icamd_conv2d_fwd_gelu at (2,8,8,96->384) with z offsets of +-12 carried through a constant input channel: z against the fp64
     convolution, a against the exact GELU of the z the kernel stored, under the bound of test_gelu_and_colsum_rows"""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cin, Cout = 2, 8, 8, 96, 384
     d = hip.conv_desc(N, H, W, Cin, Cout, 1, 1, 1, 0)
     # the route: M = 128 is below the floor (8192 rows) of the K = 96 resident form and K below the large-tile GEMM's 768
@@ -678,7 +656,7 @@ def test_conv_gelu_epilogue_with_shifted_preactivations(lib):
 @pytest.mark.parametrize("with_gelu", [False, True])
 @pytest.mark.parametrize("N,HW,C", NR.GRN_SHAPES)
 def test_grn_ranges(lib, N, HW, C, with_gelu):
-    hip = _hip()
+    hip = _harness.hip()
     assert lib.icamd_grn_supported(N, HW, C) == 1
     ops = NR.grn_operands(N, HW, C)
     a, z, dg, gamma, beta = ops["a"], ops["z"], ops["dg"], ops["gamma"], ops["beta"]
@@ -734,11 +712,10 @@ def test_grn_ranges(lib, N, HW, C, with_gelu):
 
 # ======================================================================================================== squeeze-excitation
 def se_case():
-    """the smallest case of tests/test_se_kernels_gpu.py that has more than one pixel per sample, with the channel offsets of the BatchNorm part added to y (in units of each
+    """the smallest case of tests/_se_kernels.py that has more than one pixel per sample, with the channel offsets of the BatchNorm part added to y (in units of each
     channel's own width) and b2 = +-100 in two channels: gates of exactly 1 and exactly 0, whose backward contribution is 0"""
-    import test_se_kernels_gpu as SE
     N, HW, C, rd = min((c for c in SE.CASES if c[1] > 1), key=lambda c: c[0] * c[1] * c[2])
-    c = SE._inputs(N, HW, C, rd)
+    c = SE.inputs(N, HW, C, rd)
     width = c["y"].double().std((0, 1)).float()
     off = torch.tensor([NR.OFFSET_CYCLE[k % 8] for k in range(C)])
     c["y"] = R.bf16_round(c["y"] + off * torch.exp2(torch.round(torch.log2(width))))
@@ -749,16 +726,16 @@ def se_case():
     c["mean"], c["invstd"] = mean.float(), invstd.float()
     c["scale"] = c["gamma"] * c["invstd"]
     c["shift"] = c["beta"] - c["mean"] * c["scale"]
-    c["ref"] = SE._tail(c, F64)
+    c["ref"] = SE.tail(c, F64)
     c["ysum64"] = yy.sum(1)
-    return SE, c
+    return c
 
 
 SE_ONE, SE_ZERO = 9, 22
 
 
 def test_squeeze_excitation_ranges(lib):
-    SE, c = se_case()
+    c = se_case()
     N, HW, C, rd = c["shape"]
     ref = c["ref"]
     ratio = NR.mean_over_std(c["y"])
@@ -767,7 +744,7 @@ def test_squeeze_excitation_ranges(lib):
             assert float(ratio[idx].min()) >= cls / 3.0
     pre = ref["h"] @ c["W2"].double().t() + c["b2"].double()
     assert float(pre[:, SE_ONE].min()) >= 90.0 and float(pre[:, SE_ZERO].max()) <= -90.0          # the regime
-    _, _, _, ysum, s, h, e = SE._forward_on_gpu(lib, c)
+    _, _, _, ysum, s, h, e = SE.forward_on_gpu(lib, c)
     ysum, s, h, e = ysum.cpu(), s.cpu(), h.cpu(), e.cpu()
     finite(ysum=ysum, s=s, h=h, e=e)
     assert bool((e[:, SE_ONE] == 1.0).all()) and bool((e[:, SE_ZERO] == 0.0).all())
@@ -781,9 +758,9 @@ def test_squeeze_excitation_ranges(lib):
     for k, v in errs.items():
         assert v <= max(1e-5, 2.0 * e_round), (k, v, e_round)
     # backward, fed the exact forward (the kernel by itself, as test_backward feeds it)
-    dev = SE._bwd_inputs(c)
-    out = SE._bwd_buffers(c, garbage=3.0)
-    assert SE._run_bwd(lib, c, dev, out) == 0
+    dev = SE.bwd_inputs(c)
+    out = SE.bwd_buffers(c, garbage=3.0)
+    assert SE.run_bwd(lib, c, dev, out) == 0
     got = {k: out[k].float().cpu() for k in out}
     finite(**got)
     want_dy = R.bf16_round(ref["dy"].float())
@@ -814,7 +791,7 @@ def pool_inputs(kind):
 
 @pytest.mark.parametrize("kind", ["negative", "mixed", "zeros"])
 def test_maxpool_ranges(lib, kind):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = 3, 9, 11, 64
     x = pool_inputs(kind)
     if kind == "negative":
@@ -847,7 +824,7 @@ def test_maxpool_ranges(lib, kind):
 
 
 def test_bn_relu_maxpool_fused_is_bit_identical_with_negative_scales(lib):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = 3, 9, 11, 64
     g = torch.Generator().manual_seed(374)
     y = dev16(NR.rnd_bf16(N, H, W, C, seed=375))
@@ -874,7 +851,7 @@ def test_bn_relu_maxpool_fused_is_bit_identical_with_negative_scales(lib):
 
 # ======================================================================================================== step kernels
 def run_grad_norm(lib, g, inv_scale, max_norm):
-    hip = _hip()
+    hip = _harness.hip()
     ws = torch.empty(lib.icamd_grad_norm_workspace_bytes(), dtype=torch.uint8, device=DEV)
     out = torch.full((2,), float("nan"), device=DEV)
     gd = g.to(DEV)
@@ -903,7 +880,7 @@ def test_grad_norm_ranges(lib, which):
 
 
 def optimizer_call(lib, kind, p, g, m, v, ema, shadow, lr, wd, step, gscale, clip):
-    hip = _hip()
+    hip = _harness.hip()
     s = hip.stream_ptr()
     n = p.numel()
     if kind == "adamw":

@@ -16,15 +16,16 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _harness
+from _harness import UNSUPPORTED, dev, guarded, intact, rnd_bf16
+from _harness import lib  # noqa: F401
+from _thin_conv import run_dgrad, run_fwd, run_wgrad, thin_inputs
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-BAND = 4096                    # guard elements behind every output
-SENT16 = 0x5A5B                # bf16 bit pattern of the band (a finite value no kernel produces by accident)
-SENT32 = 0x4B5A5B5C            # fp32 bit pattern of the band
-BAD_ARG, UNSUPPORTED = 1, 2
+BAD_ARG = 1
 
 # N, IH, IW, C
 POOL_CASES = [(2, 8, 8, 64), (1, 7, 9, 32), (2, 5, 5, 8), (1, 1, 1, 8), (3, 15, 14, 256), (1, 2, 3, 1024)]
@@ -34,53 +35,6 @@ THIN_CASES = [(2, 8, 8, 32), (1, 1, 1, 64), (1, 13, 17, 64), (1, 3, 40, 32), (2,
               # LDS; Cout 32, W 400: 128-pixel tiles and 64-pixel weight-gradient tiles; W 450: 64-pixel tiles and 32-pixel
               # weight-gradient tiles)
               (1, 4, 200, 64), (1, 2, 400, 32), (1, 2, 450, 32)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def rnd_bf16(*shape, scale=1.0, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    return R.bf16_round(torch.randn(*shape, generator=g) * scale)
-
-
-def dev(t):
-    return t.to(torch.bfloat16).to(DEV).contiguous()
-
-
-def guarded_bf16(shape, fill=float("nan")):
-    n = 1
-    for s in shape:
-        n *= s
-    whole = torch.full((n + BAND,), SENT16, dtype=torch.int16, device=DEV)
-    view = whole[:n].view(torch.bfloat16).view(*shape)
-    view.fill_(fill)
-    return view, (whole, n, SENT16)
-
-
-def guarded_f32(shape, fill=float("nan")):
-    n = 1
-    for s in shape:
-        n *= s
-    whole = torch.full((n + BAND,), SENT32, dtype=torch.int32, device=DEV)
-    view = whole[:n].view(torch.float32).view(*shape)
-    view.fill_(fill)
-    return view, (whole, n, SENT32)
-
-
-def intact(guard):
-    whole, n, sentinel = guard
-    torch.cuda.synchronize()
-    return bool((whole[n:] == sentinel).all())
 
 
 # ---------------------------------------------------------------------------------------------------------------- pool
@@ -94,7 +48,7 @@ def pool_ref(x, dout, addend):
 
 @pytest.mark.parametrize("case", POOL_CASES)
 def test_avgpool2x2_fwd_bwd(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, IH, IW, C = case
     OH, OW = (IH + 1) // 2, (IW + 1) // 2
     x = rnd_bf16(N, IH, IW, C, seed=1)
@@ -103,34 +57,34 @@ def test_avgpool2x2_fwd_bwd(lib, case):
     y64, dx64, dxa64 = pool_ref(x, dout, addend)
     xd, dd, ad = dev(x), dev(dout), dev(addend)
     s = hip.stream_ptr()
-    out, g_out = guarded_bf16((N, OH, OW, C))
+    out, g_out = guarded((N, OH, OW, C), torch.bfloat16)
     assert lib.icamd_avgpool2x2_fwd(hip.ptr(xd), hip.ptr(out), N, IH, IW, C, s) == 0
     assert intact(g_out)
     got = out.float().cpu()
     ulp = R.max_bf16_ulp(got, R.bf16_round(y64.float()))
     print(case, "pool fwd max ulp", ulp)
     assert torch.isfinite(got).all() and ulp <= 1.0
-    out2, g2 = guarded_bf16((N, OH, OW, C))
+    out2, g2 = guarded((N, OH, OW, C), torch.bfloat16)
     assert lib.icamd_avgpool2x2_fwd(hip.ptr(xd), hip.ptr(out2), N, IH, IW, C, s) == 0
     assert intact(g2) and torch.equal(out.view(torch.int16), out2.view(torch.int16))
     for add_d, ref in ((None, dx64), (ad, dxa64)):
-        dx, g_dx = guarded_bf16((N, IH, IW, C))
+        dx, g_dx = guarded((N, IH, IW, C), torch.bfloat16)
         assert lib.icamd_avgpool2x2_bwd(hip.ptr(dd), hip.ptr(add_d), hip.ptr(dx), N, IH, IW, C, s) == 0
         assert intact(g_dx)
         gd = dx.float().cpu()
         ulp = R.max_bf16_ulp(gd, R.bf16_round(ref.float()))
         print(case, "pool bwd", "with addend" if add_d is not None else "plain", "max ulp", ulp)
         assert torch.isfinite(gd).all() and ulp <= 1.0      # dx was NaN-filled: every element is written
-        dx2, g_dx2 = guarded_bf16((N, IH, IW, C))
+        dx2, g_dx2 = guarded((N, IH, IW, C), torch.bfloat16)
         assert lib.icamd_avgpool2x2_bwd(hip.ptr(dd), hip.ptr(add_d), hip.ptr(dx2), N, IH, IW, C, s) == 0
         assert intact(g_dx2) and torch.equal(dx.view(torch.int16), dx2.view(torch.int16))
 
 
 def test_avgpool2x2_refuses_c12_and_writes_nothing(lib):
-    hip = _hip()
+    hip = _harness.hip()
     N, IH, IW, C = 2, 6, 6, 12
     x = dev(rnd_bf16(N, IH, IW, 16, seed=1))
-    out, g_out = guarded_bf16((N, IH, IW, 16), fill=3.0)
+    out, g_out = guarded((N, IH, IW, 16), torch.bfloat16, fill=3.0)
     s = hip.stream_ptr()
     assert lib.icamd_avgpool2x2_fwd(hip.ptr(x), hip.ptr(out), N, IH, IW, C, s) == BAD_ARG
     assert lib.icamd_avgpool2x2_bwd(hip.ptr(x), None, hip.ptr(out), N, IH, IW, C, s) == BAD_ARG
@@ -139,67 +93,9 @@ def test_avgpool2x2_refuses_c12_and_writes_nothing(lib):
 
 
 # ---------------------------------------------------------------------------------------------------------------- thin convolution
-_CACHE = {}
-
-
-def thin_inputs(case):
-    """Operands and fp64-accumulated references of a case, computed once and shared by the tests (never modified)."""
-    if case in _CACHE:
-        return _CACHE[case]
-    N, H, W, Cout = case
-    hip = _hip()
-    d = hip.conv_desc(N, H, W, 32, Cout, 3, 3, 1, 1)
-    x = rnd_bf16(N, H, W, 32, seed=1)
-    w = rnd_bf16(Cout, 3, 3, 32, scale=(1.0 / (9 * 32)) ** 0.5, seed=2)
-    dy = rnd_bf16(N, H, W, Cout, seed=3)
-    bias = torch.randn(Cout, generator=torch.Generator().manual_seed(4))
-    F64 = torch.float64
-    ref = {"y": R.conv2d_fwd(x, w, 1, 1, acc=F64).float(),
-           "dx": R.conv2d_dgrad(dy, w, (H, W), 1, 1, acc=F64).float(),
-           "dw": R.conv2d_wgrad(x, dy, (3, 3), 1, 1, acc=F64)}
-    z = R.conv2d_fwd(x, w, 1, 1, bias=bias, acc=F64).float()      # (rounded after the bias; ReLU commutes with the rounding)
-    ref["z"], ref["zr"] = z, z.clamp_min(0)
-    _CACHE[case] = (d, x, w, dy, bias, ref)
-    return _CACHE[case]
-
-
-def run_fwd(lib, d, xd, wd, bias=None, stats=None, relu=0):
-    hip = _hip()
-    y, g = guarded_bf16((d.N, d.OH, d.OW, d.Cout))
-    rc = lib.icamd_conv3x3_thin_fwd(ctypes.byref(d), hip.ptr(xd), hip.ptr(wd), hip.ptr(y), hip.ptr(bias), hip.ptr(stats), relu,
-                                    hip.stream_ptr())
-    assert rc == 0
-    assert intact(g), "guard band behind y written"
-    return y
-
-
-def run_dgrad(lib, d, dyd, wd):
-    hip = _hip()
-    dx, g = guarded_bf16((d.N, d.IH, d.IW, d.Cin))
-    assert lib.icamd_conv3x3_thin_dgrad(ctypes.byref(d), hip.ptr(dyd), hip.ptr(wd), hip.ptr(dx), hip.stream_ptr()) == 0
-    assert intact(g), "guard band behind dx written"
-    return dx
-
-
-def run_wgrad(lib, d, xd, dyd, prefill=None):
-    hip = _hip()
-    dw, g = guarded_f32((d.Cout, 3, 3, 32))
-    if prefill is not None:
-        dw.copy_(prefill)
-    need = lib.icamd_conv3x3_thin_wgrad_workspace_bytes(ctypes.byref(d))
-    assert need > 0
-    ws, gw = guarded_f32((need // 4,))
-    rc = lib.icamd_conv3x3_thin_wgrad(ctypes.byref(d), hip.ptr(xd), hip.ptr(dyd), hip.ptr(dw), 0 if prefill is None else 1,
-                                      hip.ptr(ws), need, hip.stream_ptr())
-    assert rc == 0
-    assert intact(g), "guard band behind dw written"
-    assert intact(gw), "guard band behind the workspace written"
-    return dw
-
-
 @pytest.mark.parametrize("case", THIN_CASES)
 def test_thin_fwd_stats_and_act(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, Cout = case
     d, x, w, dy, bias, ref = thin_inputs(case)
     assert lib.icamd_conv3x3_thin_supported(ctypes.byref(d)) == 1
@@ -213,11 +109,11 @@ def test_thin_fwd_stats_and_act(lib, case):
     # with statistics: the same bytes; the partial rows sum to the sums of the stored values
     rows = lib.icamd_conv3x3_thin_stats_rows(ctypes.byref(d))
     assert rows > 0
-    stats, gs = guarded_f32((rows, 2, Cout))
+    stats, gs = guarded((rows, 2, Cout), torch.float32)
     y2 = run_fwd(lib, d, xd, wd, stats=stats)
     assert intact(gs), "guard band behind the statistics written"
     assert torch.equal(y2.view(torch.int16), y.view(torch.int16))
-    stats_b, _ = guarded_f32((rows, 2, Cout))
+    stats_b, _ = guarded((rows, 2, Cout), torch.float32)
     assert torch.equal(run_fwd(lib, d, xd, wd, stats=stats_b).view(torch.int16), y.view(torch.int16))
     assert torch.equal(stats.view(torch.int32), stats_b.view(torch.int32))       # run to run
     assert torch.isfinite(stats).all()
@@ -265,7 +161,7 @@ def test_thin_dgrad(lib, case):
 
 @pytest.mark.parametrize("case", THIN_CASES)
 def test_thin_wgrad(lib, case):
-    hip = _hip()
+    hip = _harness.hip()
     d, x, w, dy, bias, ref = thin_inputs(case)
     xd, dyd = dev(x), dev(dy)
     dw = run_wgrad(lib, d, xd, dyd)
@@ -289,7 +185,7 @@ def test_thin_wgrad(lib, case):
 
 
 def test_thin_refusals_touch_nothing(lib):
-    hip = _hip()
+    hip = _harness.hip()
     bad = [hip.conv_desc(2, 8, 8, 64, 64, 3, 3, 1, 1),      # Cin 64
            hip.conv_desc(2, 8, 8, 32, 32, 3, 3, 2, 1),      # stride 2
            hip.conv_desc(2, 8, 8, 32, 32, 3, 3, 1, 0),      # pad 0

@@ -12,131 +12,34 @@ import functools
 import pytest
 import torch
 
+import _harness
+from _harness import lib  # noqa: F401
+from _se_kernels import (CASES, GRADS, apply_ref, bwd_buffers, bwd_inputs, forward_on_gpu, inputs, run_bwd, tail,
+                         to_dev)
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-EPS = 1e-5
-CASES = [(3, 49, 256, 16), (2, 196, 512, 32), (5, 9, 2048, 128), (4, 1, 256, 16), (1, 3136, 256, 16), (3, 35, 64, 8)]
-GRADS = ("dgamma", "dbeta", "dW1", "db1", "dW2", "db2")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def _tail(c, dt, mask=None):
-    """The block tail in dtype dt on the case's (already rounded) inputs, with autograd.  mask None: the ReLU's own; given: that
-    mask (so that the fp64 copy differentiates the same function as the fp32 reference)."""
-    t = {k: c[k].to(dt).clone().requires_grad_() for k in ("y", "gamma", "beta", "W1", "b1", "W2", "b2")}
-    y = t["y"]
-    # BatchNorm in training mode: the statistics are functions of y
-    m = y.mean((0, 1))
-    v = ((y - m) ** 2).mean((0, 1))
-    yhat = (y - m) / torch.sqrt(v + EPS)
-    z = yhat * t["gamma"] + t["beta"]
-    s = z.mean(1)
-    h = torch.relu(s @ t["W1"].t() + t["b1"])
-    e = torch.sigmoid(h @ t["W2"].t() + t["b2"])
-    u = z * e[:, None, :] + c["res"].to(dt)
-    if mask is None:
-        mask = (u > 0).detach()
-    out = u * mask
-    out.backward(c["dout"].to(dt))
-    r = {"z": z.detach(), "s": s.detach(), "h": h.detach(), "e": e.detach(), "u": u.detach(), "mask": mask, "dy": y.grad,
-         "dgamma": t["gamma"].grad, "dbeta": t["beta"].grad, "dW1": t["W1"].grad, "db1": t["b1"].grad, "dW2": t["W2"].grad,
-         "db2": t["b2"].grad}
-    return r
-
-
-def _inputs(N, HW, C, rd):
-    """The (rounded) inputs of a case, without references"""
-    g = torch.Generator().manual_seed(1000 + N * 7 + HW + C)
-    c = {"shape": (N, HW, C, rd)}
-    # a raw convolution output with per-channel offsets and widths and a per-sample shift (so that s differs between samples)
-    y = torch.randn(N, HW, C, generator=g) * (torch.rand(C, generator=g) + 0.5) + torch.randn(C, generator=g) \
-        + 0.7 * torch.randn(N, 1, C, generator=g)
-    c["y"] = R.bf16_round(y)
-    c["gamma"] = torch.rand(C, generator=g) + 0.5
-    c["beta"] = torch.randn(C, generator=g) * 0.3
-    c["mean"] = c["y"].mean((0, 1))
-    c["invstd"] = 1.0 / torch.sqrt(c["y"].var((0, 1), unbiased=False) + EPS)
-    c["scale"] = c["gamma"] * c["invstd"]
-    c["shift"] = c["beta"] - c["mean"] * c["scale"]
-    # weights and biases sized so that the gate spreads over (0.05, 0.95)
-    c["W1"] = torch.randn(rd, C, generator=g) * (1.5 / C ** 0.5)
-    c["b1"] = torch.randn(rd, generator=g) * 0.3 + 0.3
-    c["W2"] = torch.randn(C, rd, generator=g) * (1.0 / rd ** 0.5)
-    c["b2"] = torch.randn(C, generator=g) * 1.2
-    c["res"] = R.bf16_round(torch.randn(N, HW, C, generator=g))              # both signs
-    c["dout"] = R.bf16_round(torch.randn(N, HW, C, generator=g) * 0.1)
-    return c
 
 
 @functools.lru_cache(maxsize=None)
 def _case(N, HW, C, rd):
-    c = _inputs(N, HW, C, rd)
-    c["ref"] = _tail(c, torch.float32)
-    c["ref64"] = _tail(c, torch.float64, c["ref"]["mask"])
+    c = inputs(N, HW, C, rd)
+    c["ref"] = tail(c, torch.float32)
+    c["ref64"] = tail(c, torch.float64, c["ref"]["mask"])
     c["ysum64"] = c["y"].double().sum(1)
     return c
-
-
-def _dev(t, dtype=torch.float32):
-    return t.to(dtype).to(DEV).contiguous()
-
-
-def _pack_bits(mask):
-    m = mask.flatten().to(torch.uint8).view(-1, 8)
-    return (m << torch.arange(8, dtype=torch.uint8)).sum(1).to(torch.uint8)
 
 
 def _unpack_bits(bits):
     return ((bits.cpu().view(-1, 1) >> torch.arange(8, dtype=torch.uint8)) & 1).flatten().bool()
 
 
-def _apply_ref(c, res):
-    """u = fma(fma(y, scale, shift), e, res) with the reference's e: each fused multiply-add formed exactly in fp64 and rounded to
-    fp32 once, which is what the kernel's two fp32 FMAs do.  Returns (z, u)."""
-    z = (c["y"].double() * c["scale"].double() + c["shift"].double()).float()
-    u = z.double() * c["ref"]["e"].double()[:, None, :]
-    if res is not None:
-        u = u + res.double()
-    return z, u.float()
-
-
-def _forward_on_gpu(lib, c):
-    hip = _hip()
-    N, HW, C, rd = c["shape"]
-    yd = _dev(c["y"], torch.bfloat16)
-    ysum = torch.full((N, C), float("nan"), device=DEV)
-    nb = lib.icamd_se_squeeze_workspace_bytes(N, HW, C)
-    assert nb > 0
-    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
-    assert lib.icamd_se_squeeze(hip.ptr(yd), hip.ptr(ysum), N, HW, C, hip.ptr(ws), nb, hip.stream_ptr()) == 0
-    sc, sh = _dev(c["scale"]), _dev(c["shift"])
-    w1, b1, w2, b2 = (_dev(c[k]) for k in ("W1", "b1", "W2", "b2"))
-    s, e = (torch.full((N, C), float("nan"), device=DEV) for _ in range(2))
-    h = torch.full((N, rd), float("nan"), device=DEV)
-    assert lib.icamd_se_excite_fwd(hip.ptr(ysum), hip.ptr(sc), hip.ptr(sh), 1.0 / HW, hip.ptr(w1), hip.ptr(b1), hip.ptr(w2),
-                                   hip.ptr(b2), hip.ptr(s), hip.ptr(h), hip.ptr(e), N, C, rd, hip.stream_ptr()) == 0
-    torch.cuda.synchronize()
-    return yd, sc, sh, ysum, s, h, e
-
-
 @pytest.mark.parametrize("case", CASES)
 def test_squeeze_and_excite(lib, case):
     c = _case(*case)
     ref = c["ref"]
-    _, _, _, ysum, s, h, e = _forward_on_gpu(lib, c)
+    _, _, _, ysum, s, h, e = forward_on_gpu(lib, c)
     errs = {"ysum": R.rel_l2(ysum.cpu(), c["ysum64"]), "s": R.rel_l2(s.cpu(), ref["s"]), "h": R.rel_l2(h.cpu(), ref["h"]),
             "e": R.rel_l2(e.cpu(), ref["e"])}
     print(case, {k: f"{v:.2e}" for k, v in errs.items()}, "gate range", float(ref["e"].min()), float(ref["e"].max()))
@@ -151,19 +54,19 @@ def test_gated_apply(lib, case):
     arithmetic at the same rounding points: both fused multiply-adds formed exactly and rounded to fp32 once (_apply_ref), so the
     sign of the reference's pre-activation u is the kernel's.  The mask is compared with [u_ref > 0] wherever u_ref != 0 (|u_ref|
     exceeds a bf16 ulp of itself there); such positions must be >= 99 % of all."""
-    hip = _hip()
+    hip = _harness.hip()
     c = _case(*case)
     ref = c["ref"]
     N, HW, C, rd = c["shape"]
-    yd, sc, sh = _dev(c["y"], torch.bfloat16), _dev(c["scale"]), _dev(c["shift"])
-    e = _dev(ref["e"])
-    resd = _dev(c["res"], torch.bfloat16)
+    yd, sc, sh = to_dev(c["y"], torch.bfloat16), to_dev(c["scale"]), to_dev(c["shift"])
+    e = to_dev(ref["e"])
+    resd = to_dev(c["res"], torch.bfloat16)
     out = torch.empty_like(yd)
     bits = torch.zeros(yd.numel() // 8, dtype=torch.uint8, device=DEV)
     assert lib.icamd_se_bn_apply(hip.ptr(yd), hip.ptr(sc), hip.ptr(sh), hip.ptr(e), hip.ptr(resd), None, None, hip.ptr(out),
                                  hip.ptr(bits), N, HW, C, 1, hip.stream_ptr()) == 0
     torch.cuda.synchronize()
-    z, u = _apply_ref(c, c["res"])
+    z, u = apply_ref(c, c["res"])
     want = R.bf16_round(torch.relu(u))
     oc = out.float().cpu()
     print(case, "out: max ulp", R.max_bf16_ulp(oc, want), "rel-L2", R.rel_l2(oc, want))
@@ -175,8 +78,8 @@ def test_gated_apply(lib, case):
     # the res_bn form: the residual is a raw shortcut convolution output normalised on the fly == the plain form fed the
     # shortcut icamd_bn_apply would have stored
     g = torch.Generator().manual_seed(77)
-    raw = _dev(R.bf16_round(torch.randn(N, HW, C, generator=g) * 2 + 0.5), torch.bfloat16)
-    rsc, rsh = _dev(torch.rand(C, generator=g) + 0.5), _dev(torch.randn(C, generator=g) * 0.2)
+    raw = to_dev(R.bf16_round(torch.randn(N, HW, C, generator=g) * 2 + 0.5), torch.bfloat16)
+    rsc, rsh = to_dev(torch.rand(C, generator=g) + 0.5), to_dev(torch.randn(C, generator=g) * 0.2)
     pre = torch.empty_like(raw)
     assert lib.icamd_bn_apply(hip.ptr(raw), hip.ptr(rsc), hip.ptr(rsh), None, hip.ptr(pre), None, raw.numel(), C, 0,
                               hip.stream_ptr()) == 0
@@ -192,53 +95,19 @@ def test_gated_apply(lib, case):
 
 
 def test_gated_apply_no_relu_no_residual(lib):
-    hip = _hip()
+    hip = _harness.hip()
     c = _case(*CASES[0])
     ref = c["ref"]
     N, HW, C, rd = c["shape"]
-    yd, sc, sh, e = _dev(c["y"], torch.bfloat16), _dev(c["scale"]), _dev(c["shift"]), _dev(ref["e"])
+    yd, sc, sh, e = to_dev(c["y"], torch.bfloat16), to_dev(c["scale"]), to_dev(c["shift"]), to_dev(ref["e"])
     out = torch.empty_like(yd)
     assert lib.icamd_se_bn_apply(hip.ptr(yd), hip.ptr(sc), hip.ptr(sh), hip.ptr(e), None, None, None, hip.ptr(out), None, N, HW, C,
                                  0, hip.stream_ptr()) == 0
     torch.cuda.synchronize()
-    want = R.bf16_round(_apply_ref(c, None)[1])
+    want = R.bf16_round(apply_ref(c, None)[1])
     oc = out.float().cpu()
     assert float((oc < 0).float().mean()) > 0.1
     assert R.max_bf16_ulp(oc, want) <= 1.0 and R.rel_l2(oc, want) <= 1e-3
-
-
-def _bwd_buffers(c, garbage=0.0):
-    N, HW, C, rd = c["shape"]
-    shapes = {"dgamma": (C,), "dbeta": (C,), "dW1": (rd, C), "db1": (rd,), "dW2": (C, rd), "db2": (C,)}
-    out = {k: torch.full(s, garbage, device=DEV) for k, s in shapes.items()}
-    out["dy"] = torch.full((N, HW, C), 7.0, dtype=torch.bfloat16, device=DEV)
-    return out
-
-
-def _run_bwd(lib, c, dev, out, accumulate=0, gamma=None, beta=None, ws=None):
-    hip = _hip()
-    N, HW, C, rd = c["shape"]
-    nb = lib.icamd_se_bn_bwd_workspace_bytes(N, HW, C)
-    assert nb > 0
-    if ws is None:
-        ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
-    rc = lib.icamd_se_bn_bwd(hip.ptr(dev["dout"]), hip.ptr(dev["bits"]), hip.ptr(dev["y"]), hip.ptr(dev["mean"]), hip.ptr(dev["invstd"]),
-                             hip.ptr(dev["gamma"] if gamma is None else gamma), hip.ptr(dev["beta"] if beta is None else beta),
-                             hip.ptr(dev["ysum"]), hip.ptr(dev["s"]), hip.ptr(dev["h"]), hip.ptr(dev["e"]), hip.ptr(dev["W1"]),
-                             hip.ptr(dev["W2"]), hip.ptr(out["dgamma"]), hip.ptr(out["dbeta"]), hip.ptr(out["dW1"]),
-                             hip.ptr(out["db1"]), hip.ptr(out["dW2"]), hip.ptr(out["db2"]), hip.ptr(out["dy"]), N, HW, C, rd,
-                             accumulate, hip.ptr(ws), nb, hip.stream_ptr())
-    torch.cuda.synchronize()
-    return rc
-
-
-def _bwd_inputs(c):
-    """The backward's inputs from the fp32 reference (the kernel is tested on its own, not behind the forward kernels)."""
-    ref = c["ref"]
-    dev = {k: _dev(c[k]) for k in ("mean", "invstd", "gamma", "beta", "W1", "W2")}
-    dev.update(y=_dev(c["y"], torch.bfloat16), dout=_dev(c["dout"], torch.bfloat16), bits=_pack_bits(ref["mask"]).to(DEV),
-               ysum=_dev(c["y"].sum(1)), s=_dev(ref["s"]), h=_dev(ref["h"]), e=_dev(ref["e"]))
-    return dev
 
 
 @pytest.mark.parametrize("case", CASES)
@@ -250,9 +119,9 @@ def test_backward(lib, case):
     print(case, "reference vs its fp64 copy:", {k: f"{v:.1e}" for k, v in noise.items()})
     for k in GRADS + ("dy",):
         assert float(ref[k].abs().max()) > 0.0 and noise[k] <= 5e-5, (k, noise[k])
-    dev = _bwd_inputs(c)
-    out = _bwd_buffers(c, garbage=3.0)
-    assert _run_bwd(lib, c, dev, out) == 0
+    dev = bwd_inputs(c)
+    out = bwd_buffers(c, garbage=3.0)
+    assert run_bwd(lib, c, dev, out) == 0
     errs = {k: R.rel_l2(out[k].cpu(), ref[k]) for k in GRADS}
     want_dy = R.bf16_round(ref["dy"])
     got_dy = out["dy"].float().cpu()
@@ -261,30 +130,30 @@ def test_backward(lib, case):
     for k in GRADS:
         assert errs[k] <= 1e-4, (k, errs[k])
     # two consecutive calls: bit-identical in every output
-    out2 = _bwd_buffers(c, garbage=-1.0)
-    assert _run_bwd(lib, c, dev, out2) == 0
+    out2 = bwd_buffers(c, garbage=-1.0)
+    assert run_bwd(lib, c, dev, out2) == 0
     for k in out:
         assert torch.equal(out[k], out2[k]), k
     # accumulate = 1 on top of the first call: twice one call's worth
-    assert _run_bwd(lib, c, dev, out2, accumulate=1) == 0
+    assert run_bwd(lib, c, dev, out2, accumulate=1) == 0
     for k in GRADS:
         assert R.rel_l2(out2[k].cpu(), 2.0 * out[k].cpu()) <= 1e-6, k
     assert torch.equal(out2["dy"], out["dy"])
     # gamma = beta = 0: the four SE gradients are exact zeros
-    out0 = _bwd_buffers(c, garbage=5.0)
+    out0 = bwd_buffers(c, garbage=5.0)
     zero = torch.zeros(case[2], device=DEV)
-    assert _run_bwd(lib, c, dev, out0, gamma=zero, beta=zero) == 0
+    assert run_bwd(lib, c, dev, out0, gamma=zero, beta=zero) == 0
     for k in ("dW1", "db1", "dW2", "db2"):
         assert float(out0[k].abs().max()) == 0.0, k
     assert float(out0["dy"].float().abs().max()) == 0.0 and float(out0["dbeta"].abs().max()) > 0.0
 
 
 def test_bad_arguments(lib):
-    hip = _hip()
+    hip = _harness.hip()
     c = _case(*CASES[0])
     N, HW, C, rd = c["shape"]
-    dev = _bwd_inputs(c)
-    out = _bwd_buffers(c, garbage=3.0)
+    dev = bwd_inputs(c)
+    out = bwd_buffers(c, garbage=3.0)
     nb = lib.icamd_se_bn_bwd_workspace_bytes(N, HW, C)
     ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
     sp = hip.stream_ptr()

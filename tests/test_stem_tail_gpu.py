@@ -11,6 +11,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import _harness
+from _harness import rnd_bf16, sync
+from _harness import lib  # noqa: F401
 from oracle import ops_ref as R
 
 DEV = "cuda"
@@ -24,27 +27,6 @@ RAGGED = [(3, 9, 7, 64), (5, 12, 10, 64), (1, 1, 1, 64), (2, 14, 14, 128), (2, 8
           (1, 4, 300, 64), (1, 3, 700, 64)]
 FOLD_SHAPES = [BENCH_STEM] + RAGGED
 POOL_SHAPES = [BENCH_STEM] + RAGGED + [(1, 16, 16, 128)]
-
-
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
-def rnd_bf16(*shape, scale=1.0, seed=0, device="cpu"):
-    g = torch.Generator(device=device).manual_seed(seed)
-    return R.bf16_round(torch.randn(*shape, generator=g, device=device) * scale)
-
-
-def sync():
-    torch.cuda.synchronize()
 
 
 def pool_bwd_restated(dout, x):
@@ -108,7 +90,7 @@ def side_wgrad(lib, hip):
 def test_folded_stem_backward_is_bit_identical(lib, shape):
     """icamd_bn_bwd_maxpool3x3s2 == icamd_maxpool3x3s2_bwd + icamd_bn_bwd: dy, dgamma, dbeta torch.equal, at the benchmark's
     stem shape and at ragged ones; the same bits twice in a row and next to a ring weight gradient on a second stream."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     g = torch.Generator().manual_seed(130)
     y = rnd_bf16(N, H, W, C, seed=131, device=DEV).to(torch.bfloat16)
@@ -166,7 +148,7 @@ def test_folded_stem_backward_is_bit_identical(lib, shape):
 def test_maxpool_forward_and_backward(lib, shape):
     """Forward value and argmax torch.equal to the oracle (as test_maxpool); backward torch.equal to the restatement above
     and inside test_maxpool's bounds (<= 1 bf16 ulp, rel-L2 <= 1e-3) against oracle.ops_ref.maxpool3x3s2_bwd."""
-    hip = _hip()
+    hip = _harness.hip()
     N, H, W, C = shape
     big = N * H * W * C > 1 << 24
     dev = DEV if big else "cpu"          # the references of the benchmark-size case are computed on the GPU by torch
@@ -211,7 +193,7 @@ def test_pack_input_rgb4(lib, case):
     """[B][H][W + (W & 1) + 8][4] torch.equal to oracle.ops_ref.pack_input in every mode: modes 0 and 2 move fp32 pixels and round
     once, and the mixup is two rounded products and a rounded sum, as torch's (the kernel forbids their contraction).  Everything
     outside the image is exactly zero.  Also from a source that is only 4 B aligned (a view one float into a buffer)."""
-    hip = _hip()
+    hip = _harness.hip()
     B, H, W, mode, box = case
     lam = 0.37
     We = W + (W & 1)
@@ -237,7 +219,7 @@ def test_pack_input_rgb4(lib, case):
 def test_grad_norm(lib, n):
     """icamd_grad_norm against fp64 numpy of the same fp32 data to test_fullsize_step_gpu.py::test_grad_norm's bound (1e-5
     relative), for n % 4 != 0, n smaller than the grid, n about ResNet-50's arena; two calls give the same bits."""
-    hip = _hip()
+    hip = _harness.hip()
     g = torch.randn(n, generator=torch.Generator(device=DEV).manual_seed(140), device=DEV)
     g = g * 10.0 ** torch.linspace(-4.0, 2.0, n, device=DEV)
     ref = float(np.sqrt((g.cpu().numpy().astype(np.float64) ** 2).sum()))
@@ -261,7 +243,7 @@ def test_grad_norm(lib, n):
 def test_colsum(lib, case):
     """icamd_colsum as the FC bias gradient calls it (rows 256, ld = cols = 1024) and at ragged sizes: torch.equal to the fp32
     sum taken in row order (the kernel keeps that order), and test_colsum_lerp_cast's bound against torch's own sum."""
-    hip = _hip()
+    hip = _harness.hip()
     rows, ld, cols = case
     x = rnd_bf16(rows, ld, seed=70)
     xd = x.to(torch.bfloat16).to(DEV).contiguous()

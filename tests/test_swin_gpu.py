@@ -1,7 +1,6 @@
 """Swin Transformer on the HIP kernels vs the CPU oracle (tests/_swin_ref.py, same bf16 rounding points), on the pattern of
 tests/test_vit_gpu.py and with its bounds: whole-network tolerances use the oracle's own re-association noise (fp64 vs fp32
 accumulation) as the yardstick."""
-import copy
 import os
 import pickle
 import subprocess
@@ -10,15 +9,11 @@ import sys
 import pytest
 import torch
 
-from oracle import ops_ref as R
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-from _swin_ref import SwinRef  # noqa: E402
+from _swin_ref import SwinRef
+from _swin_step import ROOT, check
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _pair(arch, C, img, seed=0, drop_path_rate=0.0):
@@ -39,47 +34,6 @@ def _pair(arch, C, img, seed=0, drop_path_rate=0.0):
     return ref, net
 
 
-def _step(ref, net, x, y, C):
-    """forward, label-smoothed loss and backward on both sides; returns what the comparisons need"""
-    from imageclassification_amd import hip
-    B = x.shape[0]
-    ref64 = copy.deepcopy(ref).double()
-    for b32, b64 in zip(ref.blocks(), ref64.blocks()):
-        b64.keep = b32.keep
-    out = ref(x)
-    loss = torch.nn.functional.cross_entropy(out, y, label_smoothing=0.1)
-    loss.backward()
-    out64 = ref64(x.double())
-    torch.nn.functional.cross_entropy(out64, y, label_smoothing=0.1).backward()
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    yd = y.cuda()
-    hip.check(net.lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, C, yd.data_ptr(), None, 1.0, 0.1, 1.0 / B,
-                                         ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(), ws["dlogits"].data_ptr(),
-                                         hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
-    return ws, logits[:, :C].float().cpu(), out.detach(), out64.detach().float(), float(loss.detach()), ref64
-
-
-def _check(tag, ref, net, x, y, C):
-    ws, got, out, out64, loss, ref64 = _step(ref, net, x, y, C)
-    noise = R.rel_l2(out64, out)
-    err = R.rel_l2(got, out)
-    p64 = dict(ref64.named_parameters())
-    rows = []
-    for name, p in ref.named_parameters():
-        rows.append((name, R.rel_l2(net.grad_of(name), p.grad), R.rel_l2(p64[name].grad.float(), p.grad)))
-    worst = max(rows, key=lambda r: r[1])
-    print(f"{tag}: logits err {err:.2e} (self-noise {noise:.2e}); loss {float(ws['loss_rows'].mean()):.5f} vs {loss:.5f}; "
-          f"worst grad err {worst[1]:.2e} (yardstick {worst[2]:.2e}) at {worst[0]}")
-    assert err <= 2.0 * max(noise, 2e-3), (err, noise)
-    assert abs(float(ws["loss_rows"].mean()) - loss) <= 5e-3 * loss
-    for name, e, n in rows:
-        assert e <= 3.0 * max(n, 1e-2), (name, e, n)
-
-
 @pytest.mark.parametrize("arch,img,B", [("swin_test", 56, 6), ("swin_test", 112, 2), ("swin_tiny_patch4_window7_224", 224, 2)])
 def test_swin_forward_backward_matches_oracle(arch, img, B):
     C = 10
@@ -87,7 +41,7 @@ def test_swin_forward_backward_matches_oracle(arch, img, B):
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
-    _check(f"{arch} img{img}", ref, net, x, y, C)
+    check(f"{arch} img{img}", ref, net, x, y, C)
 
 
 def test_swin_stochastic_depth_with_injected_masks():
@@ -112,7 +66,7 @@ def test_swin_stochastic_depth_with_injected_masks():
     net.injected_keep = keeps
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
-    _check("swin_test drop_path 0.5", ref, net, x, y, C)
+    check("swin_test drop_path 0.5", ref, net, x, y, C)
 
 
 def test_swin_accumulation_state_and_pickling(tmp_path):

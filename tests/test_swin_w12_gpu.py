@@ -15,13 +15,10 @@ import sys
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
-import _swin_w12 as W12  # noqa: E402
-import test_swin_gpu as SG  # noqa: E402
+import _swin_w12 as W12
+from _swin_step import ROOT, check
 
 pytestmark = pytest.mark.gpu
-ROOT = SG.ROOT
 ARCH = "swin_test_w12"
 
 
@@ -34,7 +31,7 @@ def test_swin_w12_forward_backward_matches_oracle(img, B):
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
-    SG._check(f"{ARCH} img{img}", ref, net, x, y, C)
+    check(f"{ARCH} img{img}", ref, net, x, y, C)
 
 
 def test_swin_w12_stochastic_depth_with_injected_masks():
@@ -58,7 +55,7 @@ def test_swin_w12_stochastic_depth_with_injected_masks():
     net.injected_keep = keeps
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
-    SG._check(f"{ARCH} drop_path 0.5", ref, net, x, y, C)
+    check(f"{ARCH} drop_path 0.5", ref, net, x, y, C)
 
 
 def test_swin_w12_engine_step_and_evaluate():

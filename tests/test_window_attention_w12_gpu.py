@@ -1,8 +1,8 @@
 """icamd_window_attention_fwd / _bwd and the relative-position gather / scatter for 12 x 12 windows (csrc/window_attention_w12.hip),
 through the C ABI.
 
-Reference, operands, guard bands, NaN-filled outputs and digests are those of tests/test_window_attention_gpu.py (fp64
-window_attention_ref of tests/_swin_ref.py, P and dS unrounded), and so are the bounds: lse allclose(1e-4, 1e-4), out rel-L2 <= 3e-3,
+Reference, operands, guard bands, NaN-filled outputs and the parity check are those of tests/_window_attention.py (fp64
+window_attention_ref of tests/_swin_ref.py, P and dS unrounded), shared with tests/test_window_attention_gpu.py, and so are the bounds: lse allclose(1e-4, 1e-4), out rel-L2 <= 3e-3,
 dq / dk / dv / dbias rel-L2 <= 6e-3 -- the rounding points of the T = 144 kernels are the same (P and dS rounded to bf16 once as MFMA
 operands, fp32 accumulation, one final rounding; dbias from the fp32 dS).  The multi-trip case adds the per 64 x 64 block checks of
 tests/test_multitrip_gpu.py, which catch a trip that writes the right values to the wrong window."""
@@ -10,8 +10,10 @@ import pytest
 import torch
 
 import _swin_w12 as W12
-import test_window_attention_gpu as WA
-from _fullsize_check import block_rel_l2, check_bf16, check_close, check_fp32, require
+import _window_attention as WA
+from _fullsize_check import check_bf16, check_close, check_fp32, require, worst_block
+from _harness import UNSUPPORTED, digest, guarded, hip, intact, rnd_bf16
+from _harness import lib  # noqa: F401
 from _swin_ref import relative_position_index, window_attention_ref
 from oracle import ops_ref as R
 
@@ -34,48 +36,9 @@ CASES = [
 MULTITRIP = (17, 24, 24, 32, 12, 6)
 
 
-@pytest.fixture(scope="module")
-def lib():
-    from imageclassification_amd import hip
-    hip.require_gpu()
-    return hip.load()
-
-
-def _hip():
-    from imageclassification_amd import hip
-    return hip
-
-
 @pytest.mark.parametrize("case", CASES)
 def test_window12_attention_matches_reference(lib, case):
-    B, Hs, Ws, H, ws, shift = case
-    qkv, dout, bias = WA.operands(B, Hs, Ws, H, ws)
-    rc_f, rc_b, out, lse, dqkv, dbias = WA.run(lib, qkv, dout, bias, B, Hs, Ws, H, ws, shift)
-    assert rc_f == 0 and rc_b == 0, (rc_f, rc_b)
-    ro, rlse, rdqkv, rdbias = WA.reference(case)
-    got = out.float().cpu()
-    glse = lse.cpu().view(-1, H, T)
-    gd = dqkv.float().cpu()
-    gb = dbias.cpu().view(H, T, T)
-    assert torch.isfinite(got).all() and torch.isfinite(glse).all() and torch.isfinite(gd).all() and torch.isfinite(gb).all()
-    lse_err = float((glse.double() - rlse).abs().max())
-    fwd = R.rel_l2(got, ro.reshape(got.shape))
-    print(f"case {case}: lse max abs err {lse_err:.3g}, out rel_l2 {fwd:.3g}")
-    errs = {}
-    rd = rdqkv.reshape(gd.shape)
-    for name, sl in (("dq", slice(0, H * D)), ("dk", slice(H * D, 2 * H * D)), ("dv", slice(2 * H * D, 3 * H * D))):
-        errs[name] = R.rel_l2(gd[:, sl], rd[:, sl])
-    errs["dbias"] = R.rel_l2(gb, rdbias)
-    print("    " + ", ".join(f"{k} rel_l2 {v:.3g}" for k, v in errs.items()))
-    assert torch.allclose(glse.double(), rlse, rtol=1e-4, atol=1e-4)
-    assert fwd <= 3e-3
-    for name in ("dq", "dk", "dv", "dbias"):
-        assert errs[name] <= 6e-3, (name, errs[name])
-
-
-def worst_block(got, ref):
-    rel, present = block_rel_l2(got.reshape(ref.shape[0], -1), ref.reshape(ref.shape[0], -1))
-    return float(rel[present].max())
+    WA.check_case(lib, case)
 
 
 def test_window12_attention_multitrip(lib):
@@ -115,10 +78,10 @@ def test_window12_attention_multitrip(lib):
         require(fails, f"window-12 attention bwd {name}")
     require(check_fp32(gb, rb, rel=6e-3, block_rel=6e-3), "window-12 attention dbias")
     # a second run repeats every output bit for bit
-    first = WA.digest(out, lse, dqkv, dbias)
+    first = digest(out, lse, dqkv, dbias)
     rc_f, rc_b, out2, lse2, dqkv2, dbias2 = WA.run(lib, qkv, dout, bias, *case)
     assert rc_f == 0 and rc_b == 0
-    assert WA.digest(out2, lse2, dqkv2, dbias2) == first
+    assert digest(out2, lse2, dqkv2, dbias2) == first
 
 
 def test_window12_accumulate_adds_onto_dbias(lib):
@@ -140,7 +103,7 @@ def test_window12_attention_is_bitwise_reproducible(lib):
     def once():
         rc_f, rc_b, out, lse, dqkv, dbias = WA.run(lib, qkv, dout, bias, *case)
         assert rc_f == 0 and rc_b == 0
-        return WA.digest(out, lse, dqkv, dbias)
+        return digest(out, lse, dqkv, dbias)
 
     assert once() == once()
 
@@ -149,18 +112,18 @@ def test_window12_attention_is_bitwise_reproducible(lib):
                                                   (1, 24, 24, 2, 12, 6, 64), (1, 30, 24, 2, 12, 6, 32), (1, 24, 24, 2, 12, 12, 32)])
 def test_window12_neighbours_are_refused_and_write_nothing(lib, B, Hs, Ws, H, ws, shift, d):
     Tw = ws * ws
-    qkv = WA.rnd_bf16(B * Hs * Ws, 3 * H * d, seed=1)
-    dout = WA.rnd_bf16(B * Hs * Ws, H * d, seed=2)
+    qkv = rnd_bf16(B * Hs * Ws, 3 * H * d, seed=1)
+    dout = rnd_bf16(B * Hs * Ws, H * d, seed=2)
     bias = torch.zeros(H, Tw, Tw)
     rc_f, rc_b, out, lse, dqkv, dbias = WA.run(lib, qkv, dout, bias, B, Hs, Ws, H, ws, shift, d=d)
-    assert rc_f == WA.ICAMD_ERR_UNSUPPORTED and rc_b == WA.ICAMD_ERR_UNSUPPORTED, (rc_f, rc_b)
+    assert rc_f == UNSUPPORTED and rc_b == UNSUPPORTED, (rc_f, rc_b)
     for t in (out, lse, dqkv, dbias):
         assert bool(torch.isnan(t.float()).all()), "a refused call wrote to an output"
 
 
 @pytest.mark.parametrize("H", [1, 3])
 def test_window12_relpos_gather_and_scatter(lib, H):
-    hip = _hip()
+    h = hip()
     ws = 12
     L = 2 * ws - 1
     g = torch.Generator().manual_seed(7 * ws + H)
@@ -168,21 +131,19 @@ def test_window12_relpos_gather_and_scatter(lib, H):
     idx = relative_position_index(ws)
     want = table[idx.view(-1)].view(T, T, H).permute(2, 0, 1).contiguous()
     td = table.to(DEV)
-    bias, bias_w = WA.guarded_f32(H * T * T, float("nan"))
-    assert lib.icamd_relpos_bias_gather(hip.ptr(td), hip.ptr(bias), H, ws, hip.stream_ptr()) == 0
-    torch.cuda.synchronize()
-    assert WA.band_intact(bias_w, H * T * T, WA.SENT32)
+    bias, bias_g = guarded((H * T, T), torch.float32, float("nan"))
+    assert lib.icamd_relpos_bias_gather(h.ptr(td), h.ptr(bias), H, ws, h.stream_ptr()) == 0
+    assert intact(bias_g)
     assert torch.equal(bias.cpu().view(H, T, T), want)                     # bit for bit
     d = torch.randn(H, T, T, generator=g)
     want_t = torch.zeros(L * L, H, dtype=torch.float64).index_add_(0, idx.view(-1), d.double().permute(1, 2, 0).reshape(T * T, H))
     dd = d.to(DEV)
-    dtab, dtab_w = WA.guarded_f32(L * L * H, float("nan"))
-    assert lib.icamd_relpos_bias_scatter(hip.ptr(dd), hip.ptr(dtab), H, ws, 0, hip.stream_ptr()) == 0
-    torch.cuda.synchronize()
-    assert WA.band_intact(dtab_w, L * L * H, WA.SENT32)
+    dtab, dtab_g = guarded((L * L, H), torch.float32, float("nan"))
+    assert lib.icamd_relpos_bias_scatter(h.ptr(dd), h.ptr(dtab), H, ws, 0, h.stream_ptr()) == 0
+    assert intact(dtab_g)
     got_t = dtab.cpu().view(L * L, H).double()
     assert R.rel_l2(got_t, want_t) <= 1e-6
-    assert lib.icamd_relpos_bias_scatter(hip.ptr(dd), hip.ptr(dtab), H, ws, 1, hip.stream_ptr()) == 0
+    assert lib.icamd_relpos_bias_scatter(h.ptr(dd), h.ptr(dtab), H, ws, 1, h.stream_ptr()) == 0
     torch.cuda.synchronize()
     assert R.rel_l2(dtab.cpu().view(L * L, H).double(), 2 * want_t) <= 1e-6
     # <gather(t), d> == <t, scatter(d)> to fp32 rounding
@@ -192,6 +153,6 @@ def test_window12_relpos_gather_and_scatter(lib, H):
 
 
 def test_window7_still_runs_on_the_single_wave_kernels(lib):
-    """the dispatch on the window side did not capture small windows: a 7 x 7 case of tests/test_window_attention_gpu.py against its
+    """the dispatch on the window side did not capture small windows: a 7 x 7 case of tests/_window_attention.py against its
     reference under its bounds (the T = 144 kernels would index a 49-token window as if it had 144 slots)"""
-    WA.test_window_attention_matches_reference(lib, WA.CASES[0])
+    WA.check_case(lib, WA.CASES[0])
