@@ -22,6 +22,10 @@ ConvNeXt V2 (the `convnextv2_*` names, GRN_ARCHS) is the same class: its block h
 GlobalResponseNorm between GELU and fc2 (`mlp.grn.weight` / `mlp.grn.bias`, shape (4 dim,), initialised to zero; restated from
 memory like the V1 block, not pinned to a timm release): dw -> LN -> fc1 + GELU (z1, a) -> GRN (g) -> fc2 -> drop path -> residual.
 GRN is csrc/grn.hip (icamd_grn_fwd / icamd_grn_bwd; the backward also applies gelu'(z1), as fc2's data gradient does for V1).
+
+The small models (convnext_atto / femto / nano; their V2 twins are not registered, see CONFIGS) have widths that are no multiple
+of 32 (40, 48, 80): the depthwise kernels take C % 8 == 0 on their register-window form (csrc/dwconv.hip: dwconv7_wgrad_runs_kernel for the weight gradient), GRN C % 32 == 0; every
+other layer took these widths already.  `_workspace` raises where that form is switched off (ICAMD_DWCONV_ROWS=0).
 """
 import ctypes
 import os
@@ -40,13 +44,24 @@ LN_EPS = 1e-6
 _FUSED_LS = os.environ.get("ICAMD_FUSED_LAYERSCALE", "1") != "0"
 
 CONFIGS = {
+    # timm's small models (atto / femto / pico / nano: conv_mlp=True there, the same parameters as [out, in, 1, 1]); the widths that
+    # are no multiple of 32 (40, 48, 80) run on the C % 8 == 0 forms of icamd_dwconv7_* (dwconv7_wgrad_runs_kernel)
+    "convnext_atto": ((2, 2, 6, 2), (40, 80, 160, 320)),
+    "convnext_femto": ((2, 2, 6, 2), (48, 96, 192, 384)),
+    "convnext_pico": ((2, 2, 6, 2), (64, 128, 256, 512)),
+    "convnext_nano": ((2, 2, 8, 2), (80, 160, 320, 640)),
     "convnext_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
     "convnext_small": ((3, 3, 27, 3), (96, 192, 384, 768)),
+    "convnext_base": ((3, 3, 27, 3), (128, 256, 512, 1024)),
+    "convnext_large": ((3, 3, 27, 3), (192, 384, 768, 1536)),
     "convnext_test": ((1, 1, 2, 1), (32, 64, 128, 192)),   # small configuration for parity tests
+    "convnext_test_narrow": ((1, 1, 2, 1), (40, 80, 160, 320)),   # parity tests only: atto's widths
     # the backbone of tests/golden/convnext_ref_vectors.npz (vectors from the reference's own ConvNeXt class,
     # /root/reference/semantic_segmentation/backbone/convnext.py:58-150)
     "convnext_pin": ((1, 1, 1, 1), (32, 64, 96, 192)),
-    # ConvNeXt V2 (timm convnextv2_*; atto / femto / nano have dims that are no multiple of 32, which icamd_dwconv7_* requires)
+    # ConvNeXt V2 (timm convnextv2_*).  convnextv2_atto / femto / nano are not registered: the kernels take their widths (GRN at
+    # 4 dim = 160 included) and tests/test_convnext_small_gpu.py runs the class at them, but tests/test_convnextv2_cpu.py pins this
+    # list to the five names below and convnextv2_atto as a name train.py rejects
     "convnextv2_pico": ((2, 2, 6, 2), (64, 128, 256, 512)),
     "convnextv2_tiny": ((3, 3, 9, 3), (96, 192, 384, 768)),
     "convnextv2_base": ((3, 3, 27, 3), (128, 256, 512, 1024)),
@@ -247,7 +262,11 @@ class ConvNeXt(ArenaModel):
                     grn = max(grn, lib.icamd_grn_workspace_bytes(N, h * w, 4 * dim))
                 wg = max(wg, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(blk["fc1"].desc(N, h, w))),
                          lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(blk["fc2"].desc(N, h, w))))
-                dwg = max(dwg, lib.icamd_dwconv7_wgrad_workspace_bytes(N, h, w, dim))
+                dwb = lib.icamd_dwconv7_wgrad_workspace_bytes(N, h, w, dim)
+                if dim % 32 != 0 and dwb == 0:
+                    raise RuntimeError(f"{self.arch}: no depthwise 7x7 kernel for {N}x{h}x{w}x{dim}: widths that are no multiple of "
+                                       "32 run on the register-window kernels only (not with ICAMD_DWCONV_ROWS=0, tensors < 4 GB)")
+                dwg = max(dwg, dwb)
                 max_act = max(max_act, rows * 4 * dim)
             stages.append(sw)
         dl = self.dims[-1]

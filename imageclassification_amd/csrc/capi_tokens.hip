@@ -114,8 +114,8 @@ int icamd_dwconv7_dgrad(const void* dy, const void* w, const void* addend, void*
 }
 
 size_t icamd_dwconv7_wgrad_workspace_bytes(int N, int H, int W, int C) {
-  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 32 != 0) return 0;
-  return (size_t)icamd_dwconv7_wgrad_blocks(N, H, W, C) * 50 * C * sizeof(float);   // [blocks][49][C] + the bias rows [blocks][C]
+  if (!icamd_dwconv7_ok(N, H, W, C)) return 0;
+  return dw_wgrad_ws(nullptr, icamd_dwconv7_wgrad_blocks(N, H, W, C), C).bytes;   // [blocks][49][C] + the bias rows [blocks][C]
 }
 
 int icamd_dwconv7_wgrad(const void* x, const void* dy, float* dw, int accumulate, void* workspace, size_t workspace_bytes,
@@ -130,7 +130,7 @@ int icamd_dwconv7_wgrad(const void* x, const void* dy, float* dw, int accumulate
 }
 
 int icamd_dwconv7_wgrad_bias_supported(int N, int H, int W, int C) {
-  return (N > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0 && ::icamd_dwconv7_wgrad_bias_supported_cxx(N, H, W, C)) ? 1 : 0;
+  return ::icamd_dwconv7_wgrad_bias_supported_cxx(N, H, W, C) ? 1 : 0;
 }
 
 int icamd_dwconv7_wgrad_bias(const void* x, const void* dy, float* dw, float* dbias, int accumulate, void* workspace,

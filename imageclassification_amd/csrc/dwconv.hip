@@ -7,6 +7,7 @@
 // in/out, fp32 accumulation, filters stored tap-major [7][7][C] (bf16 shadow of the fp32 master).
 #include "common.h"
 #include "icamd_internal.h"
+#include "workspace.h"
 #include <cstdlib>
 
 namespace {
@@ -437,6 +438,41 @@ __global__ __launch_bounds__(256, 2) void dwconv7_wgrad_rows_kernel(const bf16_t
                       cpr_wg, groups, cslice, ib, nullptr);
 }
 
+// The same walk for widths that are no multiple of 32 (C % 8 == 0: ConvNeXt atto / femto / nano, 40 .. 640 channels).  There
+// cpr_wg need not divide 256: a workgroup is `groups` = 256 / cpr_wg (n, strip) items x cpr_wg channel pairs and its last
+// 256 - groups * cpr_wg threads idle (16 of 256 at C = 40, 48, 80).  cpr_wg is the whole pixel (C / 2 <= 256) or the largest
+// divisor of C / 2 up to 256, so a workgroup's lanes read whole channel runs and a cache line of x / dy has one reader.
+// The LDS sums and the partial rows are dw_wgrad_pass's: it indexes `red` by g * cpr_wg + l and never needed the product to be 256.
+__global__ __launch_bounds__(256, 2) void dwconv7_wgrad_runs_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+                                                                    float* __restrict__ part, float* __restrict__ part_b, int N,
+                                                                    int H, int W, int C, int nstrips, int groups, int cpr_wg) {
+  __shared__ float red[7 * 2 * 256];
+  // the geometry's range, said to the compiler: dwconv7_wgrad_rows_kernel's `256 / groups` carries it, a bare argument does not, and
+  // without it hipcc allocates 256 VGPRs and spills 193 into the row loops (with it: 230 and none, as the kernel above)
+  __builtin_assume(cpr_wg >= 4 && cpr_wg <= 256);
+  const int nslices = (C >> 1) / cpr_wg;
+  const int cslice = blockIdx.x % nslices;
+  const long long ib = blockIdx.x / nslices;
+  const int tid = threadIdx.x;
+  const int cpl = tid % cpr_wg, grp = tid / cpr_wg;
+  const long long item = ib * groups + grp;                 // (n, strip)
+  const bool active = grp < groups && item < (long long)N * nstrips;
+  const int c = (cslice * cpr_wg + cpl) * 2;
+  const int strip = active ? (int)(item % nstrips) : 0, n = active ? (int)(item / nstrips) : 0;
+  const int w0 = strip * 7;
+  unsigned int colmask = 0;
+#pragma unroll
+  for (int j = 0; j < 13; ++j) colmask |= ((unsigned)(w0 - 3 + j) < (unsigned)W ? 1u : 0u) << j;
+  const unsigned int cb = (unsigned)C * 2u, rowb = (unsigned)W * cb;
+  const unsigned int img = (unsigned)n * (unsigned)H * rowb;
+  const unsigned int xo = img + (unsigned)(w0 - 3) * cb + (unsigned)c * 2u;
+  const unsigned int dyo = img + (unsigned)w0 * cb + (unsigned)c * 2u;
+  dw_wgrad_pass<0, 4>((const unsigned char*)x, (const unsigned char*)dy, part, red, active, xo, dyo, cb, rowb, colmask, w0, H, W, C,
+                      cpr_wg, groups, cslice, ib, part_b);
+  dw_wgrad_pass<4, 3>((const unsigned char*)x, (const unsigned char*)dy, part, red, active, xo, dyo, cb, rowb, colmask, w0, H, W, C,
+                      cpr_wg, groups, cslice, ib, nullptr);
+}
+
 // out = inp + keep[b] * gamma[c] * z      (rows_per_image rows of C channels per sample; keep may be NULL)
 __global__ __launch_bounds__(256) void layerscale_fwd_kernel(const bf16_t* __restrict__ z, const bf16_t* __restrict__ inp,
                                                              const float* __restrict__ gamma, const float* __restrict__ keep,
@@ -516,10 +552,15 @@ static int dw_rows_mode() {   // ICAMD_DWCONV_ROWS=0: the LDS tile kernels of ro
 static bool dw_rows_usable(int N, int H, int W, int C) {
   return dw_rows_mode() && (long long)N * H * W * C * 2 < (1ll << 32);
 }
+// The widths the entries serve: C % 32 == 0 by either form; C % 8 == 0 by the register sliding-window kernels alone (the LDS tile
+// kernels work in 32-channel groups and are not built for narrower ones).  ONE predicate for every entry and the workspace size.
+bool icamd_dwconv7_ok(int N, int H, int W, int C) {
+  return N > 0 && H > 0 && W > 0 && C > 0 && (C % CG == 0 || (C % 8 == 0 && dw_rows_usable(N, H, W, C)));
+}
 
 int icamd_dwconv7_launch(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* addend, bf16_t* y, int N, int H,
                          int W, int C, int flip, hipStream_t s) {
-  if (C % CG != 0) return ICAMD_ERR_UNSUPPORTED;
+  if (!icamd_dwconv7_ok(N, H, W, C)) return ICAMD_ERR_UNSUPPORTED;
   if (dw_rows_usable(N, H, W, C)) {
     const int nstrips = (W + 6) / 7;
     // threads = channel pairs x strips x images: 98 304 = 1 536 waves on every ConvNeXt-T stage at batch 256; 246 VGPRs
@@ -559,11 +600,19 @@ int icamd_dwconv7_launch(const bf16_t* x, const bf16_t* w, const float* bias, co
 
 // rows form: workgroup = 256 threads = groups x (256 / groups) channel pairs; groups = 256 / min(C/2, 256) so that a
 // workgroup's lanes cover whole pixels' channel runs where C/2 < 256 (C/2 must then divide 256: 16, 32, 64, 128, 256) --
-// else (C/2 = 48, 96, 192, 384: ConvNeXt's dims) the largest power-of-two slice that divides C/2
-static void dw_wgrad_rows_geometry(int N, int W, int C, int* nstrips, int* groups, int* nslices, long long* iblocks) {
+// else (C/2 = 48, 96, 192, 384: ConvNeXt's dims) the largest power-of-two slice that divides C/2.
+// C % 32 != 0 (dwconv7_wgrad_runs_kernel): the slice is the whole pixel (C/2 <= 256) or the largest divisor of C/2 up to 256, and
+// groups = 256 / slice rounded down -- the rest of the workgroup idles.  C/2 is a multiple of 4, so the slice is 4 pairs at least.
+static void dw_wgrad_rows_geometry(int N, int W, int C, int* nstrips, int* groups, int* nslices, long long* iblocks, int* cpr_wg) {
   const int cpr = C / 2;
   int slice = 256;
-  while (cpr % slice != 0) slice >>= 1;            // C % 32 == 0  =>  slice >= 16
+  if (C % CG == 0) {
+    while (cpr % slice != 0) slice >>= 1;          // C % 32 == 0  =>  slice >= 16
+  } else {
+    slice = cpr < 256 ? cpr : 256;
+    while (cpr % slice != 0) --slice;
+  }
+  *cpr_wg = slice;
   *groups = 256 / slice;
   *nslices = cpr / slice;
   *nstrips = (W + 6) / 7;
@@ -573,8 +622,8 @@ static void dw_wgrad_rows_geometry(int N, int W, int C, int* nstrips, int* group
 
 int icamd_dwconv7_wgrad_blocks(int N, int H, int W, int C) {
   if (dw_rows_usable(N, H, W, C)) {
-    int nstrips, groups, nslices; long long ib;
-    dw_wgrad_rows_geometry(N, W, C, &nstrips, &groups, &nslices, &ib);
+    int nstrips, groups, nslices, cpr_wg; long long ib;
+    dw_wgrad_rows_geometry(N, W, C, &nstrips, &groups, &nslices, &ib, &cpr_wg);
     return (int)ib;
   }
   const long long tiles = (long long)N * ((H + TS - 1) / TS) * ((W + TS - 1) / TS);
@@ -586,18 +635,24 @@ int icamd_dwconv7_wgrad_blocks(int N, int H, int W, int C) {
 
 // dbias != NULL (round 5): sum(dy) per channel out of the same pass (rows kernel only: icamd_dwconv7_wgrad_bias_supported_cxx);
 // its partial rows [ib][C] follow the [ib][49][C] filter partials in the workspace
-bool icamd_dwconv7_wgrad_bias_supported_cxx(int N, int H, int W, int C) { return C % CG == 0 && dw_rows_usable(N, H, W, C); }
+bool icamd_dwconv7_wgrad_bias_supported_cxx(int N, int H, int W, int C) { return icamd_dwconv7_ok(N, H, W, C) && dw_rows_usable(N, H, W, C); }
 
 int icamd_dwconv7_wgrad_launch(const bf16_t* x, const bf16_t* dy, float* part, float* dw, float* dbias, int N, int H, int W, int C,
                                int accumulate, hipStream_t s) {
-  if (C % CG != 0) return ICAMD_ERR_UNSUPPORTED;
+  if (!icamd_dwconv7_ok(N, H, W, C)) return ICAMD_ERR_UNSUPPORTED;
   if (dw_rows_usable(N, H, W, C)) {
-    int nstrips, groups, nslices; long long ib;
-    dw_wgrad_rows_geometry(N, W, C, &nstrips, &groups, &nslices, &ib);
+    int nstrips, groups, nslices, cpr_wg; long long ib;
+    dw_wgrad_rows_geometry(N, W, C, &nstrips, &groups, &nslices, &ib, &cpr_wg);
     if (ib * nslices >= (1ll << 31)) return ICAMD_ERR_BAD_ARG;
-    float* part_b = dbias != nullptr ? part + ib * 49 * C : nullptr;
-    hipLaunchKernelGGL(dwconv7_wgrad_rows_kernel, dim3((unsigned)(ib * nslices)), dim3(256), 0, s, x, dy, part, part_b, N, H, W, C,
-                       nstrips, groups);
+    const DwWgradWs wsp = dw_wgrad_ws(part, ib, C);
+    part = wsp.part;
+    float* part_b = dbias != nullptr ? wsp.part_b : nullptr;
+    if (C % CG == 0)
+      hipLaunchKernelGGL(dwconv7_wgrad_rows_kernel, dim3((unsigned)(ib * nslices)), dim3(256), 0, s, x, dy, part, part_b, N, H, W, C,
+                         nstrips, groups);
+    else
+      hipLaunchKernelGGL(dwconv7_wgrad_runs_kernel, dim3((unsigned)(ib * nslices)), dim3(256), 0, s, x, dy, part, part_b, N, H, W, C,
+                         nstrips, groups, cpr_wg);
     int rc = icamd_launch_status();
     if (rc) return rc;
     rc = icamd_slab_reduce_launch(part, dw, 49ll * C, (int)ib, accumulate, s);

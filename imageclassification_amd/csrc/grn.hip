@@ -253,15 +253,16 @@ __global__ __launch_bounds__(GRN_THREADS) void grn_bwd_apply_kernel(const bf16_t
   }
 }
 
-// dgamma[c] (+)= sum_n fin[n][0][c], dbeta[c] (+)= sum_n fin[n][1][c]: 64 channels x 4 sample lanes per workgroup, the samples of a
-// lane in order, the lanes in order
+// dgamma[c] (+)= sum_n fin[n][0][c], dbeta[c] (+)= sum_n fin[n][1][c]: 64 channels (the last workgroup: what is left of C) x 4
+// sample lanes per workgroup, the samples of a lane in order, the lanes in order
 __global__ __launch_bounds__(GRN_THREADS) void grn_param_grads_kernel(const float* __restrict__ fin, float* __restrict__ dgamma,
                                                                       float* __restrict__ dbeta, int N, int C, int accumulate) {
   __shared__ float red[2][4][64];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), lane = threadIdx.x >> 6;
+  const bool live = c < C;   // C % 64 == 32: the upper half of the last workgroup's channels does not exist
   float p = 0.f, q = 0.f;
 #pragma unroll 4
-  for (int n = lane; n < N; n += 4) {
+  for (int n = live ? lane : N; n < N; n += 4) {
     p += fin[((long long)n * 2 + 0) * C + c];
     q += fin[((long long)n * 2 + 1) * C + c];
   }
@@ -272,22 +273,24 @@ __global__ __launch_bounds__(GRN_THREADS) void grn_param_grads_kernel(const floa
     const int which = threadIdx.x >> 6, cc = threadIdx.x & 63;
     const float t = ((red[which][0][cc] + red[which][1][cc]) + red[which][2][cc]) + red[which][3][cc];
     float* out = (which ? dbeta : dgamma) + blockIdx.x * 64 + cc;
-    *out = accumulate ? *out + t : t;
+    if (blockIdx.x * 64 + cc < C) *out = accumulate ? *out + t : t;
   }
 }
 
 // vector columns of a reduce workgroup: all of them up to 256, else the largest divisor of C / 8 that is a multiple of 8
+// (C % 64 == 0) or of 4 (C % 64 == 32: C / 8 is a multiple of 4 only)
 int reduce_tcols(int cpr) {
   if (cpr <= GRN_THREADS) return cpr;
-  for (int t = GRN_THREADS; t >= 8; t -= 8)
+  const int q = cpr % 8 == 0 ? 8 : 4;
+  for (int t = GRN_THREADS; t >= q; t -= q)
     if (cpr % t == 0) return t;
-  return 8;
+  return q;
 }
 
 }  // namespace
 
 bool icamd_grn_ok(int N, long long HW, int C) {
-  return N >= 1 && N <= 65535 && HW >= 1 && C >= 128 && C <= GRN_MAX_C && C % 64 == 0 && HW * C < (1ll << 31);
+  return N >= 1 && N <= 65535 && HW >= 1 && C >= 128 && C <= GRN_MAX_C && C % 32 == 0 && HW * C < (1ll << 31);
 }
 
 // S row segments per sample for the reductions (about 2048 workgroups over the batch, 32 rows and more each, at most 64 partial
@@ -342,6 +345,6 @@ int icamd_grn_bwd_launch(const bf16_t* dg, const bf16_t* a, const float* gx, con
   else
     hipLaunchKernelGGL(grn_bwd_apply_kernel<false>, dim3(B, N), dim3(GRN_THREADS), 2 * C * sizeof(float), s, dg, a, gx, gamma, z, dx,
                        part, fin, HW, C, S, rpb, eps);
-  hipLaunchKernelGGL(grn_param_grads_kernel, dim3(C / 64), dim3(GRN_THREADS), 0, s, fin, dgamma, dbeta, N, C, accumulate);
+  hipLaunchKernelGGL(grn_param_grads_kernel, dim3((C + 63) / 64), dim3(GRN_THREADS), 0, s, fin, dgamma, dbeta, N, C, accumulate);
   return icamd_launch_status();
 }

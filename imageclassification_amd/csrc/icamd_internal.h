@@ -399,6 +399,7 @@ int icamd_window_attention_w12_bwd_launch(const bf16_t* qkv, const float* bias, 
 // ConvNeXt: depthwise 7x7, layer scale / stochastic depth (dwconv.hip)
 int icamd_dwconv7_launch(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* addend, bf16_t* y, int N, int H,
                          int W, int C, int flip, hipStream_t s);
+bool icamd_dwconv7_ok(int N, int H, int W, int C);   // C % 32 == 0, or C % 8 == 0 where the register-window kernels run
 int icamd_dwconv7_wgrad_blocks(int N, int H, int W, int C);
 int icamd_dwconv7_wgrad_launch(const bf16_t* x, const bf16_t* dy, float* part, float* dw, float* dbias, int N, int H, int W, int C,
                                int accumulate, hipStream_t s);

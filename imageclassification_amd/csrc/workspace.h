@@ -96,6 +96,18 @@ inline ImageAugWs image_aug_ws(void* base, int B, long long tab_words, int max_c
   return w;
 }
 
+// ---- depthwise 7x7 weight gradient (dwconv.hip): one partial filter row [49][C] per workgroup row | one bias row [C] each, sized
+// whether or not the bias is asked for   (fp32, neither rounded)
+struct DwWgradWs { float *part, *part_b; size_t bytes; };
+inline DwWgradWs dw_wgrad_ws(void* base, long long blocks, int C) {
+  WsCarver c(base);
+  DwWgradWs w;
+  w.part = c.take_exact<float>((size_t)blocks * 49 * C);
+  w.part_b = c.take_exact<float>((size_t)blocks * C);
+  w.bytes = c.bytes();
+  return w;
+}
+
 // ---- dense weight gradient (capi.hip): S filter slabs [S][Cout][Ktot] | S bias rows [S][Cout]   (fp32, neither rounded) --------
 struct WgradWs { float *slab, *bias_slab; size_t bytes; };
 inline WgradWs wgrad_ws(void* base, int S, int Cout, int Ktot) {

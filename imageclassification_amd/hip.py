@@ -207,7 +207,7 @@ _SIGNATURES = {
 # answers without a GPU, recorded from the library before the C-ABI layer was split into units; that record covers _SIGNATURES and
 # stays as it is).  Same form, bound by load() like the others; the tests that arrive with an entry hold its host layer.
 _SIGNATURES_ADDED = {
-    # ConvNeXt V2 (csrc/grn.hip): global response normalisation over [N][rows_per_image][C], C % 64 == 0, 128 <= C <= 6144
+    # ConvNeXt V2 (csrc/grn.hip): global response normalisation over [N][rows_per_image][C], C % 32 == 0, 128 <= C <= 6144
     "icamd_grn_supported": (c_int, [c_int, c_longlong, c_int]),
     "icamd_grn_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),
     "icamd_grn_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_float, _P, c_size_t, _P]),

@@ -264,8 +264,12 @@ int icamd_colsum_rows(const void* x, long long rows, int ld, int cols, float* ou
                       size_t workspace_bytes, void* stream);
 
 /* ---- ConvNeXt block pieces (/root/reference/semantic_segmentation/backbone/convnext.py:21-56; timm convnext_tiny
- *      under train.py:194).  Depthwise 7x7 pad 3: x, y NHWC bf16 [N,H,W,C] (C % 32 == 0), w bf16 [7][7][C] (tap-major
- *      shadow of the [C,1,7,7] parameter), bias fp32 [C]. ---------------------------------------------------------- */
+ *      under train.py:194).  Depthwise 7x7 pad 3: x, y NHWC bf16 [N,H,W,C] (C % 8 == 0), w bf16 [7][7][C] (tap-major
+ *      shadow of the [C,1,7,7] parameter), bias fp32 [C].
+ *      C % 32 == 0 runs everywhere.  C % 32 != 0 (40, 48, 80: ConvNeXt atto / femto / nano) runs on the register-sliding-window
+ *      kernels alone: with ICAMD_DWCONV_ROWS=0, or on a tensor of 4 GB and more, every entry below returns
+ *      ICAMD_ERR_UNSUPPORTED (the weight-gradient entries ICAMD_ERR_WORKSPACE) before anything is written, _workspace_bytes and
+ *      _supported return 0.  So does every entry for C % 8 != 0. --------------------------------------------------------- */
 int icamd_dwconv7_fwd(const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int C, void* stream);
 /* dx = depthwise-conv-transpose(dy, w) (+ addend: the residual branch's gradient) */
 int icamd_dwconv7_dgrad(const void* dy, const void* w, const void* addend, void* dx, int N, int H, int W, int C, void* stream);
@@ -275,7 +279,8 @@ int icamd_dwconv7_wgrad(const void* x, const void* dy, float* dw, int accumulate
                         int N, int H, int W, int C, void* stream);
 /* Round 5: the same pass also leaves the bias gradient dbias fp32 [C] (+)= sum over pixels dy (every dy row passes through the
  * kernel's registers once): replaces a separate icamd_colsum_rows pass over dy.  _supported: 1 where the register-sliding-window
- * kernel runs (the shapes of ConvNeXt-T at any batch); elsewhere the call returns ICAMD_ERR_UNSUPPORTED and the two calls remain. */
+ * kernel runs (the shapes of every ConvNeXt here at any batch, C % 8 == 0); elsewhere the call returns ICAMD_ERR_UNSUPPORTED and
+ * the two calls remain. */
 int icamd_dwconv7_wgrad_bias_supported(int N, int H, int W, int C);
 int icamd_dwconv7_wgrad_bias(const void* x, const void* dy, float* dw, float* dbias, int accumulate, void* workspace,
                              size_t workspace_bytes, int N, int H, int W, int C, void* stream);
@@ -321,7 +326,7 @@ int icamd_layerscale_param_grads(const float* G, const float* w, const float* bi
  * where Gx = 0); with z given (the tensor a = gelu(z) came from) dx = d z = that value * gelu'(z), rounded once.  dgamma / dbeta: fp32
  * [C], (+)= under `accumulate`.  Two passes over the wide tensors each way (per-workgroup partial sums in the workspace, summed in a
  * fixed order: no atomics, the same bits on every launch), and one [N][C]-sized launch for the parameter gradients.
- * _supported: C % 64 == 0, 128 <= C <= 6144, N <= 65535, rows_per_image * C < 2^31; elsewhere both calls return
+ * _supported: C % 32 == 0, 128 <= C <= 6144, N <= 65535, rows_per_image * C < 2^31; elsewhere both calls return
  * ICAMD_ERR_UNSUPPORTED before anything is written and _workspace_bytes returns 0. */
 int icamd_grn_supported(int N, long long rows_per_image, int C);
 size_t icamd_grn_workspace_bytes(int N, long long rows_per_image, int C);

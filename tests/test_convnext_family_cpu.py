@@ -1,0 +1,137 @@
+"""The ConvNeXt family without a GPU: the table of timm's names (atto .. large, V1 and V2), the parameter counts by the layer-list
+formula of tests/_convnext_narrow.py (which also gives the V2 counts tests/_convnextv2_ref.py holds and V1 tiny's known figure), the
+constructed models' own counts, the command-line surface, and the depthwise weight-gradient geometry for widths that are no
+multiple of 32 at the shapes tests/test_dwconv_narrow_gpu.py runs."""
+import importlib.util
+import os
+import sys
+
+import pytest
+
+import _convnextv2_ref
+from _convnext_narrow import FAMILY, NARROW, V2_UNREGISTERED, dw_wgrad_geometry, narrow_registered, param_count
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _load(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", "golden", name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+L = _load("make_arena_layouts")
+
+
+@pytest.fixture()
+def stubs(monkeypatch):
+    L.install_stubs(monkeypatch.setattr)
+
+
+V2_BUILT = ("pico", "tiny", "base", "large")        # the V2 names the package lists (tests/test_convnextv2_cpu.py pins them)
+
+
+def test_configs_hold_the_family_table():
+    from imageclassification_amd import convnext
+    for stem, (depths, dims, _, _) in FAMILY.items():
+        assert convnext.CONFIGS["convnext_" + stem] == (depths, dims), stem
+    for stem in V2_BUILT:
+        assert convnext.CONFIGS["convnextv2_" + stem] == FAMILY[stem][:2], stem
+    assert convnext.CONFIGS["convnext_test_narrow"] == NARROW
+    v2 = {"convnextv2_" + s for s in V2_BUILT} | {"convnextv2_test"}
+    assert convnext.GRN_ARCHS == v2
+    assert set(convnext.CONFIGS) == v2 | {"convnext_" + s for s in FAMILY} | {"convnext_test", "convnext_test_narrow", "convnext_pin"}
+    for left_out in ("convnext_xlarge", "convnextv2_huge", "convnext_nano_ols", "convnext_pico_ols", "convnext_atto_ols",
+                     "convnext_tiny_hnf", "convnextv2_small", *V2_UNREGISTERED):
+        assert left_out not in convnext.CONFIGS
+    for depths, dims in convnext.CONFIGS.values():
+        assert all(d % 8 == 0 for d in dims)                      # the rule of icamd_dwconv7_*, icamd_conv2d_* and icamd_layernorm_*
+        assert all((4 * d) % 32 == 0 and 128 <= 4 * d <= 6144 for d in dims)      # icamd_grn_supported
+
+
+def test_registration_for_a_test_is_undone():
+    from imageclassification_amd import convnext
+    from oracle import convnext_ref
+    before = (dict(convnext.CONFIGS), convnext.GRN_ARCHS, dict(convnext_ref.CONFIGS), dict(_convnextv2_ref.CONFIGS))
+    with narrow_registered():
+        assert set(V2_UNREGISTERED) <= convnext.GRN_ARCHS and convnext.CONFIGS["convnextv2_atto"] == FAMILY["atto"][:2]
+        assert "convnextv2_test_narrow" in _convnextv2_ref.CONFIGS and "convnext_test_narrow" in convnext_ref.CONFIGS
+    assert before == (dict(convnext.CONFIGS), convnext.GRN_ARCHS, dict(convnext_ref.CONFIGS), dict(_convnextv2_ref.CONFIGS))
+
+
+def test_parameter_count_formula():
+    for stem, (depths, dims, v1, v2) in FAMILY.items():
+        if v1 is not None:
+            assert param_count(depths, dims, False) == v1, stem
+        if v2 is not None:
+            assert param_count(depths, dims, True) == v2, stem
+    for name, n in _convnextv2_ref.PARAM_COUNTS.items():          # the four V2 counts the README already stated
+        assert param_count(*_convnextv2_ref.CONFIGS[name], True) == n, name
+
+
+@pytest.mark.parametrize("arch", ["convnext_atto", "convnextv2_atto", "convnext_femto", "convnextv2_femto", "convnext_pico",
+                                  "convnext_nano", "convnextv2_nano"])
+def test_constructed_models_have_the_counts(stubs, arch):
+    from imageclassification_amd.convnext import ConvNeXt
+    with narrow_registered():        # the V2 names of narrow widths are not the package's: the class builds them all the same
+        net = ConvNeXt(arch, 1000, device="cpu", seed=0)
+    total = 0
+    for p in net.params.values():
+        n = 1
+        for d in p.torch_shape:
+            n *= d
+        total += n
+    family, stem = arch.split("_", 1)
+    assert total == FAMILY[stem][3 if family == "convnextv2" else 2]
+    assert net.grn == (family == "convnextv2") and net.fused_ls == (not net.grn)
+    names = list(net.params)
+    assert ("stages.0.blocks.0.gamma" in names) == (not net.grn) and ("stages.0.blocks.0.mlp.grn.weight" in names) == net.grn
+
+
+def test_command_line_surface(stubs, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import train as TR
+    from imageclassification_amd.convnext import ConvNeXt
+
+    class OnCpu(ConvNeXt):
+        def __init__(self, arch, num_classes, **kw):
+            super().__init__(arch, num_classes, device="cpu", seed=0, **kw)
+
+    monkeypatch.setattr(TR, "ConvNeXt", OnCpu)
+    for name in ("convnext_atto", "convnext_femto", "convnext_pico", "convnext_nano", "convnext_base", "convnext_large",
+                 "convnext_test_narrow"):
+        assert TR.get_args_parser().parse_args(["--model", name]).model == name
+        net = TR.create_model(name, 10, 224, 0.1)
+        assert net.arch == name and net.drop_path_rate == 0.1                 # --drop_path reaches every convnext*
+        assert abs(net.stages[-1]["blocks"][-1]["rate"] - 0.1) < 1e-7 and net.stages[0]["blocks"][0]["rate"] == 0.0
+    with pytest.raises(ValueError) as e:
+        TR.create_model("convnext_xlarge", 10, 224, 0.1)
+    for name in ("convnext_atto", "convnext_nano", "convnext_large", "convnextv2_pico"):
+        assert name in str(e.value)
+    for name in ("convnextv2_huge", *V2_UNREGISTERED):
+        with pytest.raises(ValueError):
+            TR.create_model(name, 10, 224, 0.1)
+
+
+def test_weight_gradient_geometry_of_the_gpu_cases():
+    """The cases of tests/test_dwconv_narrow_gpu.py and the loops its docstring says they repeat."""
+    g = dw_wgrad_geometry(2, 14, 14, 40)
+    assert (g["slice"], g["groups"], g["idle"], g["nslices"], g["iblocks"]) == (20, 12, 16, 1, 1)
+    assert g["trips"]["lds outputs (idx += 256)"] == 2 and g["trips"]["groups summed"] == 12
+    g = dw_wgrad_geometry(70, 3, 5, 24)
+    assert (g["slice"], g["groups"], g["idle"], g["iblocks"]) == (12, 21, 4, 4) and g["trips"]["slab rows folded"] == 4
+    g = dw_wgrad_geometry(2, 29, 31, 40)
+    assert g["nstrips"] == 5 and g["trips"]["rows, first pass (base += 4)"] == 8 and g["trips"]["rows, second pass (base += 3)"] == 10
+    g = dw_wgrad_geometry(3, 33, 6, 200)
+    assert (g["slice"], g["groups"], g["idle"], g["iblocks"]) == (100, 2, 56, 2) and g["trips"]["lds outputs (idx += 256)"] == 6
+    g = dw_wgrad_geometry(2, 6, 6, 520)
+    assert (g["slice"], g["groups"], g["idle"], g["nslices"], g["iblocks"]) == (130, 1, 126, 2, 2)
+    assert g["trips"]["lds outputs (idx += 256)"] == 8 and g["trips"]["bias lds outputs"] == 2
+    g = dw_wgrad_geometry(1, 1, 1, 8)
+    assert (g["slice"], g["groups"], g["iblocks"], g["workspace"]) == (4, 64, 1, 1600)
+    # the stage shapes of atto, femto and nano at batch 256: 16 idle lanes of 256 or none, one slice
+    for C in (40, 48, 80, 160, 320, 640):
+        if C % 32:
+            g = dw_wgrad_geometry(256, 56, 56, C)
+            assert g["nslices"] == 1 and g["idle"] <= 16, C
