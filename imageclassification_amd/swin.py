@@ -2,7 +2,7 @@
 forward and backward.
 
 The reference builds every model with timm.create_model(args.model) (/root/reference/train.py:194).  Architecture restated from
-the published source (timm is absent; parity is against tests/_swin_ref.py, "timm-unpinned" like ViT and ResNet here):
+the published source (timm is absent; parity is against oracle/swin_ref.py, "timm-unpinned" like ViT and ResNet here):
 4x4/4 patch-embedding conv + bias and a LayerNorm, four stages of pre-LayerNorm blocks (eps 1e-5) whose attention runs inside
 7x7 (or 12x12: CONFIGS_W12) windows with 32-wide heads, a learned relative-position bias and, in every second block, a cyclic
 shift by half the window with its region mask; stage i > 0 opens with patch merging (2x2 gather -> LayerNorm(4C) -> bias-free Linear 4C -> 2C, current timm's placement);

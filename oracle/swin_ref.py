@@ -1,4 +1,5 @@
-"""CPU oracle for the Swin Transformer family (TEST INFRASTRUCTURE ONLY): timm's `swin_*_patch4_window7_224` in plain torch.
+"""CPU oracle for the Swin Transformer family (TEST INFRASTRUCTURE ONLY): timm's `swin_*_patch4_window7_224` and
+`swin_base_patch4_window12_384` in plain torch.
 
 timm is absent, so the architecture is restated the way timm writes it -- `torch.roll`, `window_partition` / `window_reverse`, the
 `img_mask` built by slices, the `relative_position_index` buffer, patch merging at the head of stages 1.. -- with timm's module and
@@ -12,13 +13,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from oracle.resnet_ref import _RoundBF16, _RoundWeight
+from .resnet_ref import _RoundBF16, _RoundWeight
 
+# (embed dim, depths, heads, window)
 CONFIGS = {
     "swin_tiny_patch4_window7_224": (96, (2, 2, 6, 2), (3, 6, 12, 24), 7),
     "swin_small_patch4_window7_224": (96, (2, 2, 18, 2), (3, 6, 12, 24), 7),
     "swin_base_patch4_window7_224": (128, (2, 2, 18, 2), (4, 8, 16, 32), 7),
     "swin_test": (32, (2, 2), (1, 2), 7),
+    "swin_base_patch4_window12_384": (128, (2, 2, 18, 2), (4, 8, 16, 32), 12),
+    "swin_test_w12": (32, (2, 2), (1, 2), 12),
 }
 
 

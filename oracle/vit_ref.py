@@ -15,6 +15,8 @@ from .resnet_ref import _RoundBF16, _RoundWeight
 
 CONFIGS = {"vit_base_patch16_224": (16, 768, 12, 12, 4), "vit_small_patch16_224": (16, 384, 12, 6, 4),
            "vit_tiny_test": (16, 128, 2, 2, 4)}
+CONFIGS.update({"vit_base_patch16_384": CONFIGS["vit_base_patch16_224"],      # the same networks: the size is img_size=
+                "vit_small_patch16_384": CONFIGS["vit_small_patch16_224"]})
 
 
 def _r(x, on):

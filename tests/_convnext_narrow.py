@@ -1,14 +1,13 @@
 """Shared by the tests of the small ConvNeXt models (widths that are no multiple of 32): the family table and its parameter counts,
-the registration of the parity configurations with the oracles and of the narrow V2 names with the package for the length of a test,
-a Python mirror of the depthwise weight-gradient geometry, and the GRN entries on tensors.
+the registration of the narrow V2 names with the package for the length of a test, Python mirrors of the depthwise weight-gradient
+geometry and of the GRN launch planner, and the GRN entries on tensors.
 
 Importing this module needs no GPU and makes no CUDA call."""
 import contextlib
 
 import torch
 
-import _convnextv2_ref
-from oracle import convnext_ref
+from oracle.convnext_ref import GRN_EPS
 
 # name stem -> (depths, dims, V1 parameters at 1000 classes or None, V2 parameters or None)
 FAMILY = {
@@ -44,20 +43,17 @@ V2_UNREGISTERED = {"convnextv2_atto": FAMILY["atto"][:2], "convnextv2_femto": FA
 
 @contextlib.contextmanager
 def narrow_registered():
-    """For the length of a `with`: the two parity configurations in the oracles' in-memory tables (the oracle files know the
-    32-multiple widths only), and the V2 models of narrow widths in convnext.CONFIGS / GRN_ARCHS.  The class and the kernels run
+    """For the length of a `with`: the V2 models of narrow widths in convnext.CONFIGS / GRN_ARCHS.  The class and the kernels run
     those, but the package does not list them (tests/test_convnextv2_cpu.py pins its V2 names to the oracle's), so the tests that
-    drive the V2 block at these widths add them here.  Everything is taken out again: other test modules compare these tables."""
+    drive the V2 block at these widths add them here.  Everything is taken out again: other test modules compare these tables.
+    (The oracle needs no registration: it builds any (depths, dims) pair.)"""
     from imageclassification_amd import convnext
     grn = convnext.GRN_ARCHS
-    convnext_ref.CONFIGS["convnext_test_narrow"] = NARROW
-    _convnextv2_ref.CONFIGS["convnextv2_test_narrow"] = NARROW
     convnext.CONFIGS.update(V2_UNREGISTERED)
     convnext.GRN_ARCHS = grn | set(V2_UNREGISTERED)
     try:
         yield
     finally:
-        del convnext_ref.CONFIGS["convnext_test_narrow"], _convnextv2_ref.CONFIGS["convnextv2_test_narrow"]
         for name in V2_UNREGISTERED:
             del convnext.CONFIGS[name]
         convnext.GRN_ARCHS = grn
@@ -84,6 +80,28 @@ def dw_wgrad_geometry(N, H, W, C):
                       "bias lds outputs": cdiv(2 * slice_, 256), "slab rows folded": iblocks}}
 
 
+def grn_plan(N, HW, C):
+    """icamd_grn_plan and reduce_tcols (csrc/grn.hip), and the trip count of every loop of its kernels whose length depends on
+    the problem, for the busiest thread."""
+    cpr = C // 8
+    S = max(min(cdiv(2048, N), cdiv(HW, 32), 64), 1)
+    rps = cdiv(HW, S)
+    S = cdiv(HW, rps)
+    B = max(min(cdiv(HW * cpr, 1024), cdiv(4096, N), cdiv(HW, 8)), 1)
+    rpb = cdiv(HW, B)
+    B = cdiv(HW, rpb)
+    tcols = cpr if cpr <= 256 else max(t for t in range(8, 257, 8) if cpr % t == 0)
+    rlanes = 256 // tcols
+    return {"S": S, "rps": rps, "B": B, "rpb": rpb, "tcols": tcols, "ctiles": cpr // tcols, "rlanes": rlanes,
+            "trips": {"reduce rows": cdiv(rps, rlanes),                  # grn_reduce_kernel: r += rlanes
+                      "reduce lds outputs": cdiv(tcols * 8, 256),        # o += 256 (the backward's walks twice as far)
+                      "reduce row lanes": rlanes,                        # l < rlanes
+                      "prologue channels": cdiv(C, 1024),                # c4 += 256, four channels each (grn_stats, s / t loops)
+                      "prologue segments": S,                            # s < S
+                      "apply vectors": cdiv(rpb * cpr, 256),             # i += 256
+                      "parameter-gradient samples": cdiv(N, 4)}}         # grn_param_grads_kernel: n += 4
+
+
 class Grn:
     """icamd_grn_fwd / icamd_grn_bwd on tensors"""
 
@@ -97,7 +115,7 @@ class Grn:
     def fwd(self, a, gamma, beta):
         g, gx = torch.empty_like(a), torch.empty(self.N, self.C, device="cuda")
         rc = self.lib.icamd_grn_fwd(a.data_ptr(), gamma.data_ptr(), beta.data_ptr(), g.data_ptr(), gx.data_ptr(), self.N, self.HW,
-                                    self.C, _convnextv2_ref.GRN_EPS, self.ws.data_ptr(), self.bytes, self.hip.stream_ptr())
+                                    self.C, GRN_EPS, self.ws.data_ptr(), self.bytes, self.hip.stream_ptr())
         return rc, g, gx
 
     def bwd(self, dg, a, gx, gamma, z=None, dgamma=None, dbeta=None, accumulate=0):
@@ -106,5 +124,5 @@ class Grn:
         dbeta = torch.empty(self.C, device="cuda") if dbeta is None else dbeta
         rc = self.lib.icamd_grn_bwd(dg.data_ptr(), a.data_ptr(), gx.data_ptr(), gamma.data_ptr(), None if z is None else z.data_ptr(),
                                     dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), accumulate, self.N, self.HW, self.C,
-                                    _convnextv2_ref.GRN_EPS, self.ws.data_ptr(), self.bytes, self.hip.stream_ptr())
+                                    GRN_EPS, self.ws.data_ptr(), self.bytes, self.hip.stream_ptr())
         return rc, dx, dgamma, dbeta

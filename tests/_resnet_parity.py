@@ -1,27 +1,14 @@
 """What the ResNet-family parity tests share: the reference / HIP pair builders and the whole-network protocol, split at the
 CPU / GPU line.  yardstick() -- the reference against its own fp64 copy -- needs no GPU; hip_rows() runs the HIP path on the
 same batch.  The caps on the yardstick, the tensor counts and what a family prints beyond this stay in that family's test."""
-import copy
 from collections import namedtuple
 
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
+from _parity import hip_step, oracle_step, xent_backward  # noqa: F401  (xent_backward: for the family tests that import it here)
 from oracle import ops_ref as R
 from oracle.resnet_ref import ResNetRef, _Block
-
-
-def xent_backward(net, ws, targets, num_classes, smoothing=0.0):
-    from imageclassification_amd import hip
-    lib = net.lib
-    B = targets.shape[0]
-    hip.check(lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, num_classes, targets.data_ptr(), None, 1.0,
-                                     smoothing, 1.0 / B, ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(),
-                                     ws["dlogits"].data_ptr(), hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
-    return float(ws["loss_rows"].mean())
 
 
 def named_shapes(model):
@@ -89,28 +76,20 @@ HipResult = namedtuple("HipResult", "err_logits loss rows zero_branch mean_err w
 
 def yardstick(ref, x, y, smoothing):
     """The reference and its fp64 copy (same rounding points) take one training forward + backward on the CPU."""
-    ref64 = copy.deepcopy(ref).double()
-    ref.train(); ref64.train()
-    out = ref(x)
-    loss = F.cross_entropy(out, y, label_smoothing=smoothing)
-    loss.backward()
-    out64 = ref64(x.double())
-    F.cross_entropy(out64, y, label_smoothing=smoothing).backward()
-    p64 = dict(ref64.named_parameters())
+    ref.train()                      # the twin is a copy: it trains too
+    o = oracle_step(ref, x, y, smoothing)
+    p64 = dict(o.ref64.named_parameters())
     grads = {n: p.grad for n, p in ref.named_parameters()}
     noise = {n: R.rel_l2(p64[n].grad.float(), g) for n, g in grads.items() if float(g.abs().max()) != 0.0}
-    return Yardstick(out.detach(), float(loss.detach()), grads, R.rel_l2(out64.detach().float(), out.detach()), noise,
+    return Yardstick(o.out, o.loss, grads, R.rel_l2(o.out64, o.out), noise,
                      sum(noise.values()) / len(noise), max(noise.items(), key=lambda kv: kv[1]))
 
 
 def hip_rows(net, x, y, num_classes, smoothing, yard):
     """The HIP path on the yardstick's batch.  Where the reference's gradient is all zero (zero-gamma branches) the HIP
     gradient is asserted exactly zero and counted; every other tensor gets a row."""
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    hip_loss = xent_backward(net, ws, y.cuda(), num_classes, smoothing=smoothing)
-    err_logits = R.rel_l2(logits[:, :num_classes].float().cpu(), yard.logits)
+    _, logits, hip_loss = hip_step(net, x, y, num_classes, smoothing)
+    err_logits = R.rel_l2(logits, yard.logits)
     rows, zero_branch = [], 0
     for name, grad in yard.grads.items():
         if name not in yard.noise:

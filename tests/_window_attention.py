@@ -1,10 +1,10 @@
 """Shared by the window-attention tests (tests/test_window_attention_gpu.py, tests/test_window_attention_w12_gpu.py,
 tests/test_multitrip_gpu.py, tests/test_attention_ranges_gpu.py): cases, seeded operands, the guarded forward + backward launch, the
-cached fp64 reference (tests/_swin_ref.py window_attention_ref) and the parity check of one case.  Importing it needs no GPU."""
+cached fp64 reference (oracle/swin_ref.py window_attention_ref) and the parity check of one case.  Importing it needs no GPU."""
 import torch
 
 from _harness import DEV, guarded, hip, intact, rnd_bf16
-from _swin_ref import window_attention_ref
+from oracle.swin_ref import window_attention_ref
 from oracle import ops_ref as R
 
 D = 32

@@ -25,7 +25,7 @@ import _attention_long as AL
 import _attention_ranges as AR
 import _window_attention as WA
 from _harness import lib  # noqa: F401
-from _swin_ref import window_attention_ref
+from oracle.swin_ref import window_attention_ref
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu

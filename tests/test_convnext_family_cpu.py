@@ -1,5 +1,5 @@
 """The ConvNeXt family without a GPU: the table of timm's names (atto .. large, V1 and V2), the parameter counts by the layer-list
-formula of tests/_convnext_narrow.py (which also gives the V2 counts tests/_convnextv2_ref.py holds and V1 tiny's known figure), the
+formula of tests/_convnext_narrow.py (which also gives the V2 counts oracle/convnext_ref.py holds and V1 tiny's known figure), the
 constructed models' own counts, the command-line surface, and the depthwise weight-gradient geometry for widths that are no
 multiple of 32 at the shapes tests/test_dwconv_narrow_gpu.py runs."""
 import importlib.util
@@ -8,8 +8,8 @@ import sys
 
 import pytest
 
-import _convnextv2_ref
 from _convnext_narrow import FAMILY, NARROW, V2_UNREGISTERED, dw_wgrad_geometry, narrow_registered, param_count
+from oracle import convnext_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,12 +52,14 @@ def test_configs_hold_the_family_table():
 
 def test_registration_for_a_test_is_undone():
     from imageclassification_amd import convnext
-    from oracle import convnext_ref
-    before = (dict(convnext.CONFIGS), convnext.GRN_ARCHS, dict(convnext_ref.CONFIGS), dict(_convnextv2_ref.CONFIGS))
+    before = (dict(convnext.CONFIGS), convnext.GRN_ARCHS, dict(convnext_ref.CONFIGS))
     with narrow_registered():
         assert set(V2_UNREGISTERED) <= convnext.GRN_ARCHS and convnext.CONFIGS["convnextv2_atto"] == FAMILY["atto"][:2]
-        assert "convnextv2_test_narrow" in _convnextv2_ref.CONFIGS and "convnext_test_narrow" in convnext_ref.CONFIGS
-    assert before == (dict(convnext.CONFIGS), convnext.GRN_ARCHS, dict(convnext_ref.CONFIGS), dict(_convnextv2_ref.CONFIGS))
+        for v2 in (False, True):                      # the oracle builds the pair itself: nothing is registered with it
+            ref = convnext_ref.ConvNeXtRef(NARROW, 10, v2=v2)
+            assert [st.blocks[0].conv_dw.in_channels for st in ref.stages] == [40, 80, 160, 320] and ref.v2 == v2
+            assert [len(st.blocks) for st in ref.stages] == list(NARROW[0])
+    assert before == (dict(convnext.CONFIGS), convnext.GRN_ARCHS, dict(convnext_ref.CONFIGS))
 
 
 def test_parameter_count_formula():
@@ -66,8 +68,8 @@ def test_parameter_count_formula():
             assert param_count(depths, dims, False) == v1, stem
         if v2 is not None:
             assert param_count(depths, dims, True) == v2, stem
-    for name, n in _convnextv2_ref.PARAM_COUNTS.items():          # the four V2 counts the README already stated
-        assert param_count(*_convnextv2_ref.CONFIGS[name], True) == n, name
+    for name, n in convnext_ref.PARAM_COUNTS.items():             # the four V2 counts the README already stated
+        assert param_count(*convnext_ref.CONFIGS[name], True) == n, name
 
 
 @pytest.mark.parametrize("arch", ["convnext_atto", "convnextv2_atto", "convnext_femto", "convnextv2_femto", "convnext_pico",

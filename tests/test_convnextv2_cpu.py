@@ -1,6 +1,6 @@
 """ConvNeXt V2 without a GPU: parameter counts, timm's names and order, the zero GRN init, state-dict round trips (4-D fc filters
 included), the command-line surface, the library calls of a V2 block in both passes, the V1 layouts untouched, the closed forms of
-tests/_convnextv2_ref.py against fp64 autograd, and the loop counts of csrc/grn.hip at the shapes tests/test_grn_gpu.py runs.
+oracle/convnext_ref.py against fp64 autograd, and the loop counts of csrc/grn.hip at the shapes tests/test_grn_gpu.py runs.
 
 The models construct on the CPU under the replacements of tests/golden/make_arena_layouts.py (install_stubs) and, for the call
 lists, tests/golden/make_call_traces.py (install_recorders)."""
@@ -12,7 +12,8 @@ import sys
 import pytest
 import torch
 
-from _convnextv2_ref import CONFIGS, PARAM_COUNTS, ConvNeXtV2Ref, grn_closed_form, grn_plan, grn_timm
+from _convnext_narrow import grn_plan
+from oracle.convnext_ref import CONFIGS, PARAM_COUNTS, V2_ARCHS, ConvNeXtRef, grn_closed_form, grn_timm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -64,7 +65,7 @@ def test_configs_stay_pairs_and_v1_keeps_its_count(stubs):
     for name, cfg in convnext.CONFIGS.items():
         depths, dims = cfg
         assert len(depths) == len(dims) == 4
-    assert convnext.GRN_ARCHS == set(CONFIGS) and convnext.GRN_ARCHS < set(convnext.CONFIGS)
+    assert convnext.GRN_ARCHS == V2_ARCHS and len(V2_ARCHS) == 5 and convnext.GRN_ARCHS < set(convnext.CONFIGS)
     assert not any(n in convnext.GRN_ARCHS for n in ("convnext_tiny", "convnext_small", "convnext_test", "convnext_pin"))
     # the same count, by the same formula, gives V1 tiny's known figure
     v1 = _build("convnext_tiny", 1000)
@@ -73,7 +74,7 @@ def test_configs_stay_pairs_and_v1_keeps_its_count(stubs):
 
 def test_names_order_and_init(stubs):
     net = _build("convnextv2_test")
-    ref = ConvNeXtV2Ref("convnextv2_test", 10)
+    ref = ConvNeXtRef("convnextv2_test", 10)
     sd = net.state_dict()
     assert list(sd) == list(ref.state_dict())                      # the oracle registers timm's order
     assert {k: tuple(v.shape) for k, v in sd.items()} == {k: tuple(v.shape) for k, v in ref.state_dict().items()}

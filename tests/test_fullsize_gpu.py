@@ -17,21 +17,17 @@ step: size-independent properties of the step instead of element-wise comparison
 import pytest
 import torch
 
+from _parity import xent_backward
+
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 B, HW, C = 256, 224, 1000
 
 
 def _step(net, x, y, smoothing=0.1):
-    from imageclassification_amd import hip
-    lib = hip.load()
     ws = net.pack(x)
-    logits = net.forward_packed(ws)
-    hip.check(lib.icamd_softmax_xent(logits.data_ptr(), net.ncls_p, x.shape[0], C, y.data_ptr(), None, 1.0, smoothing,
-                                     1.0 / x.shape[0], ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(),
-                                     ws["dlogits"].data_ptr(), hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
+    net.forward_packed(ws)
+    xent_backward(net, ws, y, C, smoothing)
     return ws
 
 

@@ -1,4 +1,4 @@
-"""icamd_grn_fwd / icamd_grn_bwd (csrc/grn.hip) against the fp64 closed form of tests/_convnextv2_ref.py, evaluated on the bf16
+"""icamd_grn_fwd / icamd_grn_bwd (csrc/grn.hip) against the fp64 closed form of oracle/convnext_ref.py, evaluated on the bf16
 inputs and rounded to bf16 once, where the kernels round.
 
 Bounds: g, da and dz1 rel-L2 <= 1e-3 (the project's kernel bound; an fp32 and an fp64 evaluation, both rounded, differ by <= 4e-5).
@@ -7,7 +7,8 @@ the same inputs, floor 1e-6 -- the margin is for summation order; a lost row seg
 import pytest
 import torch
 
-from _convnextv2_ref import GRN_EPS, gelu_grad, grn_closed_form, grn_plan
+from _convnext_narrow import grn_plan
+from oracle.convnext_ref import GRN_EPS, gelu_grad, grn_closed_form
 
 pytestmark = pytest.mark.gpu
 

@@ -1,5 +1,5 @@
 """icamd_grn_fwd / icamd_grn_bwd at C = 160 (C % 64 == 32: ConvNeXt V2 atto's first stage, 4 dim = 160) against the fp64 closed form of
-tests/_convnextv2_ref.py, with the bounds of tests/test_grn_gpu.py::test_grn_matches_fp64_closed_form: bf16 outputs rel-L2 <= 1e-3;
+oracle/convnext_ref.py, with the bounds of tests/test_grn_gpu.py::test_grn_matches_fp64_closed_form: bf16 outputs rel-L2 <= 1e-3;
 fp32 statistics at most 10 x the error of a plain fp32 torch evaluation of the same closed form, floor 1e-6; two launches bit-equal.
 
 At C = 160 a row has 20 vectors of 8 channels: a reduction workgroup is 20 vector columns x 12 row lanes with 16 idle threads, and
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from _convnext_narrow import Grn
-from _convnextv2_ref import gelu_grad, grn_closed_form
+from oracle.convnext_ref import gelu_grad, grn_closed_form
 
 pytestmark = pytest.mark.gpu
 

@@ -11,7 +11,7 @@ import torch
 
 import _multitrip as MT
 from _fullsize_check import check_bf16, check_fp32, check_stats
-from _swin_ref import patch_merge_gather, patch_merge_ln_ref, window_attention_ref
+from oracle.swin_ref import patch_merge_gather, patch_merge_ln_ref, window_attention_ref
 from oracle import ops_ref as R
 
 F64 = torch.float64
@@ -123,7 +123,7 @@ def _wa_grad_check(got, ref):
 
 def test_token_window_map_is_the_references(winattn):
     """winattn_token_window against window_partition of the rolled grid (what the reference does)"""
-    from _swin_ref import window_partition
+    from oracle.swin_ref import window_partition
     B, Hs, Ws, H, ws, shift = WA_CASE
     ids = torch.arange(B * Hs * Ws).view(B, Hs, Ws, 1)
     rolled = torch.roll(ids, shifts=(-shift, -shift), dims=(1, 2))

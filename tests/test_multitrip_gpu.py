@@ -8,7 +8,7 @@ Every case first shows that it IS multi-trip, from the library's own workspace /
 planner mirrors of tests/_multitrip.py otherwise (tests/test_multitrip_checks_cpu.py pins those mirrors to the trip counts below),
 so that a change of a cap cannot quietly turn it into a one-trip test.
 
-References are the ones of the kernels' own tests (tests/_swin_ref.py, tests/_se_kernels.py, oracle/ops_ref.py),
+References are the ones of the kernels' own tests (oracle/swin_ref.py, tests/_se_kernels.py, oracle/ops_ref.py),
 accumulated in fp64, on the GPU where the shape is large.  Bounds:
   * window attention: lse 1e-4 / 1e-4; out, dq, dk, dv, dbias global AND per 64 x 64 block under the bounds
     tests/test_fullsize_attention_long_gpu.py applies to icamd_attention_fwd / _bwd (3e-3 forward, 6e-3 backward, the
@@ -35,7 +35,7 @@ import _window_attention as WA
 from _fullsize_check import check_bf16, check_close, check_fp32, check_stats, require, worst_block
 from _harness import INT, UNSUPPORTED, dev, digest, guarded, intact
 from _harness import default_routing_lib as lib  # noqa: F401
-from _swin_ref import patch_merge_gather, patch_merge_ln_ref, window_attention_ref
+from oracle.swin_ref import patch_merge_gather, patch_merge_ln_ref, window_attention_ref
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu

@@ -14,8 +14,8 @@ from oracle import ops_ref as R
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _numeric_ranges as NR  # noqa: E402
-from _convnextv2_ref import grn_closed_form  # noqa: E402
-from _swin_ref import patch_merge_ln_ref  # noqa: E402
+from oracle.convnext_ref import grn_closed_form  # noqa: E402
+from oracle.swin_ref import patch_merge_ln_ref  # noqa: E402
 
 F64 = torch.float64
 

@@ -29,10 +29,10 @@ import torch.nn.functional as F
 import _harness
 import _numeric_ranges as NR
 import _se_kernels as SE
-from _convnextv2_ref import GRN_EPS, gelu_grad, grn_closed_form
+from oracle.convnext_ref import GRN_EPS, gelu_grad, grn_closed_form
 from _harness import dev as dev16
 from _harness import lib, sync  # noqa: F401
-from _swin_ref import patch_merge_ln_ref
+from oracle.swin_ref import patch_merge_ln_ref
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu

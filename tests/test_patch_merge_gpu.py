@@ -1,5 +1,5 @@
 """icamd_patch_merge_ln_fwd / _bwd (csrc/window_attention.hip) through the C ABI: the 2x2 gather into 4C channels (timm's
-x0 | x1 | x2 | x3 order) fused with LayerNorm(4C), against tests/_swin_ref.py patch_merge_ln_ref in fp64.  Bounds are those of
+x0 | x1 | x2 | x3 order) fused with LayerNorm(4C), against oracle/swin_ref.py patch_merge_ln_ref in fp64.  Bounds are those of
 tests/test_kernels_gpu.py test_layernorm_fwd_bwd; outputs carry guard bands as in the long-attention tests."""
 import pytest
 import torch
@@ -7,7 +7,7 @@ import torch
 from _harness import UNSUPPORTED, digest
 from _harness import lib  # noqa: F401
 from _patch_merge import EPS, operands, run
-from _swin_ref import patch_merge_ln_ref
+from oracle.swin_ref import patch_merge_ln_ref
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu

@@ -10,7 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from _swin_ref import SwinRef, relative_position_index as ref_index, shifted_window_mask, window_partition  # noqa: E402
+from oracle.swin_ref import SwinRef, relative_position_index as ref_index, shifted_window_mask, window_partition  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

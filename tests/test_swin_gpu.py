@@ -1,6 +1,6 @@
-"""Swin Transformer on the HIP kernels vs the CPU oracle (tests/_swin_ref.py, same bf16 rounding points), on the pattern of
-tests/test_vit_gpu.py and with its bounds: whole-network tolerances use the oracle's own re-association noise (fp64 vs fp32
-accumulation) as the yardstick."""
+"""Swin Transformer on the HIP kernels vs the CPU oracle (oracle/swin_ref.py, same bf16 rounding points), on the pattern of
+tests/test_vit_gpu.py and with its bounds (tests/_parity.py): whole-network tolerances use the oracle's own re-association noise
+(fp64 vs fp32 accumulation) as the yardstick."""
 import os
 import pickle
 import subprocess
@@ -9,35 +9,17 @@ import sys
 import pytest
 import torch
 
-from _swin_ref import SwinRef
-from _swin_step import ROOT, check
+from _parity import ROOT, check, swin_pair, xent_backward
+from oracle.swin_ref import SwinRef
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def _pair(arch, C, img, seed=0, drop_path_rate=0.0):
-    from imageclassification_amd.swin import SwinTransformer
-    torch.manual_seed(seed)
-    ref = SwinRef(arch, C, img_size=img, bf16_points=True)
-    g = torch.Generator().manual_seed(seed + 1)
-    with torch.no_grad():   # non-trivial biases, LayerNorm affine and bias tables so that every gradient path is exercised
-        for n, p in ref.named_parameters():
-            if n.endswith("relative_position_bias_table"):
-                p.copy_(0.5 * torch.randn(p.shape, generator=g))
-            elif n.endswith("bias"):
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-            elif "norm" in n and n.endswith("weight"):
-                p.copy_(0.5 + torch.rand(p.shape, generator=g))
-    net = SwinTransformer(arch, C, img_size=img, drop_path_rate=drop_path_rate)
-    net.load_state_dict(ref.state_dict())
-    return ref, net
-
-
 @pytest.mark.parametrize("arch,img,B", [("swin_test", 56, 6), ("swin_test", 112, 2), ("swin_tiny_patch4_window7_224", 224, 2)])
 def test_swin_forward_backward_matches_oracle(arch, img, B):
     C = 10
-    ref, net = _pair(arch, C, img)
+    ref, net = swin_pair(arch, C, img)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
@@ -48,7 +30,7 @@ def test_swin_stochastic_depth_with_injected_masks():
     """drop_path_rate 0.5: the same per-sample masks on both sides (a seam on each: `injected_keep` / `_Block.keep`), at least one
     dropped and one kept sample in every branch that has a rate"""
     C, B, img = 10, 6, 56
-    ref, net = _pair("swin_test", C, img, drop_path_rate=0.5)
+    ref, net = swin_pair("swin_test", C, img, drop_path_rate=0.5)
     rates = [blk["rate"] for st in net.stages for blk in st["blocks"]]
     assert rates[0] == 0.0 and abs(rates[-1] - 0.5) < 1e-6 and all(a < b for a, b in zip(rates, rates[1:]))
     g = torch.Generator().manual_seed(11)
@@ -70,10 +52,9 @@ def test_swin_stochastic_depth_with_injected_masks():
 
 
 def test_swin_accumulation_state_and_pickling(tmp_path):
-    from imageclassification_amd import hip
     from imageclassification_amd.checkpoint import DeferredModel
     C, B, img = 10, 4, 56
-    ref, net = _pair("swin_test", C, img)
+    ref, net = swin_pair("swin_test", C, img)
     # state_dict round trip, bit for bit; parameters only
     sd = net.state_dict()
     assert list(sd) == [n for n, _ in ref.named_parameters()]
@@ -84,11 +65,7 @@ def test_swin_accumulation_state_and_pickling(tmp_path):
     net.train()
     ws = net.pack(x.cuda())
     net.forward_packed(ws)
-    hip.check(net.lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, C, y.data_ptr(), None, 1.0, 0.1, 1.0 / B,
-                                         ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(), ws["dlogits"].data_ptr(),
-                                         hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
+    xent_backward(net, ws, y, C, smoothing=0.1)
     once = net.grad_arena.clone()
     net.backward_packed(ws, accumulate=True)
     torch.cuda.synchronize()
@@ -158,7 +135,6 @@ def test_swin_tiny_engine_step_and_evaluate():
 
 def test_swin_default_drop_path_draws_masks_and_stays_finite():
     """the constructor default (0.1): masks are drawn on the host, a training step runs and every gradient is finite"""
-    from imageclassification_amd import hip
     from imageclassification_amd.swin import SwinTransformer
     C, B = 10, 8
     torch.manual_seed(2)
@@ -169,11 +145,7 @@ def test_swin_default_drop_path_draws_masks_and_stays_finite():
     net.train()
     ws = net.pack(x.cuda())
     net.forward_packed(ws)
-    hip.check(net.lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, C, y.data_ptr(), None, 1.0, 0.1, 1.0 / B,
-                                         ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(), ws["dlogits"].data_ptr(),
-                                         hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
+    xent_backward(net, ws, y, C, smoothing=0.1)
     assert ws["keep_dev"].shape == (8, B)
     assert bool(torch.isfinite(net.grad_arena).all()) and float(net.grad_arena.abs().max()) > 0
 

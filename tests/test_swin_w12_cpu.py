@@ -1,5 +1,5 @@
 """The window-12 Swin models (swin_base_patch4_window12_384 and swin_test_w12), the parts that need no GPU: parameter counts, the
-product's shape listing against the tests-side reference, the stage plans, the host-side window geometry and relative-position
+product's shape listing against the oracle (oracle/swin_ref.py), the stage plans, the host-side window geometry and relative-position
 index at 12 x 12 against the way timm builds them, the kernels' host-side queries for ws = 12 and their neighbours, and the
 command-line surface.  Patterned on tests/test_swin_cpu.py."""
 import os
@@ -11,11 +11,12 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import _swin_w12 as W12  # noqa: E402
-from _swin_ref import relative_position_index as ref_index, shifted_window_mask, window_partition  # noqa: E402
+from oracle.swin_ref import CONFIGS as ORACLE_CONFIGS, SwinRef, relative_position_index as ref_index  # noqa: E402
+from oracle.swin_ref import shifted_window_mask, window_partition  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# (classes, input size, parameters): counted from SwinRef with the configurations of tests/_swin_w12.py; timm lists 87.90 M
+# (classes, input size, parameters): counted from SwinRef (oracle/swin_ref.py); timm lists 87.90 M
 COUNTS = {
     "swin_base_patch4_window12_384": (1000, 384, 87903584),
     "swin_test_w12": (10, 96, 139408),
@@ -37,7 +38,7 @@ def test_parameter_counts_and_shapes_equal_the_reference(arch):
     C, img, count = COUNTS[arch]
     shapes = swin.param_shapes(arch, C, img)
     assert sum(_numel(s) for s in shapes.values()) == count
-    ref = W12.swin_ref(arch, C, img)
+    ref = SwinRef(arch, C, img_size=img)
     assert sum(p.numel() for p in ref.parameters()) == count
     assert list(shapes.items()) == [(n, tuple(p.shape)) for n, p in ref.named_parameters()]
     assert list(ref.state_dict()) == list(shapes)                      # parameters only: no index, no mask
@@ -51,7 +52,7 @@ def test_the_tables_stay_apart():
     assert swin.CONFIGS_W12["swin_base_patch4_window12_384"] == (128, (2, 2, 18, 2), (4, 8, 16, 32), 12)
     assert swin.CONFIGS_W12["swin_test_w12"] == (32, (2, 2), (1, 2), 12)
     for arch, cfg in swin.CONFIGS_W12.items():
-        assert W12.CONFIGS[arch] == cfg
+        assert ORACLE_CONFIGS[arch] == cfg
 
 
 def test_stage_plans():

@@ -1,6 +1,6 @@
-"""The window-12 Swin models on the HIP kernels vs the CPU oracle (tests/_swin_ref.py with the configurations of tests/_swin_w12.py,
-same bf16 rounding points), with the construction and the bounds of tests/test_swin_gpu.py: logits <= 2 max(fp64 self-noise, 2e-3),
-loss within 5e-3 relative, every parameter gradient <= 3 max(yardstick, 1e-2).
+"""The window-12 Swin models on the HIP kernels vs the CPU oracle (oracle/swin_ref.py, same bf16 rounding points), with the
+construction and the bounds of tests/test_swin_gpu.py (tests/_parity.py): logits <= 2 max(fp64 self-noise, 2e-3), loss within 5e-3
+relative, every parameter gradient <= 3 max(yardstick, 1e-2).
 
 swin_test_w12 at 96^2 has a shifted window-12 stage (24^2 tokens) and a one-window stage (12^2); at 192^2 both stages are shifted
 window-12 stages (48^2, 24^2).  swin_base_patch4_window12_384 itself, at batch 1: its parameters (loaded from the reference's
@@ -15,8 +15,7 @@ import sys
 import pytest
 import torch
 
-import _swin_w12 as W12
-from _swin_step import ROOT, check
+from _parity import ROOT, check, swin_pair, swin_ref, xent_backward
 
 pytestmark = pytest.mark.gpu
 ARCH = "swin_test_w12"
@@ -25,7 +24,7 @@ ARCH = "swin_test_w12"
 @pytest.mark.parametrize("img,B", [(96, 4), (192, 2)])
 def test_swin_w12_forward_backward_matches_oracle(img, B):
     C = 10
-    ref, net = W12.pair(ARCH, C, img)
+    ref, net = swin_pair(ARCH, C, img)
     assert [(st["res"], st["ws"]) for st in net.stages] == ([(24, 12), (12, 12)] if img == 96 else [(48, 12), (24, 12)])
     assert [blk["shift"] for st in net.stages for blk in st["blocks"]] == ([0, 6, 0, 0] if img == 96 else [0, 6, 0, 6])
     g = torch.Generator().manual_seed(5)
@@ -37,7 +36,7 @@ def test_swin_w12_forward_backward_matches_oracle(img, B):
 def test_swin_w12_stochastic_depth_with_injected_masks():
     """drop_path_rate 0.5 with the same per-sample masks on both sides, as tests/test_swin_gpu.py does for swin_test"""
     C, B, img = 10, 4, 96
-    ref, net = W12.pair(ARCH, C, img, drop_path_rate=0.5)
+    ref, net = swin_pair(ARCH, C, img, drop_path_rate=0.5)
     rates = [blk["rate"] for st in net.stages for blk in st["blocks"]]
     assert rates[0] == 0.0 and abs(rates[-1] - 0.5) < 1e-6 and all(a < b for a, b in zip(rates, rates[1:]))
     g = torch.Generator().manual_seed(11)
@@ -67,7 +66,7 @@ def test_swin_w12_engine_step_and_evaluate():
     from imageclassification_amd.swin import relative_position_index
     from imageclassification_amd.utils import NativeScalerWithGradNormCount
     C, B, img = 10, 4, 96
-    ref, net = W12.pair(ARCH, C, img)
+    ref, net = swin_pair(ARCH, C, img)
     g = torch.Generator().manual_seed(1)
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
@@ -101,7 +100,7 @@ def test_swin_w12_engine_step_and_evaluate():
 def test_swin_w12_state_and_pickling(tmp_path):
     from imageclassification_amd.checkpoint import DeferredModel
     C, img = 10, 96
-    ref, net = W12.pair(ARCH, C, img)
+    ref, net = swin_pair(ARCH, C, img)
     sd = net.state_dict()
     assert list(sd) == [n for n, _ in ref.named_parameters()]                      # parameters only, timm's names and order
     assert all(torch.equal(sd[k], v) for k, v in ref.state_dict().items())
@@ -126,10 +125,9 @@ def test_swin_base_window12_384_loads_and_steps():
     the reference's forward (the bounds of the parity cases), finite and non-zero gradients"""
     import copy
     from oracle import ops_ref as R
-    from imageclassification_amd import hip
     from imageclassification_amd.swin import SwinTransformer
     arch, C = "swin_base_patch4_window12_384", 1000
-    ref = W12.perturbed_ref(arch, C, 384)
+    ref = swin_ref(arch, C, 384)
     net = SwinTransformer(arch, C, drop_path_rate=0.0)                             # no size given: the name's own
     assert net.img_size == 384 and net.plan == [(96, 12, 6), (48, 12, 6), (24, 12, 6), (12, 12, 0)]
     want = ref.state_dict()
@@ -149,11 +147,7 @@ def test_swin_base_window12_384_loads_and_steps():
     net.train()
     ws = net.pack(x.cuda())
     logits = net.forward_packed(ws)
-    hip.check(net.lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, 1, C, y.data_ptr(), None, 1.0, 0.1, 1.0,
-                                         ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(), ws["dlogits"].data_ptr(),
-                                         hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
+    xent_backward(net, ws, y, C, smoothing=0.1)
     got = logits[:, :C].float().cpu()
     assert bool(torch.isfinite(got).all())
     noise, err, loss = R.rel_l2(out64, out), R.rel_l2(got, out), float(ws["loss_rows"].mean())

@@ -1,34 +1,15 @@
-"""ViT on the HIP kernels vs the CPU oracle (oracle/vit_ref.py, same bf16 rounding points).  Whole-network tolerances
-use the oracle's own re-association noise (fp64 vs fp32 accumulation) as the yardstick, as in tests/test_model_gpu.py;
-transformers have no ReLU masks, so the noise is an order of magnitude smaller than for ResNets."""
-import copy
-import ctypes
-
+"""ViT on the HIP kernels vs the CPU oracle (oracle/vit_ref.py, same bf16 rounding points; the step: tests/_parity.py).
+Whole-network tolerances use the oracle's own re-association noise (fp64 vs fp32 accumulation) as the yardstick, as in
+tests/test_model_gpu.py; transformers have no ReLU masks, so the noise is an order of magnitude smaller than for ResNets."""
 import pytest
 import torch
 
+from _parity import assert_within, step, vit_pair, worst
 from oracle import ops_ref as R
 from oracle.vit_ref import ViTRef
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _pair(arch, C, img, seed=0):
-    from imageclassification_amd.vit import VisionTransformer
-    torch.manual_seed(seed)
-    ref = ViTRef(arch, C, img_size=img, bf16_points=True)
-    g = torch.Generator().manual_seed(seed + 1)
-    with torch.no_grad():   # non-trivial biases / LayerNorm affine / cls token so every gradient path is exercised
-        for n, p in ref.named_parameters():
-            if n.endswith("bias"):
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-            elif "norm" in n and n.endswith("weight"):
-                p.copy_(0.5 + torch.rand(p.shape, generator=g))
-        ref.cls_token.copy_(0.02 * torch.randn(ref.cls_token.shape, generator=g))
-    net = VisionTransformer(arch, C, img_size=img)
-    net.load_state_dict(ref.state_dict())
-    return ref, net
 
 
 def test_token_plumbing_kernels():
@@ -59,41 +40,15 @@ def test_token_plumbing_kernels():
                                         # every gradient tensor against the oracle's, not only the loss
                                         ("vit_base_patch16_224", 224, 2)])
 def test_vit_forward_backward_matches_oracle(arch, img, B):
-    from imageclassification_amd import hip
     C = 10
-    ref, net = _pair(arch, C, img)
-    ref64 = copy.deepcopy(ref).double()
+    ref, net = vit_pair(arch, C, img)
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
-    out = ref(x)
-    loss = torch.nn.functional.cross_entropy(out, y, label_smoothing=0.1)
-    loss.backward()
-    out64 = ref64(x.double())
-    torch.nn.functional.cross_entropy(out64, y, label_smoothing=0.1).backward()
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    yd = y.cuda()
-    hip.check(net.lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, C, yd.data_ptr(), None, 1.0, 0.1, 1.0 / B,
-                                         ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(), ws["dlogits"].data_ptr(),
-                                         hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
-    got = logits[:, :C].float().cpu()
-    noise = R.rel_l2(out64.detach().float(), out.detach())
-    err = R.rel_l2(got, out.detach())
-    assert err <= 2.0 * max(noise, 2e-3), (err, noise)
-    assert abs(float(ws["loss_rows"].mean()) - float(loss)) <= 5e-3 * float(loss)
-    p64 = dict(ref64.named_parameters())
-    worst = ("", 0.0)
-    for name, p in ref.named_parameters():
-        e = R.rel_l2(net.grad_of(name), p.grad)
-        n = R.rel_l2(p64[name].grad.float(), p.grad)
-        if e > worst[1]:
-            worst = (name, e)
-        assert e <= 3.0 * max(n, 1e-2), (name, e, n)
-    print(f"{arch} img{img}: logits err {err:.2e} (self-noise {noise:.2e}); worst grad err {worst[1]:.2e} at {worst[0]}")
+    s = step(ref, net, x, y, C)
+    w = worst(s.rows)
+    print(f"{arch} img{img}: logits err {s.err:.2e} (self-noise {s.noise:.2e}); worst grad err {w[1]:.2e} at {w[0]}")
+    assert_within(s)
 
 
 def test_vit_base_parameter_layout_and_engine_step():

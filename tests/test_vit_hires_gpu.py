@@ -1,7 +1,6 @@
 """ViT above 224^2 (T > 208 tokens: the tiled attention route of csrc/attention_long.hip) against the CPU oracle: whole-model
 forward / backward parity, one engine step, and the command line with the `_384` model names.  Tolerances are those of
-tests/test_vit_gpu.py (the oracle's own fp64-vs-fp32 re-association noise as the yardstick); its helper is restated here."""
-import copy
+tests/test_vit_gpu.py (the oracle's own fp64-vs-fp32 re-association noise as the yardstick)."""
 import os
 import subprocess
 import sys
@@ -9,75 +8,27 @@ import sys
 import pytest
 import torch
 
-from oracle import ops_ref as R
+from _parity import ROOT, assert_within, step, vit_pair, worst
 from oracle.vit_ref import ViTRef
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-# our name -> the oracle's name of the same architecture (the oracle builds any size through img_size=)
-ORACLE_ARCH = {"vit_tiny_test": "vit_tiny_test", "vit_base_patch16_384": "vit_base_patch16_224",
-               "vit_small_patch16_384": "vit_small_patch16_224"}
-
-
-def _pair(arch, C, img, seed=0):
-    from imageclassification_amd.vit import VisionTransformer
-    torch.manual_seed(seed)
-    ref = ViTRef(ORACLE_ARCH[arch], C, img_size=img, bf16_points=True)
-    g = torch.Generator().manual_seed(seed + 1)
-    with torch.no_grad():   # non-trivial biases / LayerNorm affine / cls token so every gradient path is exercised
-        for n, p in ref.named_parameters():
-            if n.endswith("bias"):
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-            elif "norm" in n and n.endswith("weight"):
-                p.copy_(0.5 + torch.rand(p.shape, generator=g))
-        ref.cls_token.copy_(0.02 * torch.randn(ref.cls_token.shape, generator=g))
-    net = VisionTransformer(arch, C, img_size=img)
-    net.load_state_dict(ref.state_dict())
-    return ref, net
 
 
 @pytest.mark.parametrize("arch,img,B", [("vit_tiny_test", 256, 3),            # T = 257
                                         ("vit_tiny_test", 384, 2),            # T = 577
                                         ("vit_base_patch16_384", 384, 2)])    # ViT-B/16 at its true width and depth, T = 577
 def test_vit_hires_forward_backward_matches_oracle(arch, img, B):
-    from imageclassification_amd import hip
     C = 10
-    ref, net = _pair(arch, C, img)
+    ref, net = vit_pair(arch, C, img)
     assert net.T == (img // 16) ** 2 + 1 and net.T > 208
-    ref64 = copy.deepcopy(ref).double()
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, 3, img, img, generator=g)
     y = torch.randint(0, C, (B,), generator=g)
-    out = ref(x)
-    loss = torch.nn.functional.cross_entropy(out, y, label_smoothing=0.1)
-    loss.backward()
-    out64 = ref64(x.double())
-    torch.nn.functional.cross_entropy(out64, y, label_smoothing=0.1).backward()
-    net.train()
-    ws = net.pack(x.cuda())
-    logits = net.forward_packed(ws)
-    yd = y.cuda()
-    hip.check(net.lib.icamd_softmax_xent(ws["logits"].data_ptr(), net.ncls_p, B, C, yd.data_ptr(), None, 1.0, 0.1, 1.0 / B,
-                                         ws["loss_rows"].data_ptr(), ws["pred"].data_ptr(), ws["dlogits"].data_ptr(),
-                                         hip.stream_ptr()), "xent")
-    net.backward_packed(ws)
-    torch.cuda.synchronize()
-    got = logits[:, :C].float().cpu()
-    noise = R.rel_l2(out64.detach().float(), out.detach())
-    err = R.rel_l2(got, out.detach())
-    print(f"{arch} img{img}: logits err {err:.2e} (self-noise {noise:.2e})")
-    assert err <= 2.0 * max(noise, 2e-3), (err, noise)
-    assert abs(float(ws["loss_rows"].mean()) - float(loss)) <= 5e-3 * float(loss)
-    p64 = dict(ref64.named_parameters())
-    worst = ("", 0.0)
-    for name, p in ref.named_parameters():
-        e = R.rel_l2(net.grad_of(name), p.grad)
-        n = R.rel_l2(p64[name].grad.float(), p.grad)
-        if e > worst[1]:
-            worst = (name, e)
-        assert e <= 3.0 * max(n, 1e-2), (name, e, n)
-    print(f"    worst grad err {worst[1]:.2e} at {worst[0]}")
+    s = step(ref, net, x, y, C)
+    w = worst(s.rows)
+    print(f"{arch} img{img}: logits err {s.err:.2e} (self-noise {s.noise:.2e})")
+    print(f"    worst grad err {w[1]:.2e} at {w[0]}")
+    assert_within(s)
 
 
 def test_vit_small_384_engine_step():
@@ -90,7 +41,7 @@ def test_vit_small_384_engine_step():
     from imageclassification_amd.vit import VisionTransformer
     C, B = 1000, 4
     torch.manual_seed(0)
-    ref = ViTRef("vit_small_patch16_224", C, img_size=384, bf16_points=True)
+    ref = ViTRef("vit_small_patch16_384", C, img_size=384, bf16_points=True)
     net = VisionTransformer("vit_small_patch16_384", C)      # no img_size: the name carries it
     assert net.img_size == 384 and net.T == 577
     net.load_state_dict(ref.state_dict())

@@ -1,6 +1,6 @@
 """icamd_window_attention_fwd / _bwd and the relative-position gather / scatter (csrc/window_attention.hip), through the C ABI.
 
-The reference (tests/_swin_ref.py window_attention_ref) does what timm does -- torch.roll, window_partition, the img_mask built by
+The reference (oracle/swin_ref.py window_attention_ref) does what timm does -- torch.roll, window_partition, the img_mask built by
 slices, window_reverse, roll back -- in fp64 with P and dS unrounded.  Bounds are those tests/test_attention_long_gpu.py applies to
 icamd_attention_fwd / _bwd against the same kind of oracle: the rounding points are the same (P and dS rounded to bf16 once as MFMA
 operands, fp32 accumulation, one final rounding).  dbias is taken in fp32 before that rounding and is held to the bound of the
@@ -14,7 +14,7 @@ import torch
 
 from _harness import UNSUPPORTED, digest, guarded, hip, intact, rnd_bf16
 from _harness import lib  # noqa: F401
-from _swin_ref import relative_position_index
+from oracle.swin_ref import relative_position_index
 from _window_attention import CASES, check_case, operands, run
 from oracle import ops_ref as R
 

@@ -2,7 +2,7 @@
 through the C ABI.
 
 Reference, operands, guard bands, NaN-filled outputs and the parity check are those of tests/_window_attention.py (fp64
-window_attention_ref of tests/_swin_ref.py, P and dS unrounded), shared with tests/test_window_attention_gpu.py, and so are the bounds: lse allclose(1e-4, 1e-4), out rel-L2 <= 3e-3,
+window_attention_ref of oracle/swin_ref.py, P and dS unrounded), shared with tests/test_window_attention_gpu.py, and so are the bounds: lse allclose(1e-4, 1e-4), out rel-L2 <= 3e-3,
 dq / dk / dv / dbias rel-L2 <= 6e-3 -- the rounding points of the T = 144 kernels are the same (P and dS rounded to bf16 once as MFMA
 operands, fp32 accumulation, one final rounding; dbias from the fp32 dS).  The multi-trip case adds the per 64 x 64 block checks of
 tests/test_multitrip_gpu.py, which catch a trip that writes the right values to the wrong window."""
@@ -14,7 +14,7 @@ import _window_attention as WA
 from _fullsize_check import check_bf16, check_close, check_fp32, require, worst_block
 from _harness import UNSUPPORTED, digest, guarded, hip, intact, rnd_bf16
 from _harness import lib  # noqa: F401
-from _swin_ref import relative_position_index, window_attention_ref
+from oracle.swin_ref import relative_position_index, window_attention_ref
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
