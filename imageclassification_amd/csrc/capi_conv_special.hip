@@ -1,5 +1,5 @@
 // C-ABI entry points of the special-purpose convolutions: grouped 3x3, the thin 3x3 and 2x2 average pool of ResNet-D, the 7x7
-// stem, the two fused bottleneck entries, BatchNorm folding into filters and the filter transposes.
+// stem, the two fused bottleneck entries, BatchNorm folding into filters, the filter transposes and the depthwise 3x3 of MobileNetV2.
 #include "capi_common.h"
 
 extern "C" {
@@ -359,6 +359,53 @@ int icamd_filter_transpose_tiled(const void* src_base, void* dst_base, const int
   if (src_base == nullptr || dst_base == nullptr || descs == nullptr || jobs == nullptr || njobs < 0) return ICAMD_ERR_BAD_ARG;
   return icamd_filter_transpose_tiled_launch((const bf16_t*)src_base, (bf16_t*)dst_base, (const long long*)descs, jobs, njobs,
                                              (hipStream_t)stream);
+}
+
+// ---- depthwise 3x3, pad 1, stride 1 / 2 (dwconv3x3.hip).  Arguments are validated before any profiling work is booked.
+int icamd_dwconv3_supported(int N, int H, int W, int C, int stride) { return icamd_dwconv3_ok(N, H, W, C, stride) ? 1 : 0; }
+
+int icamd_dwconv3_stats_rows(int N, int H, int W, int C, int stride) { return (int)icamd_dwconv3_stats_rows_cxx(N, H, W, C, stride); }
+
+static double dw3_out_elements(int N, int H, int W, int C, int stride) {
+  return (double)N * ((H - 1) / stride + 1) * ((W - 1) / stride + 1) * C;
+}
+
+int icamd_dwconv3_fwd(const void* x, const float* in_scale, const float* in_shift, const void* w, void* y, float* stats, int N, int H,
+                      int W, int C, int stride, void* stream) {
+  if (x == nullptr || w == nullptr || y == nullptr || (in_scale == nullptr) != (in_shift == nullptr)) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_dwconv3_ok(N, H, W, C, stride)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_DWCONV, stream);
+  const double out = dw3_out_elements(N, H, W, C, stride);
+  _prof.work(2.0 * N * H * W * C + 2.0 * out + (stats ? 8.0 * icamd_dwconv3_stats_rows_cxx(N, H, W, C, stride) * C : 0.0), 18.0 * out);
+  return icamd_dwconv3_fwd_launch((const bf16_t*)x, in_scale, in_shift, (const bf16_t*)w, (bf16_t*)y, stats, N, H, W, C, stride, 0,
+                                  (hipStream_t)stream);
+}
+
+int icamd_dwconv3_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int stride, void* stream) {
+  if (dy == nullptr || w == nullptr || dx == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_dwconv3_ok(N, H, W, C, stride)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_DWCONV, stream);
+  const double out = dw3_out_elements(N, H, W, C, stride);
+  _prof.work(2.0 * N * H * W * C + 2.0 * out, 18.0 * out);
+  return icamd_dwconv3_dgrad_launch((const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx, N, H, W, C, stride, (hipStream_t)stream);
+}
+
+size_t icamd_dwconv3_wgrad_workspace_bytes(int N, int H, int W, int C, int stride) {
+  return (size_t)icamd_dwconv3_wgrad_rows(N, H, W, C, stride) * 9 * C * sizeof(float);   // one region: [rows][9][C]
+}
+
+int icamd_dwconv3_wgrad(const void* x, const float* in_scale, const float* in_shift, const void* dy, float* dw, int accumulate,
+                        void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int stride, void* stream) {
+  if (x == nullptr || dy == nullptr || dw == nullptr || workspace == nullptr || (in_scale == nullptr) != (in_shift == nullptr))
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_dwconv3_ok(N, H, W, C, stride)) return ICAMD_ERR_UNSUPPORTED;
+  const size_t need = icamd_dwconv3_wgrad_workspace_bytes(N, H, W, C, stride);
+  if (need == 0 || workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_DWCONV, stream);
+  const double out = dw3_out_elements(N, H, W, C, stride);
+  _prof.work(2.0 * N * H * W * C + 2.0 * out + 2.0 * need, 18.0 * out);
+  return icamd_dwconv3_wgrad_launch((const bf16_t*)x, in_scale, in_shift, (const bf16_t*)dy, (float*)workspace, dw, N, H, W, C, stride,
+                                    accumulate, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-// C-ABI entry points of BatchNorm (finalize / apply / backward), the squeeze-and-excitation tail and max / average pooling.
+// C-ABI entry points of BatchNorm (finalize / apply / backward, the ReLU6 pair), the squeeze-and-excitation tail and max / average
+// pooling.
 #include "capi_common.h"
 
 extern "C" {
@@ -219,6 +220,33 @@ int icamd_bn_bwd_from_gy_partials(const float* partials, int nrows, const void* 
     return ICAMD_ERR_BAD_ARG;
   return bn_bwd_from_partials_impl(partials, nrows, g, y, mean, invstd, scale, dgamma, dbeta, dy, rows, C, accumulate, workspace,
                                    workspace_bytes, stream, 1);
+}
+
+// ---- BatchNorm + ReLU6 (dwconv3x3.hip) ----
+int icamd_bn_apply_relu6(const void* y, const float* scale, const float* shift, void* out, long long numel, int C, void* stream) {
+  if (y == nullptr || scale == nullptr || shift == nullptr || out == nullptr || numel <= 0 || C <= 0 || C % 8 != 0 || numel % C != 0)
+    return ICAMD_ERR_BAD_ARG;
+  ProfScope _prof(PC_BN_APPLY, stream);
+  _prof.work((double)numel * 4);
+  return icamd_bn_apply_relu6_launch((const bf16_t*)y, scale, shift, (bf16_t*)out, numel, C, (hipStream_t)stream);
+}
+
+// the workspace of icamd_bn_bwd: the same reduce pass geometry, the same finalize kernel
+size_t icamd_bn_bwd_relu6_workspace_bytes(long long rows, int C) { return icamd_bn_bwd_workspace_bytes(rows, C); }
+
+int icamd_bn_bwd_relu6(const void* dout, const void* y, const float* mean, const float* invstd, const float* scale, const float* shift,
+                       float* dgamma, float* dbeta, void* dy, long long rows, int C, int accumulate, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  if (dout == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || scale == nullptr || shift == nullptr ||
+      dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || rows <= 0 || C <= 0 || C % 8 != 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (workspace_bytes < icamd_bn_bwd_relu6_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
+  if (C > 4096) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)rows * C * (2 * 4 + 2));
+  const ReduceWs w = reduce_ws(workspace, C, bn_bwd_blocks(rows, C), 2);
+  return icamd_bn_bwd_relu6_launch((const bf16_t*)dout, (const bf16_t*)y, mean, invstd, scale, shift, dgamma, dbeta, (bf16_t*)dy, rows,
+                                   C, accumulate, w.part, w.chunks, w.scratch, (hipStream_t)stream);
 }
 
 int icamd_maxpool3x3s2_fwd(const void* x, void* out, uint8_t* argmax, int N, int IH, int IW, int C, void* stream) {

@@ -419,6 +419,21 @@ int icamd_layerscale_param_grads_launch(const float* G, const float* w, const fl
 int icamd_layerscale_bwd_launch(const bf16_t* dout, const bf16_t* z, const float* gamma, const float* keep, bf16_t* dz,
                                 float* part, long long rows, int C, long long rows_per_image, hipStream_t s);
 
+// MobileNet class: depthwise 3x3 (pad 1, stride 1 / 2) and BatchNorm + ReLU6 (dwconv3x3.hip)
+bool icamd_dwconv3_ok(int N, int H, int W, int C, int stride);   // C % 8 == 0, stride 1 or 2, grids below 2^31 workgroups
+long long icamd_dwconv3_stats_rows_cxx(int N, int H, int W, int C, int stride);
+long long icamd_dwconv3_wgrad_rows(int N, int H, int W, int C, int stride);
+int icamd_dwconv3_fwd_launch(const bf16_t* x, const float* in_scale, const float* in_shift, const bf16_t* w, bf16_t* y, float* stats,
+                             int N, int H, int W, int C, int stride, int flip, hipStream_t s);
+int icamd_dwconv3_dgrad_launch(const bf16_t* dy, const bf16_t* w, bf16_t* dx, int N, int H, int W, int C, int stride, hipStream_t s);
+int icamd_dwconv3_wgrad_launch(const bf16_t* x, const float* in_scale, const float* in_shift, const bf16_t* dy, float* part, float* dw,
+                               int N, int H, int W, int C, int stride, int accumulate, hipStream_t s);
+int icamd_bn_apply_relu6_launch(const bf16_t* y, const float* scale, const float* shift, bf16_t* out, long long numel, int C,
+                                hipStream_t s);
+int icamd_bn_bwd_relu6_launch(const bf16_t* dout, const bf16_t* y, const float* mean, const float* invstd, const float* scale,
+                              const float* shift, float* dgamma, float* dbeta, bf16_t* dy, long long rows, int C, int accumulate,
+                              float* part, double* chunks, float* c1c2, hipStream_t s);
+
 // ConvNeXt V2: global response normalisation (grn.hip)
 bool icamd_grn_ok(int N, long long HW, int C);
 void icamd_grn_plan(int N, int HW, int C, int* S, int* rps, int* B, int* rpb);

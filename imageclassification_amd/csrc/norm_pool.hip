@@ -351,6 +351,8 @@ __device__ __forceinline__ u32x4 bn_bwd_dy8(const float (&g)[8], const float (&y
 }
 
 // ------------------------------------------------------------------------------------------------
+// (The two passes below have twins behind a ReLU6 mask, bn_bwd_relu6_reduce_kernel / bn_bwd_relu6_apply_kernel in dwconv3x3.hip: kept
+// apart so that these instantiations and their bits stay as they are.  A change to the sums or to the dy expression goes there too.)
 // BN backward, pass 1: per-channel partial sums of g and g*xhat, g = dout * [act > 0]
 //   act == nullptr && relu : mask recomputed from y*scale+shift > 0 (no residual in front of the ReLU)
 // rows are pixels; block handles `rows_per_block` rows; part[blk][2][C]

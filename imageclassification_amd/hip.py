@@ -212,6 +212,17 @@ _SIGNATURES_ADDED = {
     "icamd_grn_workspace_bytes": (c_size_t, [c_int, c_longlong, c_int]),
     "icamd_grn_fwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_longlong, c_int, c_float, _P, c_size_t, _P]),
     "icamd_grn_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_longlong, c_int, c_float, _P, c_size_t, _P]),
+    # MobileNet class (csrc/dwconv3x3.hip): depthwise 3x3 pad 1 stride 1 / 2 over NHWC bf16 (C % 8 == 0), optionally forming
+    # relu6(x * scale + shift) on load; BatchNorm + ReLU6 apply and backward
+    "icamd_dwconv3_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_dwconv3_stats_rows": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_dwconv3_fwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "icamd_dwconv3_dgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "icamd_dwconv3_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_dwconv3_wgrad": (c_int, [_P, _P, _P, _P, _P, c_int, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, _P]),
+    "icamd_bn_apply_relu6": (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P]),
+    "icamd_bn_bwd_relu6_workspace_bytes": (c_size_t, [c_longlong, c_int]),
+    "icamd_bn_bwd_relu6": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_longlong, c_int, c_int, _P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_ADDED)

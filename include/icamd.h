@@ -336,6 +336,37 @@ int icamd_grn_bwd(const void* dg, const void* a, const float* gx, const float* g
                   float* dbeta, int accumulate, int N, long long rows_per_image, int C, float eps, void* workspace,
                   size_t workspace_bytes, void* stream);
 
+/* MobileNet class (csrc/dwconv3x3.hip): depthwise 3x3 convolution, pad 1, stride 1 or 2, and BatchNorm + ReLU6.
+ *   x NHWC bf16 [N,H,W,C], y / dy [N,OH,OW,C] with OH = (H - 1) / stride + 1 (= ceil(H / stride)), w bf16 [3][3][C] (tap-major shadow
+ *   of the [C,1,3,3] parameter), fp32 accumulation, every stored tensor rounded to bf16 once, no atomics (the same bits on every launch).
+ * _supported: C % 8 == 0, stride 1 or 2, any H, W >= 1.  All addressing is 64-bit, so tensors of 4 GB and more are served; a shape
+ *   whose launch grid would pass 2^31 workgroups is refused.  Elsewhere every entry returns ICAMD_ERR_UNSUPPORTED before anything is
+ *   written and _supported, _stats_rows and _workspace_bytes return 0.
+ * in_scale == NULL (then in_shift == NULL too): x is the input.  Otherwise x is the RAW output of the preceding convolution and the
+ *   kernel forms a = bf16(min(max(x * in_scale[c] + in_shift[c], 0), 6)) on load: bit for bit what icamd_bn_apply_relu6 would have
+ *   stored, so the activated tensor is never written or read.  The zero padding is zero in the activated domain.
+ * fwd: stats (optional) fp32 [_stats_rows][2][C], partial sums of the rounded y and of its square, every row written: the partial
+ *   rows icamd_bn_train_finalize consumes.
+ * dgrad: dx [N,H,W,C] = the gradient of the (activated) depthwise input; every element written exactly once, in one launch.
+ * wgrad: dw fp32 [3][3][C] (+)= sum over pixels dy * shifted a, with a formed on load as in fwd. */
+int icamd_dwconv3_supported(int N, int H, int W, int C, int stride);
+int icamd_dwconv3_stats_rows(int N, int H, int W, int C, int stride);
+int icamd_dwconv3_fwd(const void* x, const float* in_scale, const float* in_shift, const void* w, void* y, float* stats, int N, int H,
+                      int W, int C, int stride, void* stream);
+int icamd_dwconv3_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int stride, void* stream);
+size_t icamd_dwconv3_wgrad_workspace_bytes(int N, int H, int W, int C, int stride);
+int icamd_dwconv3_wgrad(const void* x, const float* in_scale, const float* in_shift, const void* dy, float* dw, int accumulate,
+                        void* workspace, size_t workspace_bytes, int N, int H, int W, int C, int stride, void* stream);
+/* out = bf16(min(max(y * scale[c] + shift[c], 0), 6))  (C % 8 == 0, numel % C == 0).
+ * bwd: the BatchNorm backward behind a ReLU6, with the mask recomputed as 0 < y * scale + shift < 6 (both strict, the forward's own
+ * fp32 expression): no mask bits and no stored activation.  dgamma / dbeta fp32 [C], (+)= under `accumulate`; workspace as
+ * icamd_bn_bwd's (zero-filled once, C <= 4096). */
+int icamd_bn_apply_relu6(const void* y, const float* scale, const float* shift, void* out, long long numel, int C, void* stream);
+size_t icamd_bn_bwd_relu6_workspace_bytes(long long rows, int C);
+int icamd_bn_bwd_relu6(const void* dout, const void* y, const float* mean, const float* invstd, const float* scale, const float* shift,
+                       float* dgamma, float* dbeta, void* dy, long long rows, int C, int accumulate, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ViT token plumbing: tokens[b][0] = cls + pos[0], tokens[b][1+i] = patches[b][i] + pos[1+i] (bf16 out, fp32 parameters);
  * batch_sum: out[j] (+)= sum_b x[b*stride + j] (cls_token / pos_embed gradients); strided row copies; zero fill. */
 int icamd_vit_tokens_fwd(const void* patches, const float* cls_token, const float* pos_embed, void* tokens, int B, int T, int C,

@@ -28,6 +28,7 @@ from imageclassification_amd.vit import CONFIGS as VIT_CONFIGS, NATIVE_SIZE as V
 from imageclassification_amd.convnext import CONFIGS as CNX_CONFIGS, ConvNeXt
 from imageclassification_amd.swin import (CONFIGS as SWIN_CONFIGS, CONFIGS_W12 as SWIN_CONFIGS_W12, NATIVE_SIZE as SWIN_NATIVE_SIZE,
                                           SwinTransformer)
+from imageclassification_amd.mobilenet import CONFIGS as MBV2_CONFIGS, MobileNetV2
 from imageclassification_amd.optim_factory import create_optimizer
 from imageclassification_amd.utils import NativeScalerWithGradNormCount as NativeScaler
 
@@ -100,7 +101,10 @@ def create_model(name, num_classes, input_size=None, drop_path=0.0):
         # the reference passes --drop_path to convnext* / efficientvit* only (train.py:189-192): Swin keeps its own default (timm: 0.1)
         # a size the windows do not tile (384 for 7x7, 224 for 12x12) is the constructor's ValueError, raised before any device work
         return SwinTransformer(name, num_classes, img_size=input_size)
-    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS) + sorted(SWIN_CONFIGS_W12)})")
+    if name in MBV2_CONFIGS:
+        # no stochastic depth in the family: the reference passes --drop_path to convnext* / efficientvit* only (train.py:189-192)
+        return MobileNetV2(name, num_classes)
+    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS) + sorted(SWIN_CONFIGS_W12) + sorted(MBV2_CONFIGS)})")
 
 
 def main(args):
