@@ -317,10 +317,11 @@ def canonical(trace, held, x):
     return out
 
 
-def run_case(case_id, setenv=None, dump=None, setattr_fn=None):
+def run_case(case_id, setenv=None, dump=None, setattr_fn=None, observer=None):
     """-> {"sha256", "calls", "stream_queries"} of one case, under install_recorders; dump: a file for the records, one per line.
     setenv(name, value or None) changes the environment and setattr_fn(module, switch, value) a switch of the case's module (a test passes
-    functions that undo themselves); by default os.environ and setattr, restored at the end."""
+    functions that undo themselves); by default os.environ and setattr, restored at the end.  observer(model, held, x) is called once
+    every phase has run, with the model, the buffers TRACE's pointers lie in and the image batch (tests/_stream_order.py)."""
     from imageclassification_amd import hip
     case = CASES[case_id]
     saved = {k: os.environ.get(k) for k in case.env}
@@ -373,6 +374,8 @@ def run_case(case_id, setenv=None, dump=None, setattr_fn=None):
         if MODELS[case.model][0] == "nets":
             phase("eval_forward_again", lambda: model.forward_packed(ws, logits_only=True))
         phase("reload", lambda: model.load_state_dict(model.state_dict()))
+        if observer is not None:
+            observer(model, held, x)
         rows = canonical(TRACE, held, x)
     finally:
         hip.load().answers = None
