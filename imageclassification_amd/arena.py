@@ -14,7 +14,8 @@ bench.py address parameters by these offsets and names, so the layout rules live
 A model derives from ArenaModel, describes its parameters to a Layout, calls `_allocate`, and supplies `_ctor_kwargs`,
 `init_weights`, `pack`, `forward_packed` and `backward_packed`; what differs between models goes into overrides (`refresh_transposed`
 for work around the transposes, `_buffer_keys` / `_load_buffers` / `state_dict` for buffers, `train` for mode-dependent state).
-`Lin` and `ArenaModel._draw_keep` are kept here; the steps and the transformer block the token models share are blocks.py's.
+`Lin` and `ArenaModel._draw_keep` are kept here; the steps and the transformer block the token models share are blocks.py's, what
+the BatchNorm families share is bnmodel.py's.
 """
 from collections import OrderedDict
 

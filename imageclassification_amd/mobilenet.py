@@ -24,11 +24,8 @@ from types import SimpleNamespace
 import torch
 
 from . import hip
-from .arena import ArenaModel, Layout, align
-from .nets import _BN, _Conv
+from .bnmodel import _BN, _Conv, BatchNormModel
 
-BN_EPS = 1e-5
-BN_MOMENTUM = 0.1
 # Does a depthwise layer form relu6(bn(y)) on load ("fwd": icamd_dwconv3_fwd, "wgrad": icamd_dwconv3_wgrad), or read a tensor that
 # icamd_bn_apply_relu6 wrote first (into ONE scratch buffer of the model: it is recomputed for the weight gradient, so the expanded
 # activation is not stored per block either way)?  A module constant per operation, not an environment variable; both routes give
@@ -92,7 +89,7 @@ class _DW:
         self.w = None
 
 
-class MobileNetV2(ArenaModel):
+class MobileNetV2(BatchNormModel):
     """HIP MobileNetV2. `model(x)` runs the forward and returns bf16 logits [B, num_classes] (a view)."""
 
     def __init__(self, arch="mobilenetv2_100", num_classes=1000, device="cuda", seed=None):
@@ -141,34 +138,15 @@ class MobileNetV2(ArenaModel):
         self.head_bn = bn("bn2", head)
         self.feat_dim = head
         self.fc = conv("classifier", head, self.num_classes, cout_p=self.ncls_p, bias=True)
-        self.max_c = max(b.c for b in self.bns)
-
-        layout = Layout()
-        add = layout.add
-        boff = soff = 0
-        for m in order:
-            if m is self.fc:      # nn.Linear: a 2-D weight in the state_dict, the 1x1 filter [ncls_p][1][1][feat] in the arena
-                m.w = add("classifier.weight", (m.cout, m.cin), "lin", (m.cout_p, 1, 1, m.cin_p))
-                m.b = add("classifier.bias", (m.cout,), "vec", (m.cout_p,))
-            elif isinstance(m, _Conv):
-                m.w = add(m.name + ".weight", (m.cout, m.cin, m.k, m.k), "conv", (m.cout_p, m.k, m.k, m.cin_p))
-            elif isinstance(m, _DW):
-                m.w = add(m.name + ".weight", (m.c, 1, 3, 3), "dw", (3, 3, m.c))
-            else:
-                m.weight = add(m.name + ".weight", (m.c,), "vec", (m.c,))
-                m.bias = add(m.name + ".bias", (m.c,), "vec", (m.c,))
-                m.buf_offset = boff          # running_mean, then running_var
-                boff = align(boff + 2 * m.c, 64)
-                m.stat_offset = soff         # mean, invstd, scale, shift of the last training forward
-                soff = align(soff + 4 * m.c, 64)
+        self.bn_width = max(b.c for b in self.bns)
         # transposed filters for the data gradients of every pointwise convolution and the classifier (the stem needs none)
-        self._allocate(layout, [(m, m.cout_p, 1, m.cin_p) for m in self.convs if m is not self.stem_conv], buffer_elems=boff)
-        self.stat_arena = torch.zeros(max(soff, 64), dtype=torch.float32, device=self.device)
+        self._layout_arenas(order, [(m, m.cout_p, 1, m.cin_p) for m in self.convs if m is not self.stem_conv])
 
-    # ------------------------------------------------------------------ parameters / state_dict
-    def _ctor_kwargs(self):
-        return {"arch": self.arch, "num_classes": self.num_classes}
+    def _add_record(self, add, m):
+        """The one kind of record of its own: a depthwise filter, tap-major in the arena."""
+        m.w = add(m.name + ".weight", (m.c, 1, 3, 3), "dw", (3, 3, m.c))
 
+    # ------------------------------------------------------------------ parameters
     def init_weights(self, seed=None):
         """timm's _init_weight_goog: convolutions N(0, sqrt(2 / fan_out)) with fan_out = k k Cout / groups, BatchNorm 1 / 0,
         classifier weight U(+-1 / sqrt(num_classes)) and bias 0."""
@@ -187,40 +165,8 @@ class MobileNetV2(ArenaModel):
                 sd[name] = torch.ones(p.torch_shape)
             else:
                 sd[name] = torch.zeros(p.torch_shape)
-        for b in self.bns:
-            sd[b.name + ".running_mean"] = torch.zeros(b.c)
-            sd[b.name + ".running_var"] = torch.ones(b.c)
-            sd[b.name + ".num_batches_tracked"] = torch.tensor(0)
+        self._fresh_buffers(sd)
         self.load_state_dict(sd)
-
-    def _buffer_keys(self):
-        return [f"{b.name}.{key}" for b in self.bns for key in ("running_mean", "running_var")]
-
-    def _load_buffers(self, sd):
-        bufs = self.buffer_arena.cpu()
-        for b in self.bns:
-            for j, key in enumerate(("running_mean", "running_var")):
-                k = f"{b.name}.{key}"
-                if k in sd:
-                    bufs[b.buf_offset + j * b.c: b.buf_offset + (j + 1) * b.c] = sd[k].detach().float().cpu()
-        self.buffer_arena.copy_(bufs)
-        k = f"{self.bns[0].name}.num_batches_tracked"
-        if k in sd:
-            self.num_batches_tracked = int(sd[k])
-
-    def state_dict(self):
-        """Parameters in module order, each BatchNorm's buffers right after its bias (torch's key order)."""
-        bufs = self.buffer_arena.cpu()
-        bn_of_bias = {b.name + ".bias": b for b in self.bns}
-        sd = OrderedDict()
-        for name, t in super().state_dict().items():
-            sd[name] = t
-            b = bn_of_bias.get(name)
-            if b is not None:
-                sd[b.name + ".running_mean"] = bufs[b.buf_offset:b.buf_offset + b.c].clone()
-                sd[b.name + ".running_var"] = bufs[b.buf_offset + b.c:b.buf_offset + 2 * b.c].clone()
-                sd[b.name + ".num_batches_tracked"] = torch.tensor(self.num_batches_tracked)
-        return sd
 
     # ------------------------------------------------------------------ workspaces
     def _workspace(self, N, H, W):
@@ -275,12 +221,11 @@ class MobileNetV2(ArenaModel):
         dfc = self.fc.desc(N, 1, 1)
         sizes.wgrad = max(sizes.wgrad, lib.icamd_conv2d_wgrad_workspace_bytes(ctypes.byref(dfc)))
         ws["stats"] = torch.empty(max(sizes.stats, 64), dtype=torch.float32, device=dev)
-        ws["bn_ws"] = torch.zeros(lib.icamd_bn_workspace_bytes(self.max_c), dtype=torch.uint8, device=dev)   # counters start at zero
+        self._bn_workspaces(ws)
         ws["wgrad_ws"] = torch.empty(sizes.wgrad, dtype=torch.uint8, device=dev)
         ws["wgrad_ws_bytes"] = sizes.wgrad
         ws["bnb_ws"] = torch.zeros(sizes.bnb, dtype=torch.uint8, device=dev)
         ws["bnb_ws_bytes"] = sizes.bnb
-        ws["scale_shift_eval"] = torch.empty(2 * self.max_c, dtype=torch.float32, device=dev)
         ws["max_act"] = sizes.act
         # loss / metric scratch
         ws["loss_rows"] = torch.empty(N, dtype=torch.float32, device=dev)
@@ -297,30 +242,6 @@ class MobileNetV2(ArenaModel):
         return ws[name]
 
     # ------------------------------------------------------------------ primitives
-    def _stats(self, bn):
-        """(mean, invstd, scale, shift) pointers of a BatchNorm's saved batch statistics."""
-        st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-        c = bn.c
-        return st, st + 4 * c, st + 8 * c, st + 12 * c
-
-    def _bn_coeffs(self, fw, bn, rows, count):
-        """(scale, shift) of `bn`: from the `rows` statistic rows the producer just wrote (training; also the saved mean / invstd
-        and the running statistics), or from the running statistics (eval)."""
-        lib, c = self.lib, bn.c
-        rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
-        if fw.training:
-            mean, invstd, scale, shift = self._stats(bn)
-            hip.check(lib.icamd_bn_train_finalize(fw.stats, rows, c, float(count), self._pf(bn.weight), self._pf(bn.bias), rm,
-                                                  rm + 4 * c, BN_MOMENTUM, BN_EPS, mean, invstd, scale, shift,
-                                                  fw.ws["bn_ws"].data_ptr(), fw.s), bn.name)
-            return scale, shift
-        # eval: one coefficient pair for the whole walk -- on the one stream every pair is consumed before the next is formed
-        scale = fw.ws["scale_shift_eval"].data_ptr()
-        shift = scale + 4 * self.max_c
-        hip.check(lib.icamd_bn_eval_coeffs(c, self._pf(bn.weight), self._pf(bn.bias), rm, rm + 4 * c, BN_EPS, scale, shift, fw.s),
-                  bn.name)
-        return scale, shift
-
     def _conv_bn(self, fw, conv, bn, x, h, w, y):
         """y = conv(x) (raw, with statistic rows when training); -> (OH, OW, scale, shift) of the BatchNorm over y"""
         d = conv.desc(fw.N, h, w)
@@ -367,7 +288,7 @@ class MobileNetV2(ArenaModel):
     def forward_packed(self, ws, logits_only=False):   # logits_only: accepted for interface parity (BatchNorm needs every output)
         """Stem, blocks, head -> ws["logits"]: training (batch statistics) or eval (running statistics), the same walk."""
         fw = self._forward_begin(ws)
-        lib, N, s = self.lib, fw.N, fw.s
+        lib, s = self.lib, fw.s
         h, w, *coeffs = self._conv_bn(fw, self.stem_conv, self.stem_bn, ws["x8"], ws["H"], ws["W"], ws["y0"])
         src = ws["y0"]                 # raw: the consumer (blocks.0.0.conv_dw) activates it
         x = None
@@ -383,11 +304,7 @@ class MobileNetV2(ArenaModel):
             x = b["out"]
         h, w, sc, sh = self._conv_bn(fw, self.head_conv, self.head_bn, x, h, w, ws["yh"])
         self._apply_relu6(fw, ws["yh"], sc, sh, ws["ah"], "bn2")
-        hip.check(lib.icamd_avgpool_fwd(ws["ah"].data_ptr(), ws["pooled"].data_ptr(), N, h * w, self.feat_dim, s), "avgpool")
-        dfc = self.fc.desc(N, 1, 1)
-        hip.check(lib.icamd_conv2d_fwd(ctypes.byref(dfc), ws["pooled"].data_ptr(), self._w(self.fc), ws["logits"].data_ptr(),
-                                       self._pf(self.fc.b), None, None, s), "classifier")
-        return ws["logits"]
+        return self._fwd_head(fw, ws["ah"], h, w)
 
     # ------------------------------------------------------------------ backward
     def _bn_bwd(self, run, bn, dout, y, dy, relu6):

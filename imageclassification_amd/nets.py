@@ -25,10 +25,9 @@ from types import SimpleNamespace
 import torch
 
 from . import hip
-from .arena import ArenaModel, Layout, align
+from .bnmodel import BN_EPS, BN_MOMENTUM, _BN, _Conv, BatchNormModel      # noqa: F401  (the names stay importable from here)
 from .streams import side_lane
 
-BN_EPS = 1e-5
 _FUSED_BNBWD = os.environ.get("ICAMD_FUSED_BNBWD", "0") == "1"
 _WGRAD_STREAM = os.environ.get("ICAMD_WGRAD_STREAM", "1") != "0"
 _DUAL_BNBWD = os.environ.get("ICAMD_DUAL_BNBWD", "1") != "0"
@@ -50,7 +49,6 @@ _FUSED_POOL_BWD = os.environ.get("ICAMD_FUSED_POOL_BWD", "1") != "0"
 _STEM_THIN_DEFAULT = {"fwd": True, "dgrad": True, "wgrad": False}
 _STEM_THIN_ENV = os.environ.get("ICAMD_STEM_THIN", "1")
 _STEM_THIN = {op: (_STEM_THIN_ENV == "2" or (_STEM_THIN_ENV != "0" and on)) for op, on in _STEM_THIN_DEFAULT.items()}
-BN_MOMENTUM = 0.1
 
 # name -> (block, blocks per stage, cardinality, base width), as timm / torchvision: a bottleneck's inner width is
 # floor(planes * base_width / 64) * cardinality and its 3x3 convolution has `cardinality` groups
@@ -174,42 +172,6 @@ def se_shapes(name, c, rd):
             (name + ".fc2.weight", (c, rd, 1, 1)), (name + ".fc2.bias", (c,))]
 
 
-class _Conv:
-    """Convolution record. weight param in arena layout [Cout_p][KH][KW][Cin_p / groups] (groups > 1: ResNeXt's 3x3, which runs on
-    the icamd_gconv3x3_* entries with this same filter for forward, data gradient and weight gradient)."""
-
-    def __init__(self, name, cin, cout, k, stride, pad, cin_p=None, cout_p=None, bias=False, k_p=None, groups=1):
-        self.name = name
-        self.groups = groups
-        self.cin, self.cout, self.k, self.stride, self.pad = cin, cout, k, stride, pad
-        self.cin_p = cin_p or cin
-        self.cout_p = cout_p or cout
-        self.k_p = k_p or k        # kernel extent of the arena layout (the stem stores 7x7 filters as 8x8x4, see _build_graph)
-        self.has_bias = bias
-        self.w = None      # arena.Param
-        self.b = None
-        self.wt_offset = None  # offset into the transposed shadow arena (None: no data gradient needed)
-        self.descs = {}    # (N, IH, IW) -> ConvDesc
-        self.thin = False  # 3x3 / stride 1 with 32 input channels (deep stem): the icamd_conv3x3_thin_* entries where routed
-        self.stem7 = False # the 7x7 / stride 2 stem on the rgb4 layout: the icamd_stem7x7s2_* entries
-
-    def desc(self, N, IH, IW):
-        key = (N, IH, IW)
-        d = self.descs.get(key)
-        if d is None:
-            d = hip.conv_desc(N, IH, IW, self.cin_p, self.cout_p, self.k, self.k, self.stride, self.pad)
-            self.descs[key] = d
-        return d
-
-
-class _BN:
-    def __init__(self, name, c):
-        self.name, self.c = name, c
-        self.weight = self.bias = None  # arena.Param
-        self.buf_offset = None          # running_mean at buf_offset, running_var at buf_offset + c
-        self.stat_offset = None         # mean, invstd, scale, shift in the per-model stat arena (4*c floats)
-
-
 class _SE:
     """Squeeze-and-excitation record: fc1 [rd][C] + bias, fc2 [C][rd] + bias, fp32 in the parameter arena in torch layout.  The
     excite kernels read the fp32 masters.  The bf16 shadow arena mirrors the whole parameter arena, so it holds a slice for these
@@ -220,8 +182,9 @@ class _SE:
         self.w1 = self.b1 = self.w2 = self.b2 = None  # arena.Param
 
 
-class ResNet(ArenaModel):
+class ResNet(BatchNormModel):
     """HIP ResNet. `model(x)` runs the forward and returns bf16 logits [B, num_classes] (a view)."""
+    bn_width = 2048     # layer4 of a bottleneck model
 
     def __init__(self, arch="resnet50", num_classes=1000, device="cuda", zero_init_last=True, seed=None):
         super().__init__(arch, num_classes, device)
@@ -302,43 +265,21 @@ class ResNet(ArenaModel):
             if "down_conv" in blk:
                 order += [blk["down_conv"], blk["down_bn"]]
         order.append(self.fc)
-        layout = Layout()
-        add = layout.add
-        boff = 0
-        soff = 0
-        for m in order:
-            if m is self.fc:      # nn.Linear: a 2-D weight in the state_dict, the 1x1 filter [ncls_p][1][1][feat] in the arena
-                m.w = add("fc.weight", (m.cout, m.cin), "lin", (m.cout_p, 1, 1, m.cin_p))
-                m.b = add("fc.bias", (m.cout,), "vec", (m.cout_p,))
-            elif isinstance(m, _Conv):
-                m.w = add(m.name + ".weight", (m.cout, m.cin // m.groups, m.k, m.k), "conv",
-                          (m.cout_p, m.k_p, m.k_p, m.cin_p // m.groups))
-                if m.has_bias:
-                    m.b = add(m.name + ".bias", (m.cout,), "vec", (m.cout_p,))
-            elif isinstance(m, _SE):
-                (n1, s1), (nb1, sb1), (n2, s2), (nb2, sb2) = se_shapes(m.name, m.c, m.rd)
-                m.w1 = add(n1, s1, "conv", (m.rd, 1, 1, m.c))     # [rd][1][1][C] is torch's (rd, C, 1, 1) memory
-                m.b1 = add(nb1, sb1, "vec", sb1)
-                m.w2 = add(n2, s2, "conv", (m.c, 1, 1, m.rd))
-                m.b2 = add(nb2, sb2, "vec", sb2)
-            else:
-                m.weight = add(m.name + ".weight", (m.c,), "vec", (m.c,))
-                m.bias = add(m.name + ".bias", (m.c,), "vec", (m.c,))
-                m.buf_offset = boff
-                boff = align(boff + 2 * m.c, 64)
-                m.stat_offset = soff
-                soff = align(soff + 4 * m.c, 64)
         # transposed filters for the data-gradient kernels (every conv except the stem's first and the grouped ones, whose data
         # gradient reads the forward layout; so does the thin route of the deep stem's other two, but those keep their 2 x 18 KB:
         # ICAMD_STEM_THIN=0 and images too wide for the thin kernels' LDS tile run on icamd_conv2d_dgrad)
-        self._allocate(layout, [(m, m.cout_p, m.k * m.k, m.cin_p) for m in self.convs if m is not self.stem_conv and m.groups == 1],
-                       buffer_elems=boff)
-        self.stat_arena = torch.zeros(max(soff, 64), dtype=torch.float32, device=self.device)
+        self._layout_arenas(order, [(m, m.cout_p, m.k * m.k, m.cin_p) for m in self.convs
+                                    if m is not self.stem_conv and m.groups == 1])
+
+    def _add_record(self, add, se):
+        """The one kind of record of its own: a block's squeeze-and-excitation module."""
+        (n1, s1), (nb1, sb1), (n2, s2), (nb2, sb2) = se_shapes(se.name, se.c, se.rd)
+        se.w1 = add(n1, s1, "conv", (se.rd, 1, 1, se.c))     # [rd][1][1][C] is torch's (rd, C, 1, 1) memory
+        se.b1 = add(nb1, sb1, "vec", sb1)
+        se.w2 = add(n2, s2, "conv", (se.c, 1, 1, se.rd))
+        se.b2 = add(nb2, sb2, "vec", sb2)
 
     # ------------------------------------------------------------------ parameters / state_dict
-    def _ctor_kwargs(self):
-        return {"arch": self.arch, "num_classes": self.num_classes}
-
     def init_weights(self, zero_init_last=True, seed=None):
         """timm ResNet.init_weights: Kaiming-normal (fan_out, relu) convs, BN weight 1 / bias 0, zero-init of the
         last BN weight of each residual block, nn.Linear default init for the classifier; SE convolutions as every nn.Conv2d."""
@@ -369,41 +310,12 @@ class ResNet(ArenaModel):
         if zero_init_last:
             for blk in self.blocks:
                 sd[blk["bns"][-1].name + ".weight"].zero_()
-        for b in self.bns:
-            sd[b.name + ".running_mean"] = torch.zeros(b.c)
-            sd[b.name + ".running_var"] = torch.ones(b.c)
-            sd[b.name + ".num_batches_tracked"] = torch.tensor(0)
+        self._fresh_buffers(sd)
         self.load_state_dict(sd)
 
-    def _buffer_keys(self):
-        return [f"{b.name}.{key}" for b in self.bns for key in ("running_mean", "running_var")]
-
     def _load_buffers(self, sd):
-        bufs = self.buffer_arena.cpu()
-        for b in self.bns:
-            for j, key in enumerate(("running_mean", "running_var")):
-                k = f"{b.name}.{key}"
-                if k in sd:
-                    bufs[b.buf_offset + j * b.c: b.buf_offset + (j + 1) * b.c] = sd[k].detach().float().cpu()
-        self.buffer_arena.copy_(bufs)
-        k = f"{self.bns[0].name}.num_batches_tracked"
-        if k in sd:
-            self.num_batches_tracked = int(sd[k])
+        super()._load_buffers(sd)
         self._fold_dirty = True
-
-    def state_dict(self):
-        """Parameters in module order, each BatchNorm's buffers right after its bias (torch's key order)."""
-        bufs = self.buffer_arena.cpu()
-        bn_of_bias = {b.name + ".bias": b for b in self.bns}
-        sd = OrderedDict()
-        for name, t in super().state_dict().items():
-            sd[name] = t
-            b = bn_of_bias.get(name)
-            if b is not None:
-                sd[b.name + ".running_mean"] = bufs[b.buf_offset:b.buf_offset + b.c].clone()
-                sd[b.name + ".running_var"] = bufs[b.buf_offset + b.c:b.buf_offset + 2 * b.c].clone()
-                sd[b.name + ".num_batches_tracked"] = torch.tensor(self.num_batches_tracked)
-        return sd
 
     def train(self, mode=True):
         self._fold_dirty = True     # parameters / running statistics may move before the next eval forward
@@ -527,7 +439,7 @@ class ResNet(ArenaModel):
         dfc = self.fc.desc(N, 1, 1)
         max_wg = max(max_wg, self._wgrad_workspace_bytes(self.fc, dfc))
         ws["stats"] = torch.empty(max_stats, dtype=torch.float32, device=dev)
-        ws["bn_ws"] = torch.zeros(lib.icamd_bn_workspace_bytes(2048), dtype=torch.uint8, device=dev)
+        self._bn_workspaces(ws)
         ws["wgrad_ws"] = torch.empty(max_wg, dtype=torch.uint8, device=dev)
         ws["wgrad_ws_bytes"] = max_wg
         ws["bnb_part"] = torch.empty(max_stats + 4 * 2 * 2048, dtype=torch.float32, device=dev)
@@ -549,7 +461,6 @@ class ResNet(ArenaModel):
         ws["pred"] = torch.empty(N, dtype=torch.int32, device=dev)
         ws["dlogits"] = torch.zeros(N, self.ncls_p, dtype=torch.bfloat16, device=dev)
         ws["dpooled"] = torch.empty(N, self.feat_dim, dtype=torch.bfloat16, device=dev)
-        ws["scale_shift_eval"] = torch.empty(2 * 2048, dtype=torch.float32, device=dev)
         self._ws[key] = ws
         return ws
 
@@ -569,12 +480,6 @@ class ResNet(ArenaModel):
         raise KeyError(ptr)
 
     # ------------------------------------------------------------------ primitive wrappers
-    def _stats(self, bn):
-        """(mean, invstd, scale, shift) pointers of a BatchNorm's saved batch statistics."""
-        st = self.stat_arena.data_ptr() + 4 * bn.stat_offset
-        c = bn.c
-        return st, st + 4 * c, st + 8 * c, st + 12 * c
-
     # The stem / grouped / dense dispatch on a convolution, once per kind of launch.  `d` is conv.desc(...) of the input shape.
     def _thin(self, conv, d, op):
         """Does `op` ("fwd", "dgrad", "wgrad") of this convolution run on the thin 3x3 kernels?"""
@@ -649,23 +554,10 @@ class ResNet(ArenaModel):
                        shift=self.eval_shift.data_ptr() + 4 * bn.shift_offset, residual=residual, relu=int(relu))
         return d
 
-    def _bn_coeffs(self, fw, conv, bn, d):
-        """(scale, shift) of `bn` over the raw output of `conv`: from the statistic rows the convolution just wrote (training; also
-        the saved mean / invstd and the running statistics), or from the running statistics (eval)."""
-        lib, c = self.lib, bn.c
-        rm = self.buffer_arena.data_ptr() + 4 * bn.buf_offset
-        if fw.training:
-            mean, invstd, scale, shift = self._stats(bn)
-            rows = self._stats_rows(conv, d)
-            hip.check(lib.icamd_bn_train_finalize(fw.stats, rows, c, float(fw.N * d.OH * d.OW), self._pf(bn.weight),
-                                                  self._pf(bn.bias), rm, rm + 4 * c, BN_MOMENTUM, BN_EPS, mean, invstd,
-                                                  scale, shift, fw.ws["bn_ws"].data_ptr(), fw.s), bn.name)
-        else:
-            scale = fw.ws["scale_shift_eval"].data_ptr()
-            shift = scale + 4 * 2048
-            hip.check(lib.icamd_bn_eval_coeffs(c, self._pf(bn.weight), self._pf(bn.bias), rm, rm + 4 * c, BN_EPS, scale,
-                                               shift, fw.s), bn.name)
-        return scale, shift
+    def _conv_bn_coeffs(self, fw, conv, bn, d):
+        """(scale, shift) of `bn` over the raw output of `conv`, whose forward just ran on descriptor `d`."""
+        rows = self._stats_rows(conv, d) if fw.training else 0
+        return self._bn_coeffs(fw, bn, rows, fw.N * d.OH * d.OW)
 
     def _conv_coeffs(self, fw, conv, bn, x, ih, iw, y):
         """y = conv(x) with what turns y into the BatchNorm output, always as (d, scale, shift), for a caller that fuses the apply
@@ -676,7 +568,7 @@ class ResNet(ArenaModel):
             return self._conv_folded(fw, conv, bn, x, ih, iw, y, False), one, one + 4 * 4096
         d = conv.desc(fw.N, ih, iw)
         self._conv_fwd(conv, d, x.data_ptr(), self._w(conv), y.data_ptr(), fw.s, stats=fw.stats)
-        return (d,) + self._bn_coeffs(fw, conv, bn, d)
+        return (d,) + self._conv_bn_coeffs(fw, conv, bn, d)
 
     def _bn_apply(self, fw, bn, y, scale, shift, out, relu, residual=None, res_bn=None, mask=None):
         """out = act(y * scale + shift (+ residual, through its own BatchNorm where res_bn is given)); mask: the ReLU bits."""
@@ -796,7 +688,7 @@ class ResNet(ArenaModel):
             hip.check(self.lib.icamd_bn_apply_conv1x1_fused(ctypes.byref(d), p.y.data_ptr(), p.scale, p.shift, p.residual, res_scale,
                                                             res_shift, x.data_ptr(), p.mask, self._w(convs[0]), b["y"][0].data_ptr(),
                                                             fw.stats, s), p.bn.name + " apply + " + convs[0].name)
-            self._bn_apply(fw, bns[0], b["y"][0], *self._bn_coeffs(fw, convs[0], bns[0], d), b["a"][0], True)
+            self._bn_apply(fw, bns[0], b["y"][0], *self._conv_bn_coeffs(fw, convs[0], bns[0], d), b["a"][0], True)
             x, h, w, first = b["a"][0], d.OH, d.OW, 1
         idn, res_bn = self._fwd_shortcut(fw, blk, b, b["in"], *b["in_hw"])
         mask = b["mask"].data_ptr() if fw.training else None
@@ -817,15 +709,6 @@ class ResNet(ArenaModel):
                 d = self._conv_bn_act(fw, conv, bn, x, h, w, y, out, True, idn.data_ptr(), res_bn, mask)
             x, h, w = out, d.OH, d.OW
         return x, h, w, deferred
-
-    def _fwd_head(self, fw, x, h, w):
-        """Global average pool + classifier -> ws["logits"]."""
-        lib, ws, N, s = self.lib, fw.ws, fw.N, fw.s
-        hip.check(lib.icamd_avgpool_fwd(x.data_ptr(), ws["pooled"].data_ptr(), N, h * w, self.feat_dim, s), "avgpool")
-        dfc = self.fc.desc(N, 1, 1)
-        hip.check(lib.icamd_conv2d_fwd(ctypes.byref(dfc), ws["pooled"].data_ptr(), self._w(self.fc),
-                                       ws["logits"].data_ptr(), self._pf(self.fc.b), None, None, s), "fc")
-        return ws["logits"]
 
     # ------------------------------------------------------------------ backward
     def backward_packed(self, ws, accumulate=False):

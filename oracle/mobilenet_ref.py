@@ -1,34 +1,18 @@
-"""References of the MobileNet-class kernels (csrc/dwconv3x3.hip), on the CPU: BatchNorm + ReLU6 with the kernel's single rounding,
-and the depthwise 3x3 convolution with its two gradients in fp64 on the bf16 operands the kernel sees."""
+"""CPU oracle: MobileNetV2 in plain torch (TEST INFRASTRUCTURE ONLY -- never imported by the product).
+
+timm's mobilenetv2_* restated from its layer list (timm is not importable here: parity with it is unpinned; the published parameter
+counts are checked in tests/test_mobilenetv2_cpu.py).  The layer list and make_divisible are written out here independently of the
+product's table, and this file imports nothing of the product: the CPU tests compare the two.
+
+`bf16_points=True` inserts the rounding points of the HIP path (oracle/resnet_ref.py's `_r` / `_w`: activations and their gradients
+to bf16, filters straight through).  A Tape records the tensors a run stores, or puts those of another run in their place
+(teacher forcing; the protocol built on it is in tests/_parity.py)."""
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
 
-from oracle import ops_ref as R
+from oracle.resnet_ref import _r, _w
 
-
-def fma32(x, scale, shift):
-    """fp32 fma(x, scale[c], shift[c]): the product of a bf16 and an fp32 value is exact in fp64 and the sum is rounded there to 53
-    bits before the rounding to 24, which differs from the single rounding of an fma only on a 2^-29 share of the inputs"""
-    return (x.double() * scale.double() + shift.double()).float()
-
-
-def bn_relu6(x, scale, shift):
-    """bf16(min(max(fma(x, scale, shift), 0), 6)): what icamd_bn_apply_relu6 stores and the on-load kernels form in registers"""
-    return R.bf16_round(fma32(x, scale, shift).clamp(0.0, 6.0))
-
-
-def dwconv3_ref(a_nhwc, w_c33, dy_nhwc, stride):
-    """F.conv2d(groups=C, padding=1) in fp64 on the (activated, rounded) input and autograd: y and dx on the bf16 grid, dw [C,3,3]"""
-    C = a_nhwc.shape[-1]
-    a = R.nhwc_to_nchw(a_nhwc.double()).requires_grad_(True)
-    w = w_c33.double().reshape(C, 1, 3, 3).clone().requires_grad_(True)
-    y = F.conv2d(a, w, None, stride, 1, 1, C)
-    y.backward(R.nhwc_to_nchw(dy_nhwc.double()))
-    return R.bf16_round(R.nchw_to_nhwc(y.detach())), R.bf16_round(R.nchw_to_nhwc(a.grad)), w.grad.reshape(C, 3, 3)
-
-
-# ---- the whole model: timm's mobilenetv2_* restated from its layer list (timm is not importable here: parity with it is unpinned;
-# the published parameter counts are checked in tests/test_mobilenetv2_cpu.py) ----------------------------------------------------
 STAGES = ((2, 2, 24), (3, 2, 32), (4, 2, 64), (3, 1, 96), (3, 2, 160), (1, 1, 320))      # repeats, first stride, out
 WIDTHS = {"mobilenetv2_035": 0.35, "mobilenetv2_050": 0.5, "mobilenetv2_075": 0.75, "mobilenetv2_100": 1.0, "mobilenetv2_140": 1.4}
 TEST_ARCH = {"stem": 16, "first": 8, "stages": ((2, 2, 16), (1, 2, 24), (2, 1, 32)), "head": 64}
@@ -70,10 +54,6 @@ def param_count(arch, num_classes=1000):
                 n += cin * mid + 2 * mid + 9 * mid + 2 * mid + mid * cout + 2 * cout
             last = cout
     return n + last * head + 2 * head + head * num_classes + num_classes
-
-
-from oracle.resnet_ref import _r, _w  # noqa: E402  (the rounding points: activations / gradients to bf16, filters straight through)
-import torch.nn as nn  # noqa: E402
 
 
 class _Force(torch.autograd.Function):
@@ -239,50 +219,3 @@ def perturb(ref, seed):
                 m.running_mean.copy_(0.2 * torch.randn(m.running_mean.shape, generator=g))
                 m.running_var.copy_(0.5 + torch.rand(m.running_var.shape, generator=g))
     return ref
-
-
-# ---- teacher-forced gradients: the whole-model check that bf16 drift cannot blur -------------------------------------------------
-def forced_gradients(ref, values, x, y, smoothing):
-    """{name: gradient} of a copy of `ref` whose stored tensors are `values` (Tape order, NCHW, on the bf16 grid), and its loss"""
-    import copy
-    m = copy.deepcopy(ref)
-    for p in m.parameters():
-        p.grad = None
-    m.train()
-    tape = Tape(values)
-    m.set_tape(tape)
-    loss = F.cross_entropy(m(x), y, label_smoothing=smoothing)
-    loss.backward()
-    assert tape.i == len(tape.values)
-    return {n: p.grad for n, p in m.named_parameters()}, float(loss.detach())
-
-
-def recorded_step(model, x, y, smoothing):
-    """one training forward + backward of `model` (any dtype) with its stored tensors recorded: (values as fp32, {name: gradient})"""
-    for p in model.parameters():
-        p.grad = None
-    model.train()
-    tape = Tape()
-    model.set_tape(tape)
-    F.cross_entropy(model(x.to(next(model.parameters()).dtype)), y, label_smoothing=smoothing).backward()
-    model.set_tape(None)
-    return [v.float() for v in tape.rec], {n: p.grad for n, p in model.named_parameters()}
-
-
-def negligible_gradients(ref, x, y, smoothing, arch="mobilenetv2_test"):
-    """Names of the BatchNorm parameters whose TRUE gradient (fp64, no rounding points) is below 1e-3 of the gradient of the
-    convolution in front of them: the bias of a BatchNorm without activation in front of a convolution + BatchNorm (exactly zero: the
-    next batch mean removes a per-channel shift) and, while no channel clamps at 6 and the bias is 0, the weight of a BatchNorm in
-    front of ReLU6 + depthwise convolution + BatchNorm (zero but for eps: the per-channel gain is normalised away).  bf16 cannot
-    resolve them: what any bf16 run computes there is rounding residue."""
-    exact = MobileNetV2Ref(arch, ref.classifier.out_features, bf16_points=False).double()
-    exact.load_state_dict(ref.state_dict())
-    exact.train()
-    F.cross_entropy(exact(x.double()), y, label_smoothing=smoothing).backward()
-    out, conv = {}, None
-    for n, p in exact.named_parameters():
-        if p.dim() == 4:
-            conv = n
-        elif p.dim() == 1 and conv is not None and float(p.grad.norm()) <= 1e-3 * float(dict(exact.named_parameters())[conv].grad.norm()):
-            out[n] = conv
-    return out

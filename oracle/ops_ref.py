@@ -575,3 +575,25 @@ def layerscale_bwd(dout, z, gamma, keep):
     k = 1.0 if keep is None else keep.float().reshape(-1, *([1] * (z.dim() - 1)))
     d = dout.float() * k
     return bf16_round(d * gamma.float()), (d * z.float()).reshape(-1, z.shape[-1]).double().sum(0).float()
+
+
+# ---- MobileNet pieces (csrc/dwconv3x3.hip): BatchNorm + ReLU6 with the kernel's single rounding, depthwise 3x3 -------------------
+def fma32(x, scale, shift):
+    """fp32 fma(x, scale[c], shift[c]): the product of a bf16 and an fp32 value is exact in fp64 and the sum is rounded there to 53
+    bits before the rounding to 24, which differs from the single rounding of an fma only on a 2^-29 share of the inputs"""
+    return (x.double() * scale.double() + shift.double()).float()
+
+
+def bn_relu6(x, scale, shift):
+    """bf16(min(max(fma(x, scale, shift), 0), 6)): what icamd_bn_apply_relu6 stores and the on-load kernels form in registers"""
+    return bf16_round(fma32(x, scale, shift).clamp(0.0, 6.0))
+
+
+def dwconv3_ref(a_nhwc, w_c33, dy_nhwc, stride):
+    """F.conv2d(groups=C, padding=1) in fp64 on the (activated, rounded) input and autograd: y and dx on the bf16 grid, dw [C,3,3]"""
+    C = a_nhwc.shape[-1]
+    a = nhwc_to_nchw(a_nhwc.double()).requires_grad_(True)
+    w = w_c33.double().reshape(C, 1, 3, 3).clone().requires_grad_(True)
+    y = F.conv2d(a, w, None, stride, 1, 1, C)
+    y.backward(nhwc_to_nchw(dy_nhwc.double()))
+    return bf16_round(nchw_to_nhwc(y.detach())), bf16_round(nchw_to_nhwc(a.grad)), w.grad.reshape(C, 3, 3)

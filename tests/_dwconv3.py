@@ -7,7 +7,6 @@ import torch
 
 import _harness
 from _harness import DEV, dev, guarded
-from _mobilenetv2_ref import bn_relu6, dwconv3_ref
 from oracle import ops_ref as R
 
 RS = 16                                                    # output rows per item (dwconv3x3.hip)
@@ -70,7 +69,7 @@ def clamp_shares(a):
 @functools.lru_cache(maxsize=None)
 def case(shape, stride, onload):
     """operands and the fp64 reference of one case, computed once: x (raw), scale / shift (onload), a (what the stencil sees), w
-    [C,3,3], dy, and y / dx / dw of dwconv3_ref"""
+    [C,3,3], dy, and y / dx / dw of R.dwconv3_ref"""
     N, H, W, C = shape
     g = torch.Generator().manual_seed(1000 + 7 * N + H + 3 * stride)
     x = R.bf16_round(1.5 * torch.randn(N, H, W, C, generator=g))
@@ -78,8 +77,8 @@ def case(shape, stride, onload):
     OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
     dy = R.bf16_round(torch.randn(N, OH, OW, C, generator=g))
     scale, shift = coeffs(C, 17 + C) if onload else (None, None)
-    a = bn_relu6(x, scale, shift) if onload else x
-    y, dx, dw = dwconv3_ref(a, w, dy, stride)
+    a = R.bn_relu6(x, scale, shift) if onload else x
+    y, dx, dw = R.dwconv3_ref(a, w, dy, stride)
     return {"x": x, "w": w, "dy": dy, "scale": scale, "shift": shift, "a": a, "y": y, "dx": dx, "dw": dw, "OH": OH, "OW": OW}
 
 

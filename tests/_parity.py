@@ -1,5 +1,5 @@
 """What the whole-network parity tests of every family share: the loss + backward call, one training step of a CPU oracle beside
-its fp64 twin, the same step on the HIP kernels, the comparison of the two, and one perturbed (oracle, HIP model) pair per family.
+its fp64 twin, the same step on the HIP kernels, the comparison of the two, one perturbed (oracle, HIP model) pair per family, and the teacher-forcing protocol.
 The oracle's own re-association noise (fp64 against fp32 accumulation, same rounding points) is the yardstick of every bound.
 Importing this module needs no GPU."""
 import copy
@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import ops_ref as R
+from oracle.mobilenet_ref import MobileNetV2Ref, Tape, perturb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -169,6 +170,18 @@ def swin_pair(arch, C, img, seed=0, drop_path_rate=0.0):
     return ref, net
 
 
+def mobilenet_pair(arch, C, perturbed, seed=0):
+    """timm's default init, or (perturbed) BatchNorm affine and running statistics at which ReLU6 clamps at both ends"""
+    from imageclassification_amd.mobilenet import MobileNetV2
+    torch.manual_seed(seed)
+    ref = MobileNetV2Ref(arch, C, bf16_points=True)
+    if perturbed:
+        perturb(ref, seed + 1)
+    net = MobileNetV2(arch, C)
+    net.load_state_dict(ref.state_dict())
+    return ref, net
+
+
 # ---------------------------------------------------------------------------------------------------------------- ConvNeXt cases
 def convnext_case(arch, C, B, HW, cfg=None):
     """One oracle evaluation of a perturbed ConvNeXt under injected stochastic-depth masks (training pass with its fp64 twin, then
@@ -204,3 +217,50 @@ def convnext_case_eval(case):
     torch.cuda.synchronize()
     net.train()
     return R.rel_l2(got, case["eval"]), R.rel_l2(case["eval64"].float(), case["eval"])
+
+
+# ---------------------------------------------------------------------------------------------------------------- teacher forcing
+# The whole-model gradient check that bf16 drift cannot blur, for an oracle with set_tape (oracle/mobilenet_ref.py::Tape)
+def forced_gradients(ref, values, x, y, smoothing):
+    """{name: gradient} of a copy of `ref` whose stored tensors are `values` (Tape order, NCHW, on the bf16 grid), and its loss"""
+    m = copy.deepcopy(ref)
+    for p in m.parameters():
+        p.grad = None
+    m.train()
+    tape = Tape(values)
+    m.set_tape(tape)
+    loss = F.cross_entropy(m(x), y, label_smoothing=smoothing)
+    loss.backward()
+    assert tape.i == len(tape.values)
+    return {n: p.grad for n, p in m.named_parameters()}, float(loss.detach())
+
+
+def recorded_step(model, x, y, smoothing):
+    """one training forward + backward of `model` (any dtype) with its stored tensors recorded: (values as fp32, {name: gradient})"""
+    for p in model.parameters():
+        p.grad = None
+    model.train()
+    tape = Tape()
+    model.set_tape(tape)
+    F.cross_entropy(model(x.to(next(model.parameters()).dtype)), y, label_smoothing=smoothing).backward()
+    model.set_tape(None)
+    return [v.float() for v in tape.rec], {n: p.grad for n, p in model.named_parameters()}
+
+
+def negligible_gradients(ref, x, y, smoothing, arch="mobilenetv2_test"):
+    """Names of the BatchNorm parameters whose TRUE gradient (fp64, no rounding points) is below 1e-3 of the gradient of the
+    convolution in front of them: the bias of a BatchNorm without activation in front of a convolution + BatchNorm (exactly zero: the
+    next batch mean removes a per-channel shift) and, while no channel clamps at 6 and the bias is 0, the weight of a BatchNorm in
+    front of ReLU6 + depthwise convolution + BatchNorm (zero but for eps: the per-channel gain is normalised away).  bf16 cannot
+    resolve them: what any bf16 run computes there is rounding residue."""
+    exact = MobileNetV2Ref(arch, ref.classifier.out_features, bf16_points=False).double()
+    exact.load_state_dict(ref.state_dict())
+    exact.train()
+    F.cross_entropy(exact(x.double()), y, label_smoothing=smoothing).backward()
+    out, conv = {}, None
+    for n, p in exact.named_parameters():
+        if p.dim() == 4:
+            conv = n
+        elif p.dim() == 1 and conv is not None and float(p.grad.norm()) <= 1e-3 * float(dict(exact.named_parameters())[conv].grad.norm()):
+            out[n] = conv
+    return out

@@ -16,7 +16,6 @@ import torch.nn.functional as F
 import _harness
 from _harness import DEV, dev, digest, guarded, intact, sync
 from _harness import lib  # noqa: F401
-from _mobilenetv2_ref import bn_relu6, fma32
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -43,7 +42,7 @@ def operands(rows, C):
 def test_bn_apply_relu6(lib, rows, C):
     hip = _harness.hip()
     y, _, _, _, _, _, scale, shift = operands(rows, C)
-    ref = bn_relu6(y, scale, shift)
+    ref = R.bn_relu6(y, scale, shift)
     at6, at0 = float((ref == 6).float().mean()), float((ref == 0).float().mean())
     print(f"({rows}, {C}): {at6:.1%} at 6, {at0:.1%} at 0")
     assert at6 >= 0.02 and at0 >= 0.20
@@ -64,7 +63,7 @@ def test_bn_apply_relu6(lib, rows, C):
 def test_bn_bwd_relu6(lib, rows, C):
     hip = _harness.hip()
     y, dout, gamma, beta, mean, invstd, scale, shift = operands(rows, C)
-    z32 = fma32(y, scale, shift)
+    z32 = R.fma32(y, scale, shift)
     mask = (z32 > 0) & (z32 < 6)
     at6, at0 = float((z32 >= 6).float().mean()), float((z32 <= 0).float().mean())
     assert at6 >= 0.02 and at0 >= 0.20

@@ -1,4 +1,4 @@
-"""The library calls of a ViT, Swin, ConvNeXt (V1 folded and unfolded, V2) and ResNet (nets.py) training step, without a GPU: every launch of construct / pack / forward / backward /
+"""The library calls of a ViT, Swin, ConvNeXt (V1 folded and unfolded, V2), ResNet (nets.py) and MobileNetV2 training step, without a GPU: every launch of construct / pack / forward / backward /
 accumulating backward / eval forward (ResNet: twice) / reload -- entry, arguments, buffers, stream, order, side-lane waits and gradient-hook calls --
 is the recorded one (tests/golden/call_traces.json, written by tests/golden/make_call_traces.py, whose docstring states what a
 record holds), and a seed still gives the weights it gave.
@@ -129,6 +129,45 @@ def test_the_resnet_cases_call_every_entry_nets_names(resnet_calls):
         named = {n for n in re.findall(r"\bicamd_\w+", f.read()) if n in hip._SIGNATURES}
     called = set().union(*(c for c, _, _ in resnet_calls.values()))
     assert len(named) > 50 and sorted(named - called) == []
+
+
+MOBILENET_CASES = ("mobilenetv2_test/default", "mobilenetv2_test/onload")
+DW_ENTRIES = ("icamd_dwconv3_fwd", "icamd_dwconv3_wgrad")        # (x, scale, shift, ...): the input and what activates it on load
+
+
+def test_mobilenet_cases_are_the_listed_ones():
+    assert set(MOBILENET_CASES) == {c for c in G.CASES if G.MODELS[G.CASES[c].model][0] == "mobilenet"}
+
+
+@pytest.mark.parametrize("case_id", MOBILENET_CASES)
+def test_the_mobilenet_cases_take_the_paths_they_are_there_for(recorders, case_id):
+    """default: icamd_bn_apply_relu6 writes the model's one scratch right in front of every depthwise forward and weight gradient,
+    which read it with null scale / shift.  onload: nothing is applied into a scratch, the depthwise entries read the raw tensor with
+    the BatchNorm's scale / shift.  One stream either way."""
+    seen = []
+    G.run_case(case_id, lambda k, v: recorders.delenv(k, raising=False) if v is None else recorders.setenv(k, v),
+               setattr_fn=recorders.setattr, observer=lambda model, held, x: seen.append(model))
+    ws, depthwise = seen[0]._ws[(G.BATCH, 64, 64)], len(seen[0].blocks)
+    launches = [r for r in G.TRACE if r[0].startswith("icamd_") and not r[0].endswith(("_bytes", "_supported", "_rows"))]
+    assert {r[2][-1] for r in launches} == {0} and not any(r[0].startswith("lane.") for r in G.TRACE)
+    dw = [k for k, r in enumerate(launches) if r[0] in DW_ENTRIES]
+    # one depthwise layer per block: one training and one eval forward, two backward passes
+    assert depthwise == 6 and [launches[k][0] for k in dw].count("icamd_dwconv3_fwd") == 2 * depthwise and len(dw) == 4 * depthwise
+    applies = [r for r in launches if r[0] == "icamd_bn_apply_relu6"]
+    if case_id.endswith("/default"):
+        a1 = ws["a1"].data_ptr()
+        for k in dw:
+            before, (x, scale, shift) = launches[k - 1], launches[k][2][:3]
+            assert before[0] == "icamd_bn_apply_relu6" and before[2][3] == a1
+            assert x == a1 and scale is None and shift is None
+        assert sum(r[2][3] == a1 for r in applies) == len(dw)
+    else:
+        assert "a1" not in ws
+        inputs = {launches[k][2][0] for k in dw}
+        assert not any(r[2][3] in inputs for r in applies)
+        stored = {t.data_ptr() for b in ws["blocks"] for t in (b["a2"],)} | {ws["ah"].data_ptr()}
+        assert {r[2][3] for r in applies} == stored          # every apply left is one whose output the step stores
+        assert all(launches[k][2][1] and launches[k][2][2] for k in dw)
 
 
 FOLDED = ["icamd_layerscale_fold", "icamd_layerscale_param_grads", "icamd_conv2d_dgrad_gelu"]

@@ -20,7 +20,6 @@ import _dwconv3 as D
 import _harness
 from _harness import DEV, guarded, intact, sync
 from _harness import lib  # noqa: F401
-from _mobilenetv2_ref import bn_relu6
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu

@@ -14,7 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import _dwconv3 as D
-from _mobilenetv2_ref import MobileNetV2Ref, WIDTHS, layer_list, param_count, plain_sequential
+from oracle.mobilenet_ref import MobileNetV2Ref, WIDTHS, layer_list, param_count, plain_sequential
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PUBLISHED = {"mobilenetv2_035": 1677128, "mobilenetv2_050": 1968680, "mobilenetv2_075": 2636424, "mobilenetv2_100": 3504872,

@@ -1,4 +1,4 @@
-"""MobileNetV2 on the HIP kernels against tests/_mobilenetv2_ref.py::MobileNetV2Ref with the rounding points of the HIP path, under the
+"""MobileNetV2 on the HIP kernels against oracle/mobilenet_ref.py::MobileNetV2Ref with the rounding points of the HIP path, under the
 yardstick protocol of tests/_resnet_parity.py: the reference's own fp64 copy sets the noise every bound is a multiple of.
 The gradients are held a second time under teacher forcing (forced_check below), where that noise is capped at 8e-3 / 2.5e-2.
 
@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from _mobilenetv2_ref import MobileNetV2Ref, forced_gradients, negligible_gradients, param_count, perturb, recorded_step
-from _parity import xent_backward
+from _parity import forced_gradients, mobilenet_pair, negligible_gradients, recorded_step, xent_backward
 from _resnet_parity import assert_hip_within_yardstick, hip_rows, parity_batch, yardstick
 from oracle import ops_ref as R
+from oracle.mobilenet_ref import param_count
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -29,13 +29,7 @@ def _net(arch=ARCH, num_classes=C):
 
 
 def _pair(perturbed, seed=0):
-    torch.manual_seed(seed)
-    ref = MobileNetV2Ref(ARCH, C, bf16_points=True)
-    if perturbed:
-        perturb(ref, seed + 1)
-    net = _net()
-    net.load_state_dict(ref.state_dict())
-    return ref, net
+    return mobilenet_pair(ARCH, C, perturbed, seed)
 
 
 def hip_stored_tensors(net, ws):
@@ -105,7 +99,7 @@ def test_one_training_step_and_eval_logits(perturbed):
     # What that yardstick is worth here: every stored tensor is a bf16 rounding point, a difference d in front of one leaves about
     # sqrt(4e-3 d) behind it, so two runs that sum in different orders drift apart layer by layer until they differ at bf16's own level
     # and ReLU6 masks flip: the reference and its fp64 copy agree to 10-20 % on most gradients, and the protocol above is that wide.
-    # So the gradients are held a second time under TEACHER FORCING (tests/_mobilenetv2_ref.py::Tape): the reference runs on the HIP
+    # So the gradients are held a second time under TEACHER FORCING (oracle/mobilenet_ref.py::Tape, tests/_parity.py): the reference runs on the HIP
     # path's own stored tensors -- input, every convolution output, a2, block outputs, head, pooled, logits --, so masks and batch
     # statistics are those of the same numbers and nothing drifts.  Its yardstick is the same construction between the reference and
     # its fp64 copy; that one is capped, and so is what it admits.
