@@ -5,6 +5,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -I../../include"
 UNITS="conv_igemm conv3x3_halo conv_grouped conv1x1_resident conv_fused_bwd conv_fused_fwd conv_stem conv_stem_deep conv_wgrad norm_pool se_ops loss_optim token_ops attention attention_long window_attention window_attention_w12 dwconv dwconv3x3 grn gemm_nt image_ops collective capi capi_conv_special capi_norm capi_tokens capi_step"
+UNITS="$UNITS dwconv5x5"
 asm_of() { echo "build/$1-hip-amdgcn-amd-amdhsa-gfx950.s"; }
 OBJS=""
 ASMS=""

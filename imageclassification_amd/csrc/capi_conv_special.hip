@@ -408,4 +408,44 @@ int icamd_dwconv3_wgrad(const void* x, const float* in_scale, const float* in_sh
                                     accumulate, (hipStream_t)stream);
 }
 
+// ---- depthwise 5x5, pad 2, stride 1 / 2 (dwconv5x5.hip).  Arguments are validated before any profiling work is booked.
+int icamd_dwconv5_supported(int N, int H, int W, int C, int stride) { return icamd_dwconv5_ok(N, H, W, C, stride) ? 1 : 0; }
+
+int icamd_dwconv5_stats_rows(int N, int H, int W, int C, int stride) { return (int)icamd_dwconv5_stats_rows_cxx(N, H, W, C, stride); }
+
+int icamd_dwconv5_fwd(const void* x, const void* w, void* y, float* stats, int N, int H, int W, int C, int stride, void* stream) {
+  if (x == nullptr || w == nullptr || y == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_dwconv5_ok(N, H, W, C, stride)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_DWCONV, stream);
+  const double out = dw3_out_elements(N, H, W, C, stride);
+  _prof.work(2.0 * N * H * W * C + 2.0 * out + (stats ? 8.0 * icamd_dwconv5_stats_rows_cxx(N, H, W, C, stride) * C : 0.0), 50.0 * out);
+  return icamd_dwconv5_fwd_launch((const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, stats, N, H, W, C, stride, 0, (hipStream_t)stream);
+}
+
+int icamd_dwconv5_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int stride, void* stream) {
+  if (dy == nullptr || w == nullptr || dx == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_dwconv5_ok(N, H, W, C, stride)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_DWCONV, stream);
+  const double out = dw3_out_elements(N, H, W, C, stride);
+  _prof.work(2.0 * N * H * W * C + 2.0 * out, 50.0 * out);
+  return icamd_dwconv5_dgrad_launch((const bf16_t*)dy, (const bf16_t*)w, (bf16_t*)dx, N, H, W, C, stride, (hipStream_t)stream);
+}
+
+size_t icamd_dwconv5_wgrad_workspace_bytes(int N, int H, int W, int C, int stride) {
+  return (size_t)icamd_dwconv5_wgrad_rows(N, H, W, C, stride) * 25 * C * sizeof(float);   // one region: [rows][25][C]
+}
+
+int icamd_dwconv5_wgrad(const void* x, const void* dy, float* dw, int accumulate, void* workspace, size_t workspace_bytes, int N, int H,
+                        int W, int C, int stride, void* stream) {
+  if (x == nullptr || dy == nullptr || dw == nullptr || workspace == nullptr) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_dwconv5_ok(N, H, W, C, stride)) return ICAMD_ERR_UNSUPPORTED;
+  const size_t need = icamd_dwconv5_wgrad_workspace_bytes(N, H, W, C, stride);
+  if (need == 0 || workspace_bytes < need) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_DWCONV, stream);
+  const double out = dw3_out_elements(N, H, W, C, stride);
+  _prof.work(2.0 * N * H * W * C + 2.0 * out + 2.0 * need, 50.0 * out);
+  return icamd_dwconv5_wgrad_launch((const bf16_t*)x, (const bf16_t*)dy, (float*)workspace, dw, N, H, W, C, stride, accumulate,
+                                    (hipStream_t)stream);
+}
+
 }  // extern "C"

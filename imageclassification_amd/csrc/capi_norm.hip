@@ -249,6 +249,92 @@ int icamd_bn_bwd_relu6(const void* dout, const void* y, const float* mean, const
                                    C, accumulate, w.part, w.chunks, w.scratch, (hipStream_t)stream);
 }
 
+// ---- BatchNorm + SiLU and the MBConv squeeze-and-excitation (dwconv5x5.hip) ----
+int icamd_bn_apply_silu(const void* y, const float* scale, const float* shift, const float* e, void* out, int N, int HW, int C,
+                        void* stream) {
+  if (y == nullptr || scale == nullptr || shift == nullptr || out == nullptr || N <= 0 || HW <= 0 || C <= 0) return ICAMD_ERR_BAD_ARG;
+  if (!icamd_silu_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_BN_APPLY, stream);
+  _prof.work((double)N * HW * C * 4 + (e ? 4.0 * N * C : 0.0));
+  return icamd_bn_apply_silu_launch((const bf16_t*)y, scale, shift, e, (bf16_t*)out, N, HW, C, (hipStream_t)stream);
+}
+
+size_t icamd_bn_silu_squeeze_workspace_bytes(int N, int HW, int C) {
+  return icamd_silu_shape_ok(N, HW, C, 1) ? icamd_silu_rowsum_bytes(N, HW, C) : 0;
+}
+
+int icamd_bn_silu_squeeze(const void* y, const float* scale, const float* shift, float* asum, int N, int HW, int C, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (y == nullptr || scale == nullptr || shift == nullptr || asum == nullptr || workspace == nullptr || N <= 0 || HW <= 0 || C <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_silu_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace_bytes < icamd_silu_rowsum_bytes(N, HW, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_POOL, stream);
+  _prof.work(2.0 * N * HW * C + 4.0 * N * C);
+  return icamd_silu_rowsum_launch(nullptr, (const bf16_t*)y, scale, shift, asum, N, HW, C, (float*)workspace, (hipStream_t)stream);
+}
+
+int icamd_se_excite_silu_fwd(const float* asum, float inv_hw, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* s, float* hpre, float* e, int N, int C, int rd, void* stream) {
+  if (asum == nullptr || w1 == nullptr || b1 == nullptr || w2 == nullptr || b2 == nullptr || s == nullptr || hpre == nullptr ||
+      e == nullptr || N <= 0 || C <= 0 || rd <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_silu_shape_ok(N, 1, C, rd)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_MISC, stream);
+  _prof.work(4.0 * N * (3.0 * C + rd) + 4.0 * (2.0 * C * rd + C + rd), 4.0 * N * C * rd);
+  return icamd_se_excite_silu_fwd_launch(asum, inv_hw, w1, b1, w2, b2, s, hpre, e, N, C, rd, (hipStream_t)stream);
+}
+
+size_t icamd_se_silu_bwd_reduce_workspace_bytes(int N, int HW, int C) { return icamd_bn_silu_squeeze_workspace_bytes(N, HW, C); }
+
+int icamd_se_silu_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift, float* de, int N, int HW, int C,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (dout == nullptr || y == nullptr || scale == nullptr || shift == nullptr || de == nullptr || workspace == nullptr || N <= 0 ||
+      HW <= 0 || C <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_silu_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  if (workspace_bytes < icamd_silu_rowsum_bytes(N, HW, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work(4.0 * N * HW * C + 4.0 * N * C);
+  return icamd_silu_rowsum_launch((const bf16_t*)dout, (const bf16_t*)y, scale, shift, de, N, HW, C, (float*)workspace,
+                                  (hipStream_t)stream);
+}
+
+int icamd_se_excite_silu_bwd(const float* de, const float* s, const float* hpre, const float* e, const float* w1, const float* w2,
+                             float* dw1, float* db1, float* dw2, float* db2, float* dsn, int N, int C, int rd, float inv_hw,
+                             int accumulate, void* stream) {
+  if (de == nullptr || s == nullptr || hpre == nullptr || e == nullptr || w1 == nullptr || w2 == nullptr || dw1 == nullptr ||
+      db1 == nullptr || dw2 == nullptr || db2 == nullptr || dsn == nullptr || N <= 0 || C <= 0 || rd <= 0)
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_silu_shape_ok(N, 1, C, rd)) return ICAMD_ERR_UNSUPPORTED;
+  ProfScope _prof(PC_MISC, stream);
+  _prof.work(4.0 * N * (5.0 * C + rd) + 16.0 * C * rd, 8.0 * N * C * rd);
+  return icamd_se_excite_silu_bwd_launch(de, s, hpre, e, w1, w2, dw1, db1, dw2, db2, dsn, N, C, rd, inv_hw, accumulate,
+                                         (hipStream_t)stream);
+}
+
+// the workspace of icamd_bn_bwd over N * HW rows: the same reduce pass geometry, the same finalize kernel
+size_t icamd_bn_bwd_silu_workspace_bytes(int N, int HW, int C) {
+  return icamd_silu_shape_ok(N, HW, C, 1) ? icamd_bn_bwd_workspace_bytes((long long)N * HW, C) : 0;
+}
+
+int icamd_bn_bwd_silu(const void* dout, const void* y, const float* mean, const float* invstd, const float* scale, const float* shift,
+                      const float* e, const float* dsn, float* dgamma, float* dbeta, void* dy, int N, int HW, int C, int accumulate,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (dout == nullptr || y == nullptr || mean == nullptr || invstd == nullptr || scale == nullptr || shift == nullptr ||
+      dgamma == nullptr || dbeta == nullptr || dy == nullptr || workspace == nullptr || N <= 0 || HW <= 0 || C <= 0 ||
+      (e == nullptr) != (dsn == nullptr))
+    return ICAMD_ERR_BAD_ARG;
+  if (!icamd_silu_shape_ok(N, HW, C, 1)) return ICAMD_ERR_UNSUPPORTED;
+  const long long rows = (long long)N * HW;
+  if (workspace_bytes < icamd_bn_bwd_workspace_bytes(rows, C)) return ICAMD_ERR_WORKSPACE;
+  ProfScope _prof(PC_BN_BWD, stream);
+  _prof.work((double)rows * C * (2 * 4 + 2) + (e ? 16.0 * N * C : 0.0));
+  const ReduceWs w = reduce_ws(workspace, C, bn_bwd_blocks(rows, C), 2);
+  return icamd_bn_bwd_silu_launch((const bf16_t*)dout, (const bf16_t*)y, mean, invstd, scale, shift, e, dsn, dgamma, dbeta, (bf16_t*)dy,
+                                  N, HW, C, accumulate, w.part, w.chunks, w.scratch, (hipStream_t)stream);
+}
+
 int icamd_maxpool3x3s2_fwd(const void* x, void* out, uint8_t* argmax, int N, int IH, int IW, int C, void* stream) {
   ProfScope _prof(PC_POOL, stream);
   _prof.work((double)N * IH * IW * C * (2 + 0.75));

@@ -434,6 +434,31 @@ int icamd_bn_bwd_relu6_launch(const bf16_t* dout, const bf16_t* y, const float* 
                               const float* shift, float* dgamma, float* dbeta, bf16_t* dy, long long rows, int C, int accumulate,
                               float* part, double* chunks, float* c1c2, hipStream_t s);
 
+// EfficientNet class: depthwise 5x5 (pad 2, stride 1 / 2), BatchNorm + SiLU and the MBConv squeeze-and-excitation (dwconv5x5.hip)
+bool icamd_dwconv5_ok(int N, int H, int W, int C, int stride);   // C % 8 == 0, stride 1 or 2, grids below 2^31 workgroups
+long long icamd_dwconv5_stats_rows_cxx(int N, int H, int W, int C, int stride);
+long long icamd_dwconv5_wgrad_rows(int N, int H, int W, int C, int stride);
+int icamd_dwconv5_fwd_launch(const bf16_t* x, const bf16_t* w, bf16_t* y, float* stats, int N, int H, int W, int C, int stride,
+                             int flip, hipStream_t s);
+int icamd_dwconv5_dgrad_launch(const bf16_t* dy, const bf16_t* w, bf16_t* dx, int N, int H, int W, int C, int stride, hipStream_t s);
+int icamd_dwconv5_wgrad_launch(const bf16_t* x, const bf16_t* dy, float* part, float* dw, int N, int H, int W, int C, int stride,
+                               int accumulate, hipStream_t s);
+bool icamd_silu_shape_ok(int N, int HW, int C, int rd);          // C % 8 == 0, C <= 4096, 1 <= rd <= 256
+void icamd_silu_plan(int N, int HW, int* S, int* rps);
+size_t icamd_silu_rowsum_bytes(int N, int HW, int C);
+int icamd_bn_apply_silu_launch(const bf16_t* y, const float* scale, const float* shift, const float* gate, bf16_t* out, int N, int HW,
+                               int C, hipStream_t s);
+int icamd_silu_rowsum_launch(const bf16_t* dout, const bf16_t* y, const float* scale, const float* shift, float* out, int N, int HW,
+                             int C, float* part, hipStream_t s);
+int icamd_se_excite_silu_fwd_launch(const float* asum, float inv_hw, const float* w1, const float* b1, const float* w2, const float* b2,
+                                    float* s_out, float* hpre, float* e, int N, int C, int rd, hipStream_t s);
+int icamd_se_excite_silu_bwd_launch(const float* de, const float* sv, const float* hpre, const float* e, const float* w1,
+                                    const float* w2, float* dw1, float* db1, float* dw2, float* db2, float* dsn, int N, int C, int rd,
+                                    float inv_hw, int accumulate, hipStream_t s);
+int icamd_bn_bwd_silu_launch(const bf16_t* dout, const bf16_t* y, const float* mean, const float* invstd, const float* scale,
+                             const float* shift, const float* gate, const float* dsn, float* dgamma, float* dbeta, bf16_t* dy, int N,
+                             int HW, int C, int accumulate, float* part, double* chunks, float* c1c2, hipStream_t s);
+
 // ConvNeXt V2: global response normalisation (grn.hip)
 bool icamd_grn_ok(int N, long long HW, int C);
 void icamd_grn_plan(int N, int HW, int C, int* S, int* rps, int* B, int* rpb);

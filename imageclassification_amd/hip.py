@@ -223,6 +223,23 @@ _SIGNATURES_ADDED = {
     "icamd_bn_apply_relu6": (c_int, [_P, _P, _P, _P, c_longlong, c_int, _P]),
     "icamd_bn_bwd_relu6_workspace_bytes": (c_size_t, [c_longlong, c_int]),
     "icamd_bn_bwd_relu6": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_longlong, c_int, c_int, _P, c_size_t, _P]),
+    # EfficientNet class (csrc/dwconv5x5.hip): depthwise 5x5 pad 2 stride 1 / 2 over NHWC bf16 (C % 8 == 0, no on-load form);
+    # BatchNorm + SiLU apply (optionally gated), per-sample sums and backward; the excitation of an MBConv block (SiLU inside)
+    "icamd_dwconv5_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_dwconv5_stats_rows": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_dwconv5_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "icamd_dwconv5_dgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "icamd_dwconv5_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "icamd_dwconv5_wgrad": (c_int, [_P, _P, _P, c_int, _P, c_size_t, c_int, c_int, c_int, c_int, c_int, _P]),
+    "icamd_bn_apply_silu": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "icamd_bn_silu_squeeze_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "icamd_bn_silu_squeeze": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "icamd_se_excite_silu_fwd": (c_int, [_P, c_float, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "icamd_se_silu_bwd_reduce_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "icamd_se_silu_bwd_reduce": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "icamd_se_excite_silu_bwd": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_float, c_int, _P]),
+    "icamd_bn_bwd_silu_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "icamd_bn_bwd_silu": (c_int, [_P] * 11 + [c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_ADDED)

@@ -367,6 +367,57 @@ int icamd_bn_bwd_relu6(const void* dout, const void* y, const float* mean, const
                        float* dgamma, float* dbeta, void* dy, long long rows, int C, int accumulate, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* EfficientNet class (csrc/dwconv5x5.hip): depthwise 5x5 convolution, pad 2, stride 1 or 2.
+ *   x NHWC bf16 [N,H,W,C] (an activated tensor: there is no on-load form), y / dy [N,OH,OW,C] with OH = (H - 1) / stride + 1, w bf16
+ *   [5][5][C] (tap-major shadow of the [C,1,5,5] parameter), fp32 accumulation, every stored tensor rounded to bf16 once, no atomics
+ *   (the same bits on every launch), 64-bit addressing.
+ * _supported: C % 8 == 0, stride 1 or 2, any H, W >= 1 (also below 5); a shape whose launch grid would pass 2^31 workgroups is
+ *   refused.  Elsewhere every entry returns ICAMD_ERR_UNSUPPORTED before anything is written and _supported, _stats_rows and
+ *   _workspace_bytes return 0.
+ * fwd: stats (optional) fp32 [_stats_rows][2][C], partial sums of the rounded y and of its square, every row written: the partial
+ *   rows icamd_bn_train_finalize consumes.
+ * dgrad: dx [N,H,W,C], every element written exactly once, in one launch (stride 2: a gather).
+ * wgrad: dw fp32 [5][5][C] (+)= sum over pixels dy * shifted x. */
+int icamd_dwconv5_supported(int N, int H, int W, int C, int stride);
+int icamd_dwconv5_stats_rows(int N, int H, int W, int C, int stride);
+int icamd_dwconv5_fwd(const void* x, const void* w, void* y, float* stats, int N, int H, int W, int C, int stride, void* stream);
+int icamd_dwconv5_dgrad(const void* dy, const void* w, void* dx, int N, int H, int W, int C, int stride, void* stream);
+size_t icamd_dwconv5_wgrad_workspace_bytes(int N, int H, int W, int C, int stride);
+int icamd_dwconv5_wgrad(const void* x, const void* dy, float* dw, int accumulate, void* workspace, size_t workspace_bytes, int N, int H,
+                        int W, int C, int stride, void* stream);
+/* BatchNorm + SiLU and the squeeze-and-excitation of an MBConv block (csrc/dwconv5x5.hip).  y bf16 [N][HW][C], C % 8 == 0,
+ * C <= 4096, 1 <= rd <= 256; elsewhere every entry returns an error before anything is written and the size queries return 0.
+ *   z = fma(y, scale[c], shift[c]) in fp32;  a = bf16(z / (1 + exp(-z)))   (finite for |z| <= 2^20, NaN stays NaN)
+ *   silu'(z) = sigma(z) (1 + z (1 - sigma(z))), recomputed from y: no mask bits and no stored activation
+ * bn_apply_silu: out = a (e == NULL) or bf16(float(a) * e[n][c]) with the gate e fp32 [N][C]: a gated block never stores a.
+ * bn_silu_squeeze: asum[n][c] = sum_hw float(a), fp32, without writing a.
+ * se_excite_silu_fwd: s = asum * inv_hw; hpre = W1 s + b1; e = sigmoid(W2 silu(hpre) + b2).  All fp32; W1 [rd][C], W2 [C][rd]
+ *   (torch layout); s [N][C], hpre [N][rd], e [N][C] are kept for the backward.
+ * se_silu_bwd_reduce: de[n][c] = sum_hw dout * float(a), dout the gradient of the gated tensor.
+ * se_excite_silu_bwd: dp2 = de e (1 - e); dW2 = dp2^T silu(hpre), db2 = sum_n dp2; dh = (dp2 W2) silu'(hpre); dW1 = dh^T s,
+ *   db1 = sum_n dh; dsn[n][c] = (dh W1) inv_hw, the amount added to every pixel's gradient of a.  Parameter gradients (+)= under
+ *   `accumulate`.
+ * bn_bwd_silu: the BatchNorm backward behind the SiLU.  Upstream gradient: dout (e == NULL and dsn == NULL) or dout * e[n][c] +
+ *   dsn[n][c] (both given).  A reduce and an apply pass around icamd_bn_bwd's finalize kernel; dgamma / dbeta fp32 [C], (+)= under
+ *   `accumulate`; workspace as icamd_bn_bwd's over N * HW rows (zero-filled once). */
+int icamd_bn_apply_silu(const void* y, const float* scale, const float* shift, const float* e, void* out, int N, int HW, int C,
+                        void* stream);
+size_t icamd_bn_silu_squeeze_workspace_bytes(int N, int HW, int C);
+int icamd_bn_silu_squeeze(const void* y, const float* scale, const float* shift, float* asum, int N, int HW, int C, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int icamd_se_excite_silu_fwd(const float* asum, float inv_hw, const float* w1, const float* b1, const float* w2, const float* b2,
+                             float* s, float* hpre, float* e, int N, int C, int rd, void* stream);
+size_t icamd_se_silu_bwd_reduce_workspace_bytes(int N, int HW, int C);
+int icamd_se_silu_bwd_reduce(const void* dout, const void* y, const float* scale, const float* shift, float* de, int N, int HW, int C,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int icamd_se_excite_silu_bwd(const float* de, const float* s, const float* hpre, const float* e, const float* w1, const float* w2,
+                             float* dw1, float* db1, float* dw2, float* db2, float* dsn, int N, int C, int rd, float inv_hw,
+                             int accumulate, void* stream);
+size_t icamd_bn_bwd_silu_workspace_bytes(int N, int HW, int C);
+int icamd_bn_bwd_silu(const void* dout, const void* y, const float* mean, const float* invstd, const float* scale, const float* shift,
+                      const float* e, const float* dsn, float* dgamma, float* dbeta, void* dy, int N, int HW, int C, int accumulate,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ViT token plumbing: tokens[b][0] = cls + pos[0], tokens[b][1+i] = patches[b][i] + pos[1+i] (bf16 out, fp32 parameters);
  * batch_sum: out[j] (+)= sum_b x[b*stride + j] (cls_token / pos_embed gradients); strided row copies; zero fill. */
 int icamd_vit_tokens_fwd(const void* patches, const float* cls_token, const float* pos_embed, void* tokens, int B, int T, int C,

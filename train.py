@@ -29,6 +29,7 @@ from imageclassification_amd.convnext import CONFIGS as CNX_CONFIGS, ConvNeXt
 from imageclassification_amd.swin import (CONFIGS as SWIN_CONFIGS, CONFIGS_W12 as SWIN_CONFIGS_W12, NATIVE_SIZE as SWIN_NATIVE_SIZE,
                                           SwinTransformer)
 from imageclassification_amd.mobilenet import CONFIGS as MBV2_CONFIGS, MobileNetV2
+from imageclassification_amd.efficientnet import CONFIGS as EFFNET_CONFIGS, EfficientNet
 from imageclassification_amd.optim_factory import create_optimizer
 from imageclassification_amd.utils import NativeScalerWithGradNormCount as NativeScaler
 
@@ -104,7 +105,10 @@ def create_model(name, num_classes, input_size=None, drop_path=0.0):
     if name in MBV2_CONFIGS:
         # no stochastic depth in the family: the reference passes --drop_path to convnext* / efficientvit* only (train.py:189-192)
         return MobileNetV2(name, num_classes)
-    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS) + sorted(SWIN_CONFIGS_W12) + sorted(MBV2_CONFIGS)})")
+    if name in EFFNET_CONFIGS:
+        # no dropout and no stochastic depth: timm's defaults for the family are 0 and --drop_path does not reach it (as above)
+        return EfficientNet(name, num_classes)
+    raise ValueError(f"model '{name}' is not built for the MI355X path yet (available: {sorted(ARCHS) + sorted(VIT_CONFIGS) + sorted(CNX_CONFIGS) + sorted(SWIN_CONFIGS) + sorted(SWIN_CONFIGS_W12) + sorted(MBV2_CONFIGS) + sorted(EFFNET_CONFIGS)})")
 
 
 def main(args):
