@@ -1,5 +1,5 @@
-"""What the BatchNorm families (nets.py's ResNets, mobilenet.py's MobileNetV2) share between ArenaModel and the model, defined once:
-the convolution and BatchNorm records, their slices of the arenas, the running statistics in the state_dict, the saved batch
+"""What the BatchNorm families (nets.py's ResNets; mobilenet.py's MobileNetV2 and efficientnet.py's EfficientNet, through mbconv.py)
+share between ArenaModel and the model, defined once: the convolution and BatchNorm records, their slices of the arenas, the running statistics in the state_dict, the saved batch
 statistics, the BatchNorm coefficients of a forward pass, and the head (global average pool + classifier).
 
 A model derives from BatchNormModel, builds its records (`convs`, `bns`, the classifier `fc`), hands them to `_layout_arenas` in

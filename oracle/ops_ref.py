@@ -589,11 +589,106 @@ def bn_relu6(x, scale, shift):
     return bf16_round(fma32(x, scale, shift).clamp(0.0, 6.0))
 
 
-def dwconv3_ref(a_nhwc, w_c33, dy_nhwc, stride):
-    """F.conv2d(groups=C, padding=1) in fp64 on the (activated, rounded) input and autograd: y and dx on the bf16 grid, dw [C,3,3]"""
+def dwconv_ref(a_nhwc, w_ckk, dy_nhwc, stride, k):
+    """F.conv2d(groups=C, padding=k // 2) in fp64 on the (activated, rounded) input and autograd: y and dx on the bf16 grid, dw [C,k,k]"""
     C = a_nhwc.shape[-1]
     a = nhwc_to_nchw(a_nhwc.double()).requires_grad_(True)
-    w = w_c33.double().reshape(C, 1, 3, 3).clone().requires_grad_(True)
-    y = F.conv2d(a, w, None, stride, 1, 1, C)
+    w = w_ckk.double().reshape(C, 1, k, k).clone().requires_grad_(True)
+    y = F.conv2d(a, w, None, stride, k // 2, 1, C)
     y.backward(nhwc_to_nchw(dy_nhwc.double()))
-    return bf16_round(nchw_to_nhwc(y.detach())), bf16_round(nchw_to_nhwc(a.grad)), w.grad.reshape(C, 3, 3)
+    return bf16_round(nchw_to_nhwc(y.detach())), bf16_round(nchw_to_nhwc(a.grad)), w.grad.reshape(C, k, k)
+
+
+def dwconv3_ref(a_nhwc, w_c33, dy_nhwc, stride):
+    return dwconv_ref(a_nhwc, w_c33, dy_nhwc, stride, 3)
+
+
+def dwconv5_ref(x_nhwc, w_c55, dy_nhwc, stride):
+    return dwconv_ref(x_nhwc, w_c55, dy_nhwc, stride, 5)
+
+
+# ---- EfficientNet pieces (csrc/dwconv5x5.hip): BatchNorm + SiLU and the MBConv squeeze-and-excitation, in fp64 -------------------
+def silu64(z):
+    z = z.double()
+    return z * torch.sigmoid(z)
+
+
+def silu_grad64(z):
+    sg = torch.sigmoid(z.double())
+    return sg * (1.0 + z.double() * (1.0 - sg))
+
+
+def bn_silu(y, scale, shift):
+    """a = bf16(silu(fma32(y, scale, shift))), the silu in fp64 on the kernel's fp32 z: what icamd_bn_apply_silu stores"""
+    return bf16_round(silu64(fma32(y, scale, shift)).float())
+
+
+def boundary_share(y, scale, shift):
+    """share of the elements whose fp64 silu(z) sits within 2^-13 (relative: 8 fp32 ulps) of the midpoint between two bf16 values: where
+    a kernel whose fp32 silu is a few ulps off may round the other way"""
+    v = silu64(fma32(y, scale, shift))
+    lo = v.float().view(torch.int32).bitwise_and(-65536).view(torch.float32).double()        # truncated to the bf16 grid
+    step = torch.exp2(torch.floor(torch.log2(v.abs().clamp_min(1e-300))) - 7)
+    mid = lo + torch.sign(v) * step / 2
+    return float(((v - mid).abs() <= v.abs() * 2.0 ** -13).float().mean())
+
+
+def excite_fwd(asum, inv_hw, w1, b1, w2, b2):
+    """fp64: s, hpre, e"""
+    s = asum.double() * inv_hw
+    hpre = s @ w1.double().t() + b1.double()
+    e = torch.sigmoid(silu64(hpre) @ w2.double().t() + b2.double())
+    return s, hpre, e
+
+
+def excite_bwd(de, s, hpre, e, w1, w2, inv_hw):
+    """fp64, the kernels' form: dw1, db1, dw2, db2, dsn"""
+    de, s, hpre, e, w1, w2 = (t.double() for t in (de, s, hpre, e, w1, w2))
+    dp2 = de * e * (1 - e)
+    dw2, db2 = dp2.t() @ silu64(hpre), dp2.sum(0)
+    dh = (dp2 @ w2) * silu_grad64(hpre)
+    dw1, db1 = dh.t() @ s, dh.sum(0)
+    return dw1, db1, dw2, db2, (dh @ w1) * inv_hw
+
+
+def bn_bwd_silu(dout, y, mean, invstd, scale, shift, e=None, dsn=None, fp32_z=True):
+    """fp64, the kernels' two passes: g = upstream * silu'(z); (dgamma, dbeta) = (sum g xhat, sum g); dy = scale (g - mean g - xhat mean
+    (g xhat)).  dout, y [N][HW][C]; e, dsn [N][C]"""
+    z = fma32(y, scale, shift).double() if fp32_z else y.double() * scale.double() + shift.double()
+    up = dout.double() if e is None else dout.double() * e.double()[:, None, :] + dsn.double()[:, None, :]
+    g = up * silu_grad64(z)
+    xhat = (y.double() - mean.double()) * invstd.double()
+    M = y.shape[0] * y.shape[1]
+    dbeta, dgamma = g.sum((0, 1)), (g * xhat).sum((0, 1))
+    dy = scale.double() * (g - dbeta / M - xhat * (dgamma / M))
+    return dy, dgamma, dbeta
+
+
+def se_block_two_pass(y, gamma, beta, w1, b1, w2, b2, dout, eps=1e-5):
+    """BatchNorm (batch statistics) + SiLU + SE gate and its backward in fp64 without rounding, in the order the kernels take: squeeze
+    pass, excite, apply pass; gate-gradient pass, excite backward, reduce pass, apply pass.  y, dout [N][HW][C]"""
+    y = y.double()
+    N, HW, C = y.shape
+    mean, var = y.mean((0, 1)), y.var((0, 1), unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + eps)
+    scale = gamma.double() * invstd
+    shift = beta.double() - mean * scale
+    a = silu64(y * scale + shift)
+    s, hpre, e = excite_fwd(a.sum(1), 1.0 / HW, w1, b1, w2, b2)
+    out = a * e[:, None, :]
+    de = (dout.double() * a).sum(1)
+    dw1, db1, dw2, db2, dsn = excite_bwd(de, s, hpre, e, w1, w2, 1.0 / HW)
+    dy, dgamma, dbeta = bn_bwd_silu(dout, y, mean, invstd, scale, shift, e, dsn, fp32_z=False)
+    return out, {"y": dy, "gamma": dgamma, "beta": dbeta, "w1": dw1, "b1": db1, "w2": dw2, "b2": db2}
+
+
+def se_block_autograd(y, gamma, beta, w1, b1, w2, b2, dout, eps=1e-5):
+    """the plain expression under fp64 autograd"""
+    t = {k: v.double().clone().requires_grad_(True) for k, v in (("y", y), ("gamma", gamma), ("beta", beta), ("w1", w1), ("b1", b1),
+                                                                 ("w2", w2), ("b2", b2))}
+    N, HW, C = y.shape
+    a = F.silu(F.batch_norm(t["y"].reshape(N * HW, C), None, None, t["gamma"], t["beta"], True, 0.0, eps)).reshape(N, HW, C)
+    gate = torch.sigmoid(F.linear(F.silu(F.linear(a.mean(1), t["w1"], t["b1"])), t["w2"], t["b2"]))
+    out = a * gate[:, None, :]
+    (out * dout.double()).sum().backward()
+    return out.detach(), {k: v.grad for k, v in t.items()}

@@ -1,6 +1,7 @@
-"""What the depthwise 3x3 / ReLU6 BatchNorm tests share: the launch geometry of csrc/dwconv3x3.hip mirrored in Python (so that a
-test can say which loop a shape drives through more than one trip), seeded operands with the clamp shares the tests require, and
-thin runners of the entries.  Importing this module needs no GPU."""
+"""What the depthwise 3x3 / 5x5 and ReLU6 BatchNorm tests share: the launch geometry of csrc/dwconv3x3.hip and csrc/dwconv5x5.hip
+mirrored in Python (one geometry: the two differ in the taps of a kernel row alone; so that a test can say which loop a shape drives
+through more than one trip), seeded operands (3x3: with the clamp shares the tests require), and thin runners of the 3x3 entries.
+Importing this module needs no GPU."""
 import functools
 
 import torch
@@ -9,10 +10,13 @@ import _harness
 from _harness import DEV, dev, guarded
 from oracle import ops_ref as R
 
-RS = 16                                                    # output rows per item (dwconv3x3.hip)
-# (N, H, W, C): the issue's six, then the two that drive what those do not (see trips())
+RS = 16                                                    # output rows per item (dwconv3x3.hip, dwconv5x5.hip)
+# 3x3, (N, H, W, C): the issue's six, then the two that drive what those do not (see trips())
 SHAPES = [(2, 7, 7, 24), (3, 9, 11, 48), (2, 14, 14, 144), (2, 8, 8, 528), (1, 1, 5, 16), (3, 57, 57, 96), (2100, 3, 5, 16),
           (2, 5, 5, 1344)]
+# 5x5, (N, H, W, C), each at stride 1 and 2: the issue's eight; trips(..., k=5) shows they run every loop more than once
+SHAPES5 = [(2, 2, 3, 8), (1, 1, 5, 16), (2, 7, 7, 24), (3, 9, 11, 48), (2, 14, 14, 144), (3, 37, 41, 40), (2, 5, 5, 1152),
+           (2100, 3, 5, 16)]
 
 
 def cdiv(a, b):
@@ -20,7 +24,7 @@ def cdiv(a, b):
 
 
 def geometry(N, H, W, C, stride, cap, pixels_per_row):
-    """dw3_geometry: forward (cap 2048, 16 pixels per partial row) and weight gradient (1024, 64)"""
+    """dw3_geometry and dw5_geometry, the same function: forward (cap 2048, 16 pixels per partial row) and weight gradient (1024, 64)"""
     OH, OW, cpr = (H - 1) // stride + 1, (W - 1) // stride + 1, C // 8
     cv = min(cpr, 256)
     while cpr % cv or (256 // cv) * cv < 192:
@@ -42,13 +46,14 @@ def wgrad_geometry(N, H, W, C, stride):
     return geometry(N, H, W, C, stride, 1024, 64)
 
 
-def trips(N, H, W, C, stride):
-    """trip count of every loop of dwconv3_fwd_kernel / dwconv3_wgrad_kernel whose length depends on the problem"""
+def trips(N, H, W, C, stride, k=3):
+    """trip count of every loop of dwconv{k}_fwd_kernel / dwconv{k}_wgrad_kernel whose length depends on the problem; a thread leaves
+    the k taps of a kernel row times its 8 channels in the LDS (red[256 * 24], red[256 * 40])"""
     f, w = fwd_geometry(N, H, W, C, stride), wgrad_geometry(N, H, W, C, stride)
     return {"items of a workgroup, forward": f["ipb"], "items of a workgroup, weight gradient": w["ipb"],
             "rows of a segment": min(RS, f["OH"]), "row segments": f["rowsegs"], "column groups": f["colgroups"],
             "column lanes folded per output": f["lanes"], "LDS outputs of the statistics fold (o += 256)": cdiv(f["cv"] * 16, 256),
-            "LDS outputs of a kernel row of taps (o += 256)": cdiv(w["cv"] * 24, 256), "channel slices per pixel": f["nslices"],
+            "LDS outputs of a kernel row of taps (o += 256)": cdiv(w["cv"] * 8 * k, 256), "channel slices per pixel": f["nslices"],
             "partial rows, forward": f["rows"], "partial rows, weight gradient": w["rows"]}
 
 
@@ -82,8 +87,21 @@ def case(shape, stride, onload):
     return {"x": x, "w": w, "dy": dy, "scale": scale, "shift": shift, "a": a, "y": y, "dx": dx, "dw": dw, "OH": OH, "OW": OW}
 
 
+@functools.lru_cache(maxsize=None)
+def dw5_case(shape, stride):
+    """operands and the fp64 reference of one 5x5 case, computed once"""
+    N, H, W, C = shape
+    g = torch.Generator().manual_seed(2000 + 7 * N + H + 3 * stride)
+    x = R.bf16_round(1.5 * torch.randn(N, H, W, C, generator=g))
+    w = R.bf16_round(0.2 * torch.randn(C, 5, 5, generator=g))
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    dy = R.bf16_round(torch.randn(N, OH, OW, C, generator=g))
+    y, dx, dw = R.dwconv5_ref(x, w, dy, stride)
+    return {"x": x, "w": w, "dy": dy, "y": y, "dx": dx, "dw": dw, "OH": OH, "OW": OW}
+
+
 class Runner:
-    """the entries on device tensors; outputs are guarded and every call asserts its return code"""
+    """the 3x3 entries on device tensors; outputs are guarded and every call asserts its return code"""
 
     def __init__(self, lib, shape, stride):
         self.lib, self.hip, self.shape, self.stride = lib, _harness.hip(), shape, stride

@@ -1,4 +1,5 @@
-"""Generates tests/golden/call_traces.json: one SHA-256 per case over every library call a ViT, Swin, ConvNeXt, ResNet or MobileNetV2 step makes.
+"""Generates tests/golden/call_traces.json: one SHA-256 per case over every library call a ViT, Swin, ConvNeXt, ResNet, MobileNetV2 or
+EfficientNet step makes.
 
 Run at the commit whose launches are to be pinned (no GPU needed):
     python tests/golden/make_call_traces.py
@@ -6,7 +7,7 @@ To see what moved when the test fails, write the records themselves at both comm
     python tests/golden/make_call_traces.py --dump DIR
 
 The models run on the CPU under make_arena_layouts.install_stubs plus three more replacements (`install_recorders`): the library
-records (entry, arguments) and returns 0 (a ResNet, MobileNetV2 or routed ConvNeXt case carries a table of other answers for the queries, `Case.answers`),
+records (entry, arguments) and returns 0 (a ResNet, MobileNetV2, EfficientNet or routed ConvNeXt case carries a table of other answers for the queries, `Case.answers`),
 torch.cuda.current_stream is a stand-in whose stream is 0, and streams.SideLane is a
 lane of the same interface that runs a launch with stream 1 when it is enabled (0 otherwise) and leaves a record for every
 before_write that meets a pending read and for every join.  grad_ready_hook records (lo, hi, events).  A case is: construct at
@@ -57,8 +58,10 @@ MODELS = {
 RESNETS = ("resnet50", "resnet18", "resnext50_32x4d", "seresnet50", "resnet50d", "resnet18d", "seresnext26d_32x4d")
 MODELS.update({arch: ("nets", "ResNet", {"arch": arch}, 64) for arch in RESNETS})
 MODELS["mobilenetv2_test"] = ("mobilenet", "MobileNetV2", {"arch": "mobilenetv2_test"}, 64)
+MODELS.update({arch: ("efficientnet", "EfficientNet", {"arch": arch}, 64) for arch in ("efficientnet_test", "efficientnet_b1")})
 # the models whose seed-0 weights the fixture keeps
-STATE_MODELS = ("vit_tiny_test", "swin_test", "swin_test_w12", "convnext_test", "resnet50", "seresnext26d_32x4d", "mobilenetv2_test")
+STATE_MODELS = ("vit_tiny_test", "swin_test", "swin_test_w12", "convnext_test", "resnet50", "seresnext26d_32x4d", "mobilenetv2_test",
+                "efficientnet_test")
 
 # One case.  more: further constructor arguments; masks: drop-path masks per block (None: none injected); env: environment
 # (None: unset).  A ResNet or routed ConvNeXt case also has answers = (what a *_supported query returns, {entry: another answer})
@@ -129,6 +132,10 @@ CASES = {
     "seresnext26d_32x4d/unfolded": _resnet("seresnext26d_32x4d", attrs={"fold_eval": False}),
     "mobilenetv2_test/default": _mobilenet(False),
     "mobilenetv2_test/onload": _mobilenet(True),
+    # EfficientNet has no switch; every query answers as for a ResNet case.  b1 is the one configuration whose blocks.0.1 is a
+    # depthwise-separable block with a skip (its data gradient is added to the skip's by icamd_bn_apply)
+    "efficientnet_test/default": Case("efficientnet_test", answers=(1, {})),
+    "efficientnet_b1/ds_skip": Case("efficientnet_b1", answers=(1, {})),
 }
 
 TRACE = []          # the records of the case that is running
@@ -249,8 +256,9 @@ def state_record(model):
 
 # |weight| stays below this (0.25 where a model is not listed).  A ResNet's filters are Kaiming-normal with std sqrt(2 / (cout k k)),
 # at most 0.354 (the 16-row first SE convolution): 4.0 is more than 11 standard deviations.  MobileNetV2's depthwise filters are
-# N(0, sqrt(2 / 9)) = 0.471: 4.0 is 8.5 of them
-STATE_BOUND = {"resnet50": 4.0, "seresnext26d_32x4d": 4.0, "mobilenetv2_test": 4.0}
+# N(0, sqrt(2 / 9)) = 0.471: 4.0 is 8.5 of them.  EfficientNet's widest draw is the conv_reduce of a squeeze-and-excitation whose
+# reduced width is 2 (blocks.1.0 of efficientnet_test: fan_out = 2, std 1.0): 8.0 is 8 of them
+STATE_BOUND = {"resnet50": 4.0, "seresnext26d_32x4d": 4.0, "mobilenetv2_test": 4.0, "efficientnet_test": 8.0}
 
 
 def state_tol(numel, bound=0.25):

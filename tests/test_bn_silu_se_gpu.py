@@ -1,5 +1,5 @@
 """The BatchNorm + SiLU and MBConv squeeze-and-excitation entries of csrc/dwconv5x5.hip, each against the fp64 reference of
-tests/_efficientnet_ref.py on the same operands (every entry takes the REFERENCE's arrays as inputs, so no error is carried from one
+oracle/ops_ref.py on the same operands (every entry takes the REFERENCE's arrays as inputs, so no error is carried from one
 entry into the next).
 
   icamd_bn_apply_silu       equal to bf16(silu64(fma32(y, scale, shift))) but for at most 1e-3 of the elements, those one bf16 step off
@@ -15,7 +15,6 @@ c += 256 (C >= 1152), samples per wave in the parameter-gradient kernel (N = 5 >
 import pytest
 import torch
 
-import _efficientnet_ref as E
 import _harness
 from _harness import DEV, dev, digest, guarded, intact, sync
 from _harness import lib  # noqa: F401
@@ -135,8 +134,8 @@ def to_device(o):
 def check_all(lib, o, N, HW, C, rd, tag):
     """every entry of the section on the operands `o`, each fed the reference's arrays"""
     y, dout, scale, shift = o["y"], o["dout"], o["scale"], o["shift"]
-    a = E.bn_silu(y, scale, shift)
-    print(f"{tag}: {E.boundary_share(y, scale, shift):.2e} of the elements within 8 fp32 ulps of a bf16 rounding boundary")
+    a = R.bn_silu(y, scale, shift)
+    print(f"{tag}: {R.boundary_share(y, scale, shift):.2e} of the elements within 8 fp32 ulps of a bf16 rounding boundary")
     assert bool(torch.isfinite(a).all())
     # forward: ungated apply, squeeze, excite, gated apply
     got_a = run_apply(lib, o, N, HW, C)
@@ -145,7 +144,7 @@ def check_all(lib, o, N, HW, C, rd, tag):
     got_asum = run_rowsum(lib, o, N, HW, C, False)
     print(f"{tag}: asum rel_l2 {R.rel_l2(got_asum.cpu(), asum):.2e}")
     assert R.rel_l2(got_asum.cpu(), asum) <= 1e-4
-    s, hpre, e = E.excite_fwd(asum, 1.0 / HW, o["w1"], o["b1"], o["w2"], o["b2"])
+    s, hpre, e = R.excite_fwd(asum, 1.0 / HW, o["w1"], o["b1"], o["w2"], o["b2"])
     gs, gh, ge = run_excite_fwd(lib, f32(asum), o, N, HW, C, rd)
     for name, g, r in (("s", gs, s), ("hpre", gh, hpre), ("e", ge, e)):
         print(f"{tag}: {name} rel_l2 {R.rel_l2(g.cpu(), r):.2e}")
@@ -160,7 +159,7 @@ def check_all(lib, o, N, HW, C, rd, tag):
     print(f"{tag}: de rel_l2 {R.rel_l2(got_de.cpu(), de):.2e}")
     assert R.rel_l2(got_de.cpu(), de) <= 1e-4
     s32, h32, de32 = s.float(), hpre.float(), de.float()
-    refs = E.excite_bwd(de32, s32, h32, e32, o["w1"], o["w2"], 1.0 / HW)
+    refs = R.excite_bwd(de32, s32, h32, e32, o["w1"], o["w2"], 1.0 / HW)
     for base in (None, 1.0):
         got = run_excite_bwd(lib, f32(de32), f32(s32), f32(h32), f32(e32), o, N, HW, C, rd, base)
         for name, g, r in zip(("dw1", "db1", "dw2", "db2", "dsn"), got, refs):
@@ -170,7 +169,7 @@ def check_all(lib, o, N, HW, C, rd, tag):
     dsn32 = refs[4].float()
     for gate in (None, (e32, dsn32)):
         ge_, gd_ = (None, None) if gate is None else (f32(gate[0]), f32(gate[1]))
-        rdy, rdg, rdb = E.bn_bwd_silu(dout, y, o["mean"], o["invstd"], scale, shift, *(gate or ()))
+        rdy, rdg, rdb = R.bn_bwd_silu(dout, y, o["mean"], o["invstd"], scale, shift, *(gate or ()))
         rdy = R.bf16_round(rdy.float())
         ws = None
         for acc, base in ((0, 0.0), (1, 1.5)):

@@ -1,4 +1,5 @@
-"""The library calls of a ViT, Swin, ConvNeXt (V1 folded and unfolded, V2), ResNet (nets.py) and MobileNetV2 training step, without a GPU: every launch of construct / pack / forward / backward /
+"""The library calls of a ViT, Swin, ConvNeXt (V1 folded and unfolded, V2), ResNet (nets.py), MobileNetV2 and EfficientNet training step,
+without a GPU: every launch of construct / pack / forward / backward /
 accumulating backward / eval forward (ResNet: twice) / reload -- entry, arguments, buffers, stream, order, side-lane waits and gradient-hook calls --
 is the recorded one (tests/golden/call_traces.json, written by tests/golden/make_call_traces.py, whose docstring states what a
 record holds), and a seed still gives the weights it gave.
@@ -168,6 +169,48 @@ def test_the_mobilenet_cases_take_the_paths_they_are_there_for(recorders, case_i
         stored = {t.data_ptr() for b in ws["blocks"] for t in (b["a2"],)} | {ws["ah"].data_ptr()}
         assert {r[2][3] for r in applies} == stored          # every apply left is one whose output the step stores
         assert all(launches[k][2][1] and launches[k][2][2] for k in dw)
+
+
+EFFICIENTNET_CASES = ("efficientnet_test/default", "efficientnet_b1/ds_skip")
+SE_SILU_ENTRIES = {"forward": ("icamd_bn_silu_squeeze", "icamd_se_excite_silu_fwd"),
+                   "backward": ("icamd_se_silu_bwd_reduce", "icamd_se_excite_silu_bwd")}
+
+
+def test_efficientnet_cases_are_the_listed_ones():
+    assert set(EFFICIENTNET_CASES) == {c for c in G.CASES if G.MODELS[G.CASES[c].model][0] == "efficientnet"}
+
+
+@pytest.mark.parametrize("case_id", EFFICIENTNET_CASES)
+def test_the_efficientnet_cases_take_the_paths_they_are_there_for(recorders, case_id):
+    """One stream.  The squeeze and the excitation run once per block in each of the two forwards, the gate-gradient reduce and the
+    excitation backward once per block in each of the two backwards; nothing is activated by ReLU6.  efficientnet_test has depthwise
+    layers of both filter sizes.  efficientnet_b1's blocks.0.1 is a depthwise-separable block with a skip: each backward adds its
+    data gradient to the skip's with the one icamd_bn_apply a backward makes, the only one whose addend is not NULL."""
+    seen = []
+    G.run_case(case_id, lambda k, v: recorders.delenv(k, raising=False) if v is None else recorders.setenv(k, v),
+               setattr_fn=recorders.setattr, observer=lambda model, held, x: seen.append(model))
+    blocks = len(seen[0].blocks)
+    launches = [r for r in G.TRACE if r[0].startswith("icamd_") and not r[0].endswith(("_bytes", "_supported", "_rows"))]
+    assert {r[2][-1] for r in launches} == {0} and not any(r[0].startswith("lane.") for r in G.TRACE)
+    names = [r[0] for r in launches]
+    assert "icamd_bn_apply_relu6" not in names and "icamd_bn_bwd_relu6" not in names
+    for phases, entries in ((("forward", "eval_forward"), SE_SILU_ENTRIES["forward"]),
+                            (("backward", "backward_accumulate"), SE_SILU_ENTRIES["backward"])):
+        for entry in entries:
+            assert names.count(entry) == 2 * blocks
+            assert all([r[0] for r in G.phase_records(ph)].count(entry) == blocks for ph in phases)
+    skips = [[r for r in G.phase_records(ph) if r[0] == "icamd_bn_apply"] for ph in ("backward", "backward_accumulate")]
+    if case_id == "efficientnet_test/default":
+        assert blocks == 6 and skips == [[], []]
+        for op in ("fwd", "dgrad", "wgrad"):
+            assert names.count(f"icamd_dwconv3_{op}") > 0 and names.count(f"icamd_dwconv5_{op}") > 0
+            assert names.count(f"icamd_dwconv3_{op}") + names.count(f"icamd_dwconv5_{op}") == 2 * blocks
+    else:
+        assert blocks == 23 and seen[0].blocks[1].kind == "ds" and seen[0].blocks[1].residual
+        assert [len(s) for s in skips] == [1, 1] and all(s[0][2][3] is not None for s in skips)      # (y, scale, shift, addend, ...)
+        # the forward's applies: one per block, the addend there exactly for the blocks with a skip
+        fwd = [r[2][3] is not None for r in G.phase_records("forward") if r[0] == "icamd_bn_apply"]
+        assert fwd == [b.residual for b in seen[0].blocks]
 
 
 FOLDED = ["icamd_layerscale_fold", "icamd_layerscale_param_grads", "icamd_conv2d_dgrad_gelu"]

@@ -3,7 +3,7 @@ and with the on-load form a = relu6(x * scale + shift), at stride 1 and 2.
 
 The shapes: odd sizes, OH = ceil(H / 2), a single row, C % 16 != 0 (24), C % 32 != 0 (48, 144, 528), C above 512, borders between
 images.  The loops of dwconv3_fwd_kernel / dwconv3_wgrad_kernel whose trip count depends on the problem, and the shape that runs
-each more than once (tests/_dwconv3.py::trips mirrors the geometry; tests/test_mobilenetv2_cpu.py asserts these counts):
+each more than once (tests/_dwconv.py::trips mirrors the geometry; tests/test_mobilenetv2_cpu.py asserts these counts):
 
   rows of a segment (oh), row segments, column groups          (3, 57, 57, 96): 16 rows, 4 segments, 3 groups of 21 columns
   column lanes folded per output (l < lanes)                   every shape: 3 (C = 528, 1344) .. 128 (C = 16)
@@ -16,7 +16,7 @@ each more than once (tests/_dwconv3.py::trips mirrors the geometry; tests/test_m
 import pytest
 import torch
 
-import _dwconv3 as D
+import _dwconv as D
 import _harness
 from _harness import DEV, guarded, intact, sync
 from _harness import lib  # noqa: F401

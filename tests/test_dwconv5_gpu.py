@@ -3,7 +3,7 @@ stride 1 and 2, with the bounds of tests/test_dwconv3_gpu.py.
 
 The shapes: an image smaller than the filter on both axes, a single row, odd sizes, OH = ceil(H / 2), C % 16 != 0 (24, 40), C % 32 != 0
 (40, 48, 144), B0's widest 5x5 layer (1152), borders between images.  The loops of dwconv5_fwd_kernel / dwconv5_wgrad_kernel whose trip
-count depends on the problem, and the shape that runs each more than once (tests/_efficientnet_ref.py::trips mirrors the geometry;
+count depends on the problem, and the shape that runs each more than once (tests/_dwconv.py::trips(..., k=5) mirrors the geometry;
 tests/test_efficientnet_cpu.py asserts these counts):
 
   rows of a segment (oh), row segments                         (3, 37, 41, 40): 16 rows, 3 segments at stride 1, 2 at stride 2
@@ -17,7 +17,7 @@ tests/test_efficientnet_cpu.py asserts these counts):
 import pytest
 import torch
 
-import _efficientnet_ref as E
+import _dwconv as D
 import _harness
 from _harness import DEV, dev, guarded, intact, sync
 from _harness import lib  # noqa: F401
@@ -25,7 +25,7 @@ from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
 
-CASES = [(shape, stride) for shape in E.SHAPES for stride in (1, 2)]
+CASES = [(shape, stride) for shape in D.SHAPES5 for stride in (1, 2)]
 
 
 def same_bits(a, b):
@@ -76,7 +76,7 @@ class Runner:
 def test_dwconv5_fwd_dgrad_wgrad(lib, shape, stride):
     hip = _harness.hip()
     N, H, W, C = shape
-    c = E.dw5_case(shape, stride)
+    c = D.dw5_case(shape, stride)
     assert lib.icamd_dwconv5_supported(N, H, W, C, stride) == 1
     run = Runner(lib, shape, stride)
     assert run.stats_rows > 0 and run.wsb > 0

@@ -12,7 +12,9 @@ import sys
 import pytest
 import torch
 
-import _efficientnet_ref as E
+import _dwconv as D
+from oracle import efficientnet_ref as E
+from oracle import ops_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_ENTRIES = {"icamd_dwconv5_supported": 5, "icamd_dwconv5_stats_rows": 5, "icamd_dwconv5_fwd": 10, "icamd_dwconv5_dgrad": 9,
@@ -175,10 +177,10 @@ def test_host_side_answers():
         assert lib.icamd_dwconv5_supported(*bad) == 0 and lib.icamd_dwconv5_stats_rows(*bad) == 0
         assert lib.icamd_dwconv5_wgrad_workspace_bytes(*bad) == 0
     # the geometry the tests name their loops by is the library's
-    for shape in E.SHAPES + [(256, 56, 56, 144), (256, 28, 28, 240), (256, 14, 14, 672), (256, 7, 7, 1152)]:
+    for shape in D.SHAPES5 + [(256, 56, 56, 144), (256, 28, 28, 240), (256, 14, 14, 672), (256, 7, 7, 1152)]:
         for stride in (1, 2):
-            assert lib.icamd_dwconv5_stats_rows(*shape, stride) == E.fwd_geometry(*shape, stride)["rows"]
-            assert lib.icamd_dwconv5_wgrad_workspace_bytes(*shape, stride) == E.wgrad_geometry(*shape, stride)["rows"] * 25 * shape[3] * 4
+            assert lib.icamd_dwconv5_stats_rows(*shape, stride) == D.fwd_geometry(*shape, stride)["rows"]
+            assert lib.icamd_dwconv5_wgrad_workspace_bytes(*shape, stride) == D.wgrad_geometry(*shape, stride)["rows"] * 25 * shape[3] * 4
     queries = (lib.icamd_bn_silu_squeeze_workspace_bytes, lib.icamd_se_silu_bwd_reduce_workspace_bytes, lib.icamd_bn_bwd_silu_workspace_bytes)
     assert all(q(2, 49, 144) > 0 for q in queries)
     assert lib.icamd_bn_bwd_silu_workspace_bytes(2, 49, 144) == lib.icamd_bn_bwd_workspace_bytes(98, 144)
@@ -203,8 +205,8 @@ def test_two_pass_reference_equals_fp64_autograd(N, HW, C, rd):
     g = torch.Generator().manual_seed(10 * N + C)
     r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)     # noqa: E731
     args = (r(N, HW, C) * 1.5 + r(C), r(C) + 2, r(C), r(rd, C), r(rd), r(C, rd), r(C), r(N, HW, C))
-    out, grads = E.se_block_two_pass(*args)
-    out64, grads64 = E.se_block_autograd(*args)
+    out, grads = R.se_block_two_pass(*args)
+    out64, grads64 = R.se_block_autograd(*args)
     assert torch.allclose(out, out64, rtol=1e-10, atol=1e-10)
     for k in grads64:
         assert torch.allclose(grads[k], grads64[k], rtol=1e-10, atol=1e-10), k
@@ -249,7 +251,7 @@ def test_reference_without_rounding_points_is_the_plain_network():
 def test_loop_counts_at_the_gpu_test_shapes():
     """what the docstring of tests/test_dwconv5_gpu.py says each shape drives through more than one trip: the issue's list runs every
     loop whose length depends on the problem more than once"""
-    t = {(shape, s): E.trips(*shape, s) for shape in E.SHAPES for s in (1, 2)}
+    t = {(shape, s): D.trips(*shape, s, k=5) for shape in D.SHAPES5 for s in (1, 2)}
     for name in next(iter(t.values())):
         assert any(v[name] > 1 for v in t.values()), name
     big = t[((3, 37, 41, 40), 1)]

@@ -1,7 +1,7 @@
-"""EfficientNet on the HIP kernels against tests/_efficientnet_ref.py::EfficientNetRef with the rounding points of the HIP path, under the
+"""EfficientNet on the HIP kernels against oracle/efficientnet_ref.py::EfficientNetRef with the rounding points of the HIP path, under the
 two protocols of tests/test_mobilenetv2_gpu.py with that file's multipliers and floors: the yardstick protocol of
 tests/_resnet_parity.py (the reference's own fp64 copy sets the noise every bound is a multiple of), and the gradients a second time
-under teacher forcing (forced_check below), where that noise is capped.
+under teacher forcing (tests/_parity.py::forced_check), where that noise is capped.
 
 efficientnet_test: stem 16; ds k3 -> 8; ir (k3, s2) -> 16 twice; ir (k5, s2) -> 24; ir (k5, s1) -> 32 twice; head 64 -- one block of every
 kind.  Input 64 x 64, batch 8, 10 classes: the feature maps are 32, 32, 16, 8, 8, so the last BatchNorms see 8 x 8 x 8 = 512 values per
@@ -24,11 +24,10 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-import _efficientnet_ref as E
-from _parity import forced_gradients, recorded_step, xent_backward
+from _parity import efficientnet_pair, forced_check, xent_backward
 from _resnet_parity import assert_hip_within_yardstick, hip_rows, parity_batch, yardstick
+from oracle import efficientnet_ref as E
 from oracle import ops_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -45,70 +44,12 @@ def _net(arch=ARCH, num_classes=C):
 
 
 def _pair(perturbed, seed=None):
-    return E.efficientnet_pair(ARCH, C, perturbed, SEEDS[perturbed] if seed is None else seed)
+    return efficientnet_pair(ARCH, C, perturbed, SEEDS[perturbed] if seed is None else seed)
 
 
-def hip_stored_tensors(net, ws):
-    """the HIP path's stored tensors of the step just run, in Tape order, NCHW fp32 on the host"""
-    nchw = lambda t: t.float().cpu().permute(0, 3, 1, 2).contiguous()     # noqa: E731
-    out = [nchw(ws["x8"][..., :3]), nchw(ws["y0"])]
-    for blk, b in zip(net.blocks, ws["blocks"]):
-        out += ([nchw(b["y1"])] if blk.kind == "ir" else []) + [nchw(b[k]) for k in ("y2", "a2", "y3", "out")]
-    return out + [nchw(ws["yh"]), nchw(ws["ah"]), ws["pooled"].float().cpu(), ws["logits"][:, :net.num_classes].float().cpu()]
-
-
-def negligible_gradients(ref, x, y):
-    """Names of the BatchNorm parameters whose TRUE gradient (fp64, no rounding points) is below 1e-3 of the gradient of the
-    convolution in front of them: the bias of a BatchNorm without activation in front of a convolution + BatchNorm (exactly zero: the
-    next batch mean removes a per-channel shift).  bf16 cannot resolve them: what any bf16 run computes there is rounding residue."""
-    exact = E.EfficientNetRef(ARCH, C, bf16_points=False).double()
-    exact.load_state_dict(ref.state_dict())
-    exact.train()
-    F.cross_entropy(exact(x.double()), y, label_smoothing=SMOOTHING).backward()
-    out, conv, params = {}, None, dict(exact.named_parameters())
-    for n, p in params.items():
-        if ".se." in n:
-            continue
-        if p.dim() == 4:
-            conv = n
-        elif p.dim() == 1 and conv is not None and float(p.grad.norm()) <= 1e-3 * float(params[conv].grad.norm()):
-            out[n] = conv
-    return out
-
-
-def forced_check(ref, net, x, y):
-    """Gradients of the HIP step just run (ws still holds it) against the reference forced onto the HIP path's stored tensors; the
-    yardstick is the reference forced onto its fp64 copy's tensors against that copy's gradients, capped at mean 8e-3 / worst 2.5e-2
-    (module docstring).  The HIP path gets the per-tensor and mean rules of tests/_resnet_parity.py::assert_hip_within_yardstick on
-    these rows.  The six biases whose true gradient is zero are held on their own: on every side at most 1e-2 of the gradient of the
-    convolution in front of them."""
-    ws = net._workspace(B, HW, HW)
-    hip_vals = hip_stored_tensors(net, ws)
-    zero = negligible_gradients(ref, x, y)
-    assert sorted(zero) == ["blocks.0.0.bn2.bias", "blocks.1.0.bn3.bias", "blocks.1.1.bn3.bias", "blocks.2.0.bn3.bias",
-                            "blocks.3.0.bn3.bias", "blocks.3.1.bn3.bias"]
-    twin = copy.deepcopy(ref).double()
-    vals64, g64 = recorded_step(twin, x, y, SMOOTHING)
-    assert [tuple(v.shape) for v in vals64] == [tuple(v.shape) for v in hip_vals] and len(hip_vals) == 35
-    gn, _ = forced_gradients(ref, vals64, x, y, SMOOTHING)                 # the yardstick: forced onto the fp64 copy
-    gh, loss = forced_gradients(ref, hip_vals, x, y, SMOOTHING)           # forced onto the HIP path
-    names = [n for n, _ in ref.named_parameters()]
-    rows = [(n, R.rel_l2(net.grad_of(n), gh[n]), R.rel_l2(g64[n].float(), gn[n])) for n in names if n not in zero]
-    assert len(rows) == len(names) - 6 == 83 - 6
-    mean_err, mean_noise = sum(r[1] for r in rows) / len(rows), sum(r[2] for r in rows) / len(rows)
-    worst, worst_noise = max(rows, key=lambda r: r[1]), max(rows, key=lambda r: r[2])
-    print(f"forced: {len(rows)} tensors, yardstick mean {mean_noise:.2e} worst {worst_noise[2]:.2e} at {worst_noise[0]}; HIP mean "
-          f"{mean_err:.2e} worst {worst[1]:.2e} (noise {worst[2]:.2e}) at {worst[0]}; loss {loss:.5f}")
-    for n, e, z in sorted(rows, key=lambda r: r[1] / max(r[2], 5e-3), reverse=True)[:8]:
-        print(f"    {n}: HIP {e:.2e}, noise {z:.2e}")
-    assert mean_noise <= 8e-3 and worst_noise[2] <= 2.5e-2
-    assert mean_err <= 2.0 * max(mean_noise, 1e-3)
-    for n, e, z in rows:
-        assert e <= 3.0 * max(z, 5e-3), (n, e, z)
-    for n, conv in zero.items():
-        for side, g, gc in (("HIP", net.grad_of(n), net.grad_of(conv)), ("reference", gh[n], gh[conv]), ("fp64 copy", g64[n], g64[conv])):
-            ratio = float(torch.linalg.vector_norm(g.double()) / torch.linalg.vector_norm(gc.double()))
-            assert ratio <= 1e-2, (n, side, ratio)
+# the six biases whose true gradient is zero: a BatchNorm without activation in front of a convolution + BatchNorm
+ZERO_GRADIENT = ["blocks.0.0.bn2.bias", "blocks.1.0.bn3.bias", "blocks.1.1.bn3.bias", "blocks.2.0.bn3.bias", "blocks.3.0.bn3.bias",
+                 "blocks.3.1.bn3.bias"]
 
 
 @pytest.mark.parametrize("perturbed", [False, True], ids=["timm_default_init", "perturbed_batchnorm_and_se"])
@@ -132,7 +73,8 @@ def test_one_training_step_and_eval_logits(perturbed):
     if perturbed:
         assert float(gates.min()) < 0.2 and float(gates.max()) > 0.8
     # the free-running protocol drifts (tests/test_mobilenetv2_gpu.py says why): the gradients once more under teacher forcing
-    forced_check(ref, net, x, y)
+    forced_check(ref, net, E.EfficientNetRef(ARCH, C, bf16_points=False).double(), x, y, SMOOTHING, negligible=ZERO_GRADIENT,
+                 n_params=83, skip=(".se.",))
     assert net.num_batches_tracked == 1
     # eval-mode logits after that step, every side on its own running statistics; the yardstick is again the fp64 twin
     twin.train()

@@ -13,7 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-import _dwconv3 as D
+import _dwconv as D
 from oracle.mobilenet_ref import MobileNetV2Ref, WIDTHS, layer_list, param_count, plain_sequential
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

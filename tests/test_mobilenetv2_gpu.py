@@ -1,6 +1,7 @@
 """MobileNetV2 on the HIP kernels against oracle/mobilenet_ref.py::MobileNetV2Ref with the rounding points of the HIP path, under the
 yardstick protocol of tests/_resnet_parity.py: the reference's own fp64 copy sets the noise every bound is a multiple of.
-The gradients are held a second time under teacher forcing (forced_check below), where that noise is capped at 8e-3 / 2.5e-2.
+The gradients are held a second time under teacher forcing (tests/_parity.py::forced_check), where that noise is capped at 8e-3 /
+2.5e-2.
 
 mobilenetv2_test: stem 16; ds -> 8; ir (r2, s2) -> 16; ir (r1, s2) -> 24; ir (r2, s1) -> 32; head 64 -- a stride-2 block, stride-1
 blocks with and without residual, the depthwise-separable block.  Input 64 x 64, batch 8, 10 classes: the feature maps are 32, 32, 16,
@@ -12,10 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-from _parity import forced_gradients, mobilenet_pair, negligible_gradients, recorded_step, xent_backward
+from _parity import forced_check, mobilenet_pair, xent_backward
 from _resnet_parity import assert_hip_within_yardstick, hip_rows, parity_batch, yardstick
 from oracle import ops_ref as R
-from oracle.mobilenet_ref import param_count
+from oracle.mobilenet_ref import MobileNetV2Ref, param_count
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -30,49 +31,6 @@ def _net(arch=ARCH, num_classes=C):
 
 def _pair(perturbed, seed=0):
     return mobilenet_pair(ARCH, C, perturbed, seed)
-
-
-def hip_stored_tensors(net, ws):
-    """the HIP path's stored tensors of the step just run, in Tape order, NCHW fp32 on the host"""
-    nchw = lambda t: t.float().cpu().permute(0, 3, 1, 2).contiguous()     # noqa: E731
-    out = [nchw(ws["x8"][..., :3]), nchw(ws["y0"])]
-    for blk, b in zip(net.blocks, ws["blocks"]):
-        out += ([nchw(b["y1"])] if blk.kind == "ir" else []) + [nchw(b[k]) for k in ("y2", "a2", "y3", "out")]
-    return out + [nchw(ws["yh"]), nchw(ws["ah"]), ws["pooled"].float().cpu(), ws["logits"][:, :net.num_classes].float().cpu()]
-
-
-def forced_check(ref, net, x, y, expect_negligible):
-    """Gradients of the HIP step just run (ws still holds it) against the reference forced onto the HIP path's stored tensors.
-    Caps on the yardstick (reference forced onto its fp64 copy's tensors, against that copy's gradients): mean 8e-3 -- the tightest
-    cap a family of this project puts on its yardstick (tests/test_resnet_family_gpu.py) --, worst 2.5e-2, three relative bf16 steps
-    (2^-7): with masks and statistics pinned, what is left is the rounding of the stored gradient tensors.  The HIP path gets the
-    per-tensor and mean rules of tests/_resnet_parity.py::assert_hip_within_yardstick on these rows.  The parameters whose true
-    gradient is zero are taken out of the rows and held on their own: on every side at most 1e-2 of the gradient of the convolution
-    in front of them (rounding residue: a few bf16 steps of that gradient's terms)."""
-    ws = net._workspace(B, HW, HW)
-    hip_vals = hip_stored_tensors(net, ws)
-    zero = negligible_gradients(ref, x, y, SMOOTHING)
-    assert len(zero) == expect_negligible, sorted(zero)
-    twin = copy.deepcopy(ref).double()
-    vals64, g64 = recorded_step(twin, x, y, SMOOTHING)
-    assert [tuple(v.shape) for v in vals64] == [tuple(v.shape) for v in hip_vals] and len(hip_vals) == 35
-    gn, _ = forced_gradients(ref, vals64, x, y, SMOOTHING)                 # the yardstick: forced onto the fp64 copy
-    gh, loss = forced_gradients(ref, hip_vals, x, y, SMOOTHING)           # forced onto the HIP path
-    names = [n for n, _ in ref.named_parameters()]
-    rows = [(n, R.rel_l2(net.grad_of(n), gh[n]), R.rel_l2(g64[n].float(), gn[n])) for n in names if n not in zero]
-    assert len(rows) == len(names) - expect_negligible == 59 - expect_negligible
-    mean_err, mean_noise = sum(r[1] for r in rows) / len(rows), sum(r[2] for r in rows) / len(rows)
-    worst, worst_noise = max(rows, key=lambda r: r[1]), max(rows, key=lambda r: r[2])
-    print(f"forced: {len(rows)} tensors, yardstick mean {mean_noise:.2e} worst {worst_noise[2]:.2e} at {worst_noise[0]}; HIP mean "
-          f"{mean_err:.2e} worst {worst[1]:.2e} (noise {worst[2]:.2e}) at {worst[0]}; loss {loss:.5f}")
-    assert mean_noise <= 8e-3 and worst_noise[2] <= 2.5e-2
-    assert mean_err <= 2.0 * max(mean_noise, 1e-3)
-    for n, e, z in rows:
-        assert e <= 3.0 * max(z, 5e-3), (n, e, z)
-    for n, conv in zero.items():
-        for side, g, gc in (("HIP", net.grad_of(n), net.grad_of(conv)), ("reference", gh[n], gh[conv]), ("fp64 copy", g64[n], g64[conv])):
-            ratio = float(torch.linalg.vector_norm(g.double()) / torch.linalg.vector_norm(gc.double()))
-            assert ratio <= 1e-2, (n, side, ratio)
 
 
 @pytest.mark.parametrize("perturbed", [False, True], ids=["timm_default_init", "perturbed_batchnorm"])
@@ -103,7 +61,8 @@ def test_one_training_step_and_eval_logits(perturbed):
     # path's own stored tensors -- input, every convolution output, a2, block outputs, head, pooled, logits --, so masks and batch
     # statistics are those of the same numbers and nothing drifts.  Its yardstick is the same construction between the reference and
     # its fp64 copy; that one is capped, and so is what it admits.
-    forced_check(ref, net, x, y, expect_negligible=6 if perturbed else 12)
+    forced_check(ref, net, MobileNetV2Ref(ARCH, C, bf16_points=False).double(), x, y, SMOOTHING, negligible=6 if perturbed else 12,
+                 n_params=59)
     assert net.num_batches_tracked == 1
     # eval-mode logits after that step, every side on its own running statistics; the yardstick is again the fp64 twin, which took
     # the same training forward

@@ -10,8 +10,9 @@ GPU (tests/_stream_order.py states the access model, the extents and how happens
     such a change is named by its launches and its buffer even where it also moves the recorded trace (compared in a test of its own);
   - hand-written traces of a few records pin what counts as a conflict and as an ordering.
 
-MobileNetV2 (`mobilenetv2_test`, two cases of the generator's table) has no side lane, so its hazards and unjoined launches are
-empty by construction and the hook check is the one that bears on it.
+MobileNetV2 (`mobilenetv2_test`, two cases of the generator's table) and EfficientNet (`efficientnet_test`, `efficientnet_b1`, one
+case each) have no side lane, so their hazards and unjoined launches are empty by construction and the hook check is the one that
+bears on them.
 """
 import json
 import os
@@ -28,10 +29,13 @@ with open(os.path.join(S.HERE, "golden", "call_traces.json")) as f:
 # the cases whose backward stays on one stream: the lane's switch is off, the model has no lane, or the route keeps it off
 LANE_OFF = {"vit_tiny_test/lane_off", "swin_test/no_drop", "swin_test/drop", "swin_test_w12/no_drop", "swin_test_w12/drop",
             "convnext_test/lane_off", "convnext_test/unfolded_lane_off", "convnextv2_test/no_drop_lane_off", "resnet50/fused_bnbwd",
-            "resnet50/one_stream_unfolded", "mobilenetv2_test/default", "mobilenetv2_test/onload"}
+            "resnet50/one_stream_unfolded", "mobilenetv2_test/default", "mobilenetv2_test/onload", "efficientnet_test/default",
+            "efficientnet_b1/ds_skip"}
 CASE_IDS = list(G.CASES)
 LANE_ON = [c for c in CASE_IDS if c not in LANE_OFF]
 MOBILENET = "mobilenetv2_test/default"
+EFFICIENTNET = "efficientnet_test/default"
+ONE_STREAM_MBCONV = (MOBILENET, EFFICIENTNET, "efficientnet_b1/ds_skip")
 
 
 @pytest.fixture(scope="module")
@@ -156,11 +160,12 @@ def test_observing_leaves_the_trace_as_recorded(runs, case_id):
 
 
 def test_nineteen_cases_run_the_lane():
-    assert len(LANE_ON) == 19 and LANE_OFF < set(CASE_IDS) and len(CASE_IDS) == 31 and CASE_IDS == list(FIXTURE["cases"])
+    assert len(LANE_ON) == 19 and LANE_OFF < set(CASE_IDS) and len(CASE_IDS) == 33 and CASE_IDS == list(FIXTURE["cases"])
 
 
-def test_mobilenetv2_is_ordered(runs):
-    run = runs[MOBILENET]
+@pytest.mark.parametrize("case_id", ONE_STREAM_MBCONV)
+def test_mobilenetv2_is_ordered(runs, case_id):
+    run = runs[case_id]
     assert [n for n, _, _ in run.backward] == ["backward", "backward_accumulate"]
     writes = [a for a in run.accesses if a.base == run.grad_base and a.write and any(lo <= a.index < hi for _, lo, hi in run.backward)]
     written = {run.describe(a.base, a.start) for a in writes}
@@ -315,7 +320,8 @@ def test_a_hook_without_the_lanes_events_is_reported(recorders, monkeypatch, cas
 
 
 @pytest.mark.parametrize("case_id, module, cls", [("convnext_test/routed", "convnext", "ConvNeXt"), ("resnet50/routed", "nets", "ResNet"),
-                                                  (MOBILENET, "mobilenet", "MobileNetV2")])
+                                                  (MOBILENET, "mobilenet", "MobileNetV2"),
+                                                  (EFFICIENTNET, "efficientnet", "EfficientNet")])
 def test_a_hook_called_one_block_early_is_reported(recorders, runs, monkeypatch, case_id, module, cls):
     """Every hook announces the range the NEXT hook of the unbroken pass announces: the block in between has not run yet."""
     import importlib
